@@ -13,9 +13,11 @@ One step = one pass of the hot path over one synthetic batch that is already res
        soft-margin triplet loss (diagonal all-gather + scalar all-reduce), rank counts for the local
        queries                                                  (A7-A10, A12, :297-382, :543-552)
 Per-GPU batch is fixed (weak scaling); value = global pairs / max-over-ranks step time.
-Prints ONE JSON line on rank 0. At N=1 the line also carries one compact block per other single-GPU BASELINE config
-(config 1 cvig_baseline, the config-2 training step, config 4 cvig_semantic on the bf16 MFMA, config 5 retrieval), each
-measured in this run with its dominant kernel's roofline; `--no-side-blocks` leaves them out.
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the K steps and prints the line (with --dump-outputs DIR it
+first writes what the last timed step returned). `--full` adds everything else: the cpu_baseline of the headline, at N=1 one
+compact block per other single-GPU BASELINE config (config 1 cvig_baseline, the config-2 training step, config 4 cvig_semantic
+on the bf16 MFMA, config 5 retrieval), each measured in this run with its dominant kernel's roofline (`--no-side-blocks` leaves
+them out), and at N>1 the training step in the same group and the standalone collectives microbench.
 """
 import argparse
 import hashlib
@@ -36,6 +38,8 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0  # same table, dense bf16 MFMA (no sparsity)
 PEAK_HBM_GBS = 8000.0           # same guide: HBM3E ~8 TB/s
 LINE_BUDGET = 6144             # bytes of the one stdout line (the driver's record keeps the last 8 KB of stdout)
 DOMINANT = (128, 1, False, 8)  # conv3x3_nhwc_f32_kernel<128,1,false,8,0,9> (TN, SH, POOL, NW, GEO, TAPS): layers 5,10,12,17,19,21 at B=128
+DUMP_BUDGET = 60 << 20         # data bytes of --dump-outputs, all arrays together (the .npy headers stay within 64 MB with it)
+DUMP_SEED = 20240              # the element sample of an array over its share of DUMP_BUDGET
 
 
 def make_inputs(cvig_fov, ops, synth, batch, fov, seed, device, channels=3):
@@ -218,7 +222,7 @@ class StepBench(object):
             self.optimizer.step()
         with torch.no_grad():
             ranks = self.ops.rank_count(d, self.rank * self.B)
-        return loss.detach(), ranks, ori
+        return loss.detach(), ranks, ori, d.detach()
 
     def infer_step(self):
         phase = self.parallel.phase
@@ -230,7 +234,7 @@ class StepBench(object):
             with phase('overhead_all_gather'):
                 ov_all = self.parallel._all_gather_cat(ov) if self.world > 1 else ov     # global gallery; surfaces stay local
             loss, ranks, ori, d = self.cvig_fov.evaluate_global_batch(ov_all, su, self.rank * self.B)
-        return loss, ranks, ori
+        return loss, ranks, ori, d
 
     def graph_body(self, g_raw, o_raw):
         with torch.no_grad():
@@ -251,7 +255,7 @@ class StepBench(object):
         timer = self.parallel.PHASES = None if self.graph else self.parallel.PhaseTimer()
         t0 = time.perf_counter()
         for _ in range(steps):
-            loss, ranks, ori = self.step()
+            out = self.step()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -260,6 +264,9 @@ class StepBench(object):
         prof, ops.PROFILE = ops.PROFILE, None
         self.parallel.PHASES = None
         self.phases = timer.summary(steps) if timer is not None else {}
+        loss, ranks, ori = out[:3]
+        # what the last timed step returned to its caller, this rank's share (the whole-step hipGraph returns no distances)
+        self.outputs = dict(zip(('loss', 'ranks', 'orientation', 'distance'), out))
         if world > 1:
             t = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -441,7 +448,17 @@ def main():
     ap.add_argument('--decode-scaling-seconds', type=float, default=1.0)
     ap.add_argument('--no-ring', action='store_true', help='e2e: torch DataLoader staging (shared-memory pickling + pin_memory thread) instead of ring.PinnedRing')
     ap.add_argument('--workers', type=int, default=12, help='e2e: DataLoader workers (reference: 12, model/cvig_fov.py:402)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the timed step: the headline\'s cpu_baseline, the side blocks (the other BASELINE configs, '
+                         'precisions, batch sizes, retrieval, HBM kernels, data path) and, in a process group, the training step run '
+                         'behind the inference headline and the collectives microbench. Off: set-up, warm-up, timed steps, line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='infer / train / retrieval: after the timed steps, write what the last timed step returned on rank 0 as '
+                         'DIR/<name>.npy (float32, or float64 for integer arrays), %d MiB of data at most in all: an array over its '
+                         'share is replaced by a fixed, seeded sample of its elements' % (DUMP_BUDGET >> 20))
     a = ap.parse_args()
+    if a.dump_outputs and a.mode not in ('infer', 'train', 'retrieval'):
+        sys.exit('--dump-outputs: the timed step of --mode %s returns no arrays to write' % a.mode)
 
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -452,6 +469,7 @@ def main():
         sys.exit(launch_ranks(a.gpus))
     if world != a.gpus:
         sys.exit('bench.py --gpus %d was started with WORLD_SIZE=%d' % (a.gpus, world))
+    torch.manual_seed(1234)          # names the run: Dropout2d masks of the training step are drawn from torch.initial_seed()
     if a.single_device:
         local = 0
     torch.cuda.set_device(local)
@@ -540,22 +558,53 @@ def stamp(what, t0=[None]):
     sys.stderr.flush()
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor or array} -> path/<name>.npy, float32 (float64 for integer and float64 arrays, exact), so that two
+    builds can be compared output for output on the same inputs. An array larger than its share of DUMP_BUDGET is written as a fixed
+    sample of its flattened elements: sorted indices drawn without replacement from DUMP_SEED, the same for every run of that shape."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        v = v.detach().cpu() if isinstance(v, torch.Tensor) else v
+        if isinstance(v, torch.Tensor) and not v.is_floating_point():
+            v = v.to(torch.float64)
+        elif isinstance(v, torch.Tensor) and v.dtype != torch.float64:
+            v = v.to(torch.float32)
+        v = np.asarray(v)
+        host[name] = v.astype(np.float64 if v.dtype.kind in 'iub' or v.dtype == np.float64 else np.float32)
+    share = DUMP_BUDGET // max(1, len(host))
+    for name, v in host.items():
+        note = ''
+        if v.nbytes > share:
+            k = share // v.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(v.size, size=k, replace=False))
+            note = ' (seeded sample of %d of %d elements, shape %s)' % (k, v.size, list(v.shape))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), v)
+        stamp('dump-outputs: %s %s %s%s' % (os.path.join(path, name + '.npy'), v.dtype, list(v.shape), note))
+
+
 def step_line(a, rank, world, device, cvig_fov, ops):
-    """The headline line. Order: the headline measurement, then its cpu_baseline, and only then -- in a CHILD
-    process whose failure cannot lose either -- the blocks of the other single-GPU BASELINE configs. stdout gets the compact line
-    (<= LINE_BUDGET bytes), the full record goes to --detail-out and stderr."""
+    """The headline line. Order: the headline measurement (and --dump-outputs), then -- with --full only -- its
+    cpu_baseline, and only then -- in a CHILD process whose failure cannot lose either -- the blocks of the other single-GPU BASELINE
+    configs. stdout gets the compact line (<= LINE_BUDGET bytes), the full record goes to --detail-out and stderr."""
     stamp('start (%s %s %s B=%d, %d rank(s))' % (a.model, a.mode, a.precision, a.batch, world))
     sb = StepBench(a.model, a.mode, a.precision, a.batch, a.fov, rank, world, device, a.graph).run(a.steps, a.warmup)
     out = sb.line()
     stamp('headline: %.1f pairs/s, %.3f ms per step' % (sb.value, sb.ms))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, sb.outputs)
     out['collectives'] = collectives_info(a, rank, world, device, sb.phases, sb.ms)          # every rank takes part; rank 0 prints
     grouped = world > 1 or a.pg_of_one
     headline = a.mode == 'infer' and a.precision == 'fp32' and not a.graph
-    cpu_args = (sb.ground_raw[:a.cpu_pairs].cpu(), sb.ov_raw[:a.cpu_pairs].cpu(), sb.wts, sb.semantic) if headline and rank == 0 else None
+    cpu_leg_on = a.full and headline and not a.no_cpu_baseline
+    cpu_args = (sb.ground_raw[:a.cpu_pairs].cpu(), sb.ov_raw[:a.cpu_pairs].cpu(), sb.wts, sb.semantic) if cpu_leg_on and rank == 0 else None
     phases = sb.phases
     del sb
     torch.cuda.empty_cache()
-    if grouped and a.mode == 'infer' and not a.graph and not a.no_train_step:
+    if a.full and grouped and a.mode == 'infer' and not a.graph and not a.no_train_step:
         # BASELINE configs[2] is a DDP TRAINING config (model/cvig_fov.py:444-461; nn.DataParallel, model/cvig_baseline.py:339-343): the
         # N > 1 line therefore also runs the training step in the same process group -- the overhead-embedding all-gather, the
         # reduce-scatter of their gradients and the two asynchronous bucket all-reduces inside a real step, not only standalone
@@ -566,12 +615,12 @@ def step_line(a, rank, world, device, cvig_fov, ops):
         stamp('train step in the same group: %.1f pairs/s, %.3f ms per step' % (tb.value, tb.ms))
         del tb
         torch.cuda.empty_cache()
-    if grouped and not a.no_microbench:
+    if a.full and grouped and not a.no_microbench:
         out['collectives']['microbench'] = collectives_microbench(a, rank, world, device, phases)
         stamp('collectives microbench')
     out['guards'] = guards_block(ops)
-    side = world == 1 and headline and not a.no_side_blocks and a.model == 'fov' and a.fov == 360 and a.batch == 128
-    if headline and not a.no_cpu_baseline:
+    side = a.full and world == 1 and headline and not a.no_side_blocks and a.model == 'fov' and a.fov == 360 and a.batch == 128
+    if cpu_leg_on:
         def cpu_leg():
             if rank == 0:
                 out['cpu_baseline'] = cpu_baseline(a, *cpu_args)
@@ -1283,6 +1332,8 @@ def retrieval(a, rank, world, device, cvig_fov, ops):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     prof, ops.PROFILE = ops.PROFILE, None
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {'ranks': ranks_h, 'topk_distance': vals, 'topk_index': idx})
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

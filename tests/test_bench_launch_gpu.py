@@ -49,7 +49,7 @@ def _run_bench(*args, timeout=900):
 def test_bench_two_ranks_self_launched_infer():
     one = _run_bench('--gpus', '1', '--steps', '1', '--warmup', '1', '--batch', '8', '--no-cpu-baseline', '--no-side-blocks')
     two = _run_bench('--gpus', '2', '--backend', 'gloo', '--single-device', '--steps', '1', '--warmup', '1', '--batch', '8',
-                     '--no-cpu-baseline')
+                     '--no-cpu-baseline', '--full')
     assert two['n_gpus'] == 2 and two['config']['global_batch'] == 16 and two['config']['pairs_per_gpu'] == 8
     assert two['recall']['N'] == 16 and two['unit'] == 'pairs/s' and two['value'] > 0 and two['scaling'] == 'weak'
     assert one['n_gpus'] == 1 and one['recall']['N'] == 8
@@ -119,7 +119,7 @@ def test_bench_one_rank_under_the_launcher_equals_the_plain_run():
 
 def test_bench_two_ranks_self_launched_train_and_retrieval():
     tr = _run_bench('--gpus', '2', '--backend', 'gloo', '--single-device', '--mode', 'train', '--steps', '1', '--warmup', '1',
-                    '--batch', '8')
+                    '--batch', '8', '--full')
     assert tr['n_gpus'] == 2 and 'training step' in tr['metric'] and np.isfinite(tr['loss'])
     pp = tr['_detail']['collectives']['per_phase_ms']
     mb = tr['collectives']['microbench']
@@ -195,7 +195,8 @@ def test_bench_collectives_block_through_rccl_in_a_world_of_one():
     """`--pg-of-one`: the bench's collectives block and microbench inside a real process group on backend nccl = RCCL (one rank: a second
     one cannot share the test box's GPU) -- the RCCL-only branches of the N > 1 line (device_id init, RCCL version, all_gather_into_tensor,
     the counted all-reduce) execute on hardware before the first multi-GPU run does."""
-    one = _run_bench('--gpus', '1', '--pg-of-one', '--steps', '1', '--warmup', '1', '--batch', '8', '--no-cpu-baseline', '--no-side-blocks')
+    one = _run_bench('--gpus', '1', '--pg-of-one', '--steps', '1', '--warmup', '1', '--batch', '8', '--no-cpu-baseline', '--no-side-blocks',
+                     '--full')
     c = one['collectives']
     assert c['backend'] == 'nccl (RCCL)' and c['world'] == 1 and c['rccl_version'] and c['all_reduce_of_ones'] == 1.0 and c['ranks_seen'] == 1
     mb = c['microbench']
@@ -211,8 +212,33 @@ def test_bench_two_ranks_with_the_cpu_baseline_behind_the_group():
     """N > 1 with the cpu_baseline on: rank 0 times the CPU port AFTER every rank has left the process group (no rank sits in a
     collective meanwhile); the line carries the three legs of BASELINE.md section 4."""
     two = _run_bench('--gpus', '2', '--backend', 'gloo', '--single-device', '--steps', '1', '--warmup', '1', '--batch', '4',
-                     '--cpu-pairs', '2', '--no-microbench')
+                     '--cpu-pairs', '2', '--no-microbench', '--full')
     c = two['cpu_baseline']
     assert c['kind'] == 'port' and c['passes'] == 3 and len(c['pass_pairs_per_s']) == 3 and c['value'] > 0
     assert c['train_pairs_per_s'] > 0 and c['rank_ms_per_query'] > 0
     assert two['n_gpus'] == 2 and two['collectives']['ranks_seen'] == 2 and two['train_step']['value'] > 0
+
+
+def test_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain `bench.py --gpus 1` times exactly --steps steps and carries nothing that needs runs of its own (cpu_baseline, side
+    blocks: --full); --dump-outputs writes what the last timed step returned (loss, ranks, orientation, distances), the same bits from
+    run to run on the same arguments."""
+    dirs = [str(tmp_path / 'a'), str(tmp_path / 'b')]
+    lines = [_run_bench('--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '8', '--dump-outputs', d) for d in dirs]
+    for line in lines:
+        assert line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0
+        assert abs(line['value'] - 8 * 1e3 / line['ms_per_step']) <= 1e-3 * line['value']        # one step's time, not the run's
+        for k in ('cpu_baseline', 'side', 'train_step'):
+            assert k not in line, k
+        assert 'microbench' not in line['collectives']
+    want = {'loss': ((), np.float32), 'ranks': ((8,), np.float64), 'orientation': ((8, 8), np.float64), 'distance': ((8, 8), np.float32)}
+    got = [{n: np.load(os.path.join(d, n + '.npy')) for n in want} for d in dirs]
+    for d in dirs:
+        assert sorted(os.listdir(d)) == sorted(n + '.npy' for n in want)
+    for n, (shape, dtype) in want.items():
+        assert got[0][n].shape == shape and got[0][n].dtype == dtype, (n, got[0][n].shape, got[0][n].dtype)
+        assert np.array_equal(got[0][n], got[1][n]), n
+    assert float(got[0]['loss']) == lines[0]['loss']
+    assert float(np.mean(got[0]['ranks'] <= 1) * 100) == lines[0]['recall']['top1_pct']
+    d = got[0]['distance']
+    assert np.array_equal(got[0]['ranks'], (d <= np.diagonal(d)[None, :]).sum(axis=0))          # ops.rank_count on the dumped distances

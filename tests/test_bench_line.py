@@ -122,3 +122,25 @@ def test_sweep_record_is_one_row_per_point(tmp_path):
     text, line, detail, rc, err = _emit(sweep, tmp_path, mode='sweep')
     assert len(text) < bench.LINE_BUDGET and len(line['points']) == 8 and len(line['points'][0]) == len(line['points_columns'])
     assert 'kernels' in detail['points'][0]
+
+
+def test_dump_outputs_are_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: integer arrays go out as float64 (exact), float32 as float32; an array over its share of the budget is replaced
+    by the same seeded sample of its elements in every run."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, 'DUMP_BUDGET', 4096)
+    dist = torch.randn((64, 64), generator=torch.Generator().manual_seed(5))
+    arrays = {'loss': torch.tensor(0.25), 'ranks': torch.arange(10, dtype=torch.int32), 'distance': dist}
+    dirs = [str(tmp_path / 'a'), str(tmp_path / 'b')]
+    with redirect_stderr(io.StringIO()):
+        for d in dirs:
+            bench.dump_outputs(d, arrays)
+    got = [{n: np.load(os.path.join(d, n + '.npy')) for n in arrays} for d in dirs]
+    assert got[0]['loss'].dtype == np.float32 and got[0]['loss'].shape == () and float(got[0]['loss']) == 0.25
+    assert got[0]['ranks'].dtype == np.float64 and np.array_equal(got[0]['ranks'], np.arange(10))
+    s = got[0]['distance']
+    assert s.dtype == np.float32 and s.ndim == 1 and 0 < s.nbytes <= 4096 // 3 and np.isin(s, dist.numpy()).all()
+    assert sum(os.path.getsize(os.path.join(dirs[0], n + '.npy')) - 128 for n in arrays) <= 4096
+    for n in arrays:
+        assert np.array_equal(got[0][n], got[1][n]), n

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$R"
 O=gpurun_out/final
 mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 python3 bench.py --mode train > $O/bench_train.json 2> $O/bench_train.err
 python3 bench.py --precision bf16 > $O/bench_bf16.json 2> $O/bench_bf16.err
 python3 bench.py --precision fp16x3 > $O/bench_fp16x3.json 2> $O/bench_fp16x3.err
@@ -17,12 +17,12 @@ python3 bench.py --precision fp16x3 --mode train > $O/bench_fp16x3_train.json 2>
 python3 bench.py --mode train --precision bf16 > $O/bench_bf16_train.json 2> $O/bench_bf16_train.err
 python3 bench.py --model semantic --precision bf16 > $O/bench_semantic_bf16.json 2> $O/bench_semantic_bf16.err
 python3 bench.py --model semantic --mode train --precision bf16 > $O/bench_semantic_bf16_train.json 2> $O/bench_semantic_bf16_train.err
-python3 bench.py --model semantic > $O/bench_semantic.json 2> $O/bench_semantic.err
+python3 bench.py --model semantic --full > $O/bench_semantic.json 2> $O/bench_semantic.err
 python3 bench.py --model semantic --mode train > $O/bench_semantic_train.json 2> $O/bench_semantic_train.err
-python3 bench.py --fov 70 > $O/bench_fov70.json 2> $O/bench_fov70.err
+python3 bench.py --fov 70 --full > $O/bench_fov70.json 2> $O/bench_fov70.err
 python3 bench.py --mode retrieval --steps 2 --warmup 1 > $O/bench_retrieval.json 2> $O/bench_retrieval.err
 echo benches done
-rocprofv3 --kernel-trace --stats -d $O/prof -o p --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/prof.log
+rocprofv3 --kernel-trace --stats -d $O/prof -o p --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --full > $O/bench_under_rocprof.json 2> $O/prof.log
 rocprofv3 --kernel-trace --stats -d $O/prof_train -o p --output-format csv -- python3 bench.py --mode train --steps 5 --warmup 2 > $O/train_under_rocprof.json 2> $O/prof_train.log
 rocprofv3 --kernel-trace --stats -d $O/prof_bf16 -o p --output-format csv -- python3 bench.py --precision bf16 --steps 5 --warmup 2 > $O/bf16_under_rocprof.json 2> $O/prof_bf16.log
 rocprofv3 --kernel-trace --stats -d $O/prof_fp16x3 -o p --output-format csv -- python3 bench.py --precision fp16x3 --steps 5 --warmup 2 > $O/fp16x3_under_rocprof.json 2> $O/prof_fp16x3.log
@@ -31,8 +31,8 @@ rocprofv3 --kernel-trace --stats -d $O/prof_bf16_train -o p --output-format csv 
 echo stats done
 for m in "infer:" "train:--mode train" "bf16:--precision bf16" "bf16_train:--mode train --precision bf16" "fp16x3:--precision fp16x3"; do
   tag=${m%%:*}; flags=${m#*:}
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch_$tag -o p --output-format csv -- python3 bench.py $flags --steps 2 --warmup 1 --no-cpu-baseline > $O/pmc_fetch_$tag.json 2> $O/pmc_fetch_$tag.log
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write_$tag -o p --output-format csv -- python3 bench.py $flags --steps 2 --warmup 1 --no-cpu-baseline > $O/pmc_write_$tag.json 2> $O/pmc_write_$tag.log
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch_$tag -o p --output-format csv -- python3 bench.py $flags --steps 2 --warmup 1 --no-cpu-baseline --full > $O/pmc_fetch_$tag.json 2> $O/pmc_fetch_$tag.log
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write_$tag -o p --output-format csv -- python3 bench.py $flags --steps 2 --warmup 1 --no-cpu-baseline --full > $O/pmc_write_$tag.json 2> $O/pmc_write_$tag.log
   echo pmc $tag done
 done
 python3 tools/make_traffic.py 128 infer:$O/pmc_fetch_infer/p_counter_collection.csv:$O/pmc_write_infer/p_counter_collection.csv \
@@ -42,7 +42,7 @@ python3 tools/make_traffic.py 128 infer:$O/pmc_fetch_infer/p_counter_collection.
   fp16x3:$O/pmc_fetch_fp16x3/p_counter_collection.csv:$O/pmc_write_fp16x3/p_counter_collection.csv > $O/traffic.json
 for m in "infer:" "train:--mode train" "bf16:--precision bf16" "bf16_train:--mode train --precision bf16" "fp16x3:--precision fp16x3"; do
   tag=${m%%:*}; flags=${m#*:}
-  rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/pmc_mfma_$tag -o p --output-format csv -- python3 bench.py $flags --steps 2 --warmup 1 --no-cpu-baseline > $O/pmc_mfma_$tag.json 2> $O/pmc_mfma_$tag.log
+  rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/pmc_mfma_$tag -o p --output-format csv -- python3 bench.py $flags --steps 2 --warmup 1 --no-cpu-baseline --full > $O/pmc_mfma_$tag.json 2> $O/pmc_mfma_$tag.log
 done
 python3 tools/make_mfma_util.py infer:$O/pmc_mfma_infer/p_counter_collection.csv train:$O/pmc_mfma_train/p_counter_collection.csv \
   bf16:$O/pmc_mfma_bf16/p_counter_collection.csv bf16_train:$O/pmc_mfma_bf16_train/p_counter_collection.csv \
