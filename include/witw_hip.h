@@ -219,6 +219,46 @@ int witw_triplet_loss_slab_bwd(const float* distance, const float* diag, const f
 int witw_triplet_loss_bwd(const float* distance, const float* workspace, const float* grad_loss /*[1]*/,
                           float* grad_distance /*[B,B]*/, int B, float alpha, void* stream);
 
+/* ---- batch-hard soft-margin triplet loss (Hermans et al. 2017; opt-in, not in the reference). With Dm = D whose diagonal is
+ * +inf: rv/ri = row minima / argmins of Dm (overhead anchor -> hardest negative surface), cv/ci = column minima / argmins
+ * (surface anchor -> hardest negative overhead); loss = (sum_i softplus(a(d_i - rv_i)) + sum_j softplus(a(d_j - cv_j))) / (2B),
+ * softplus(x) = log(1+exp(x)). Selection as torch.min: a NaN is the minimum at the first NaN's index, else ties go to the lowest
+ * index. Indices are int64 GLOBAL row / column numbers. Fixed-order reductions, no atomics: bitwise reproducible.
+ * workspace: witw_batch_hard_workspace_bytes(Bo, Bs) bytes (-1 for a bad shape). */
+long long witw_batch_hard_workspace_bytes(int Bo, int Bs);
+/* full form on D[B,B] -> rv, ri, cv, ci [B] and the loss [1] */
+int witw_batch_hard_fwd(const float* distance, int B, float alpha, float* rv, long long* ri, float* cv, long long* ci, float* loss,
+                        void* workspace, void* stream);
+/* slab form on the column slab D[Bo][Bs] of the global columns [col0, col0+Bs): rv/ri [Bo] = row minima over THESE columns only
+ * (reduce them over the ranks with witw_batch_hard_merge_rows), cv/ci [Bs] = complete column minima */
+int witw_batch_hard_slab_mine(const float* distance, int Bo, int Bs, int col0, float* rv, long long* ri, float* cv, long long* ci,
+                              void* workspace, void* stream);
+/* rv_parts / ri_parts [n_parts][B] (per-rank row minima, rank order) -> the global rv / ri [B]; an earlier part wins a tie */
+int witw_batch_hard_merge_rows(const float* rv_parts, const long long* ri_parts, int n_parts, int B, float* rv, long long* ri,
+                               void* stream);
+/* un-normalised partial of the slab: row terms of the anchors col0..col0+Bs-1 (global rv [Bo]) + column terms of its columns;
+ * the sum over the ranks / (2*Bo) is the loss */
+int witw_batch_hard_slab_loss(const float* distance, const float* rv, const float* cv, int Bo, int Bs, int col0, float alpha,
+                              float* partial, void* stream);
+/* the gradient's pair list restricted to the slab's columns (B = global batch, diag [B] = global diagonal, rv/ri [B] global,
+ * cv/ci [Bs]; Bs = B, col0 = 0 for the full form): 2*Bs + B entries (pair_o global row, pair_s local column, pair_w weight
+ * including grad_loss [1]); entries for rows whose hardest negative lies in another slab are (-1, -1, 0) */
+int witw_batch_hard_pairs(const float* diag, const float* rv, const long long* ri, const float* cv, const long long* ci,
+                          const float* grad_loss, int B, int Bs, int col0, float alpha, int* pair_o, int* pair_s, float* pair_w,
+                          void* stream);
+/* dense dL/dD [B,B] of the full form for grad_loss [1] (at most 3B non-zeros) */
+int witw_batch_hard_bwd(const float* distance, const float* rv, const long long* ri, const float* cv, const long long* ci,
+                        const float* grad_loss, float* grad_distance, int B, float alpha, void* stream);
+/* Backward of witw_match_fwd for a pair list instead of a dense grad_distance: grad_distance[o][s] = sum of pair_w over the
+ * pairs (o, s). orientation / score / workspace as for witw_match_bwd. grad_ov [Bo,16,4,64] and grad_su [Bs,16,4,We] are written
+ * in full (rows without pairs are zero). Pairs with an index outside [0,Bo) x [0,Bs) are ignored. Deterministic: the pairs are
+ * sorted into per-row segments on the device (partners ascending, duplicates in list order) and each segment is summed in
+ * order; no atomics. n_pairs <= 8192; scratch: witw_match_bwd_pairs_scratch_bytes(n_pairs, Bo, Bs) bytes (-1 if unsupported). */
+long long witw_match_bwd_pairs_scratch_bytes(int n_pairs, int Bo, int Bs);
+int witw_match_bwd_pairs(const float* ov, const float* su, const long long* orientation, const float* score, const float* workspace,
+                         const int* pair_o, const int* pair_s, const float* pair_w, int n_pairs, int Bo, int Bs, int We,
+                         float* grad_ov, float* grad_su, void* scratch, void* stream);
+
 /* ---- bf16 inference path of the encoder (BASELINE config "cvig_semantic ... bf16 MFMA"): bf16 NHWC activations
  * (channels padded to 16) and packed bf16 filters, fp32 accumulate on v_mfma_f32_32x32x16_bf16, fp32 bias;
  * the last layer writes the fp32 NCHW embedding (out_nchw_f32). Pointers typed void* carry bf16 data. */

@@ -120,6 +120,15 @@ SIGNATURES = {
     'witw_triplet_loss_slab_sig': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     'witw_triplet_loss_slab_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_void_p]),
     'witw_triplet_loss_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    'witw_batch_hard_workspace_bytes': (c_longlong, [c_int, c_int]),
+    'witw_batch_hard_fwd': (c_int, [c_void_p, c_int, c_float] + [c_void_p] * 7),
+    'witw_batch_hard_slab_mine': (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6),
+    'witw_batch_hard_merge_rows': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'witw_batch_hard_slab_loss': (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_float, c_void_p, c_void_p]),
+    'witw_batch_hard_pairs': (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_float] + [c_void_p] * 4),
+    'witw_batch_hard_bwd': (c_int, [c_void_p] * 7 + [c_int, c_float, c_void_p]),
+    'witw_match_bwd_pairs_scratch_bytes': (c_longlong, [c_int] * 3),
+    'witw_match_bwd_pairs': (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p] * 4),
     'witw_resize_bilinear_normalize': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_int, c_void_p]),
     'witw_resize_bilinear_normalize_batched': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_int, c_void_p]),
     'witw_normalize': (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_void_p]),

@@ -59,7 +59,7 @@ const char* witw_last_error(void) { return g_err; }
 // rocprof kernel names), "" before the first launch. Lets a parity test assert WHICH kernel it compared with the oracle.
 const char* witw_last_kernel_variant(void) { return g_variant; }
 
-int witw_version(void) { return 100; }  // 0.1.0
+int witw_version(void) { return 200; }  // 0.2.0: batch-hard loss, pair-list match backward
 
 // 0 when device `dev` exists and is a gfx950 part; the message says what was found otherwise.
 int witw_device_check(int dev) {

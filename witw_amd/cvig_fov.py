@@ -50,6 +50,10 @@ class Globals:
     # not in the reference: how test() ranks the queries against the gallery. 'direct' = the reference's sum on every pair,
     # 'dft' = the spectral pass with exact re-scoring (same ranks), 'auto' = 'dft' from cvig_fov.SPECTRAL_FROM pairs on.
     match_method = 'auto'
+    # not in the reference: the training objective of train() (`--loss`). 'soft_margin' = the reference's all-pairs soft-margin
+    # triplet loss (triplet_loss); 'batch_hard' = the soft-margin loss on each anchor's hardest negative in the global batch
+    # (batch_hard_triplet_loss, Hermans et al. 2017).
+    loss = 'soft_margin'
 
 
 def _default_device():
@@ -798,6 +802,30 @@ def triplet_loss(distances, alpha=10.):
     return _TripletLoss.apply(distances, float(alpha))
 
 
+class _BatchHardTripletLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, distances, alpha):
+        d = distances.contiguous()
+        loss, rv, ri, cv, ci = ops.batch_hard_fwd(d, alpha)
+        ctx.save_for_backward(d, rv, ri, cv, ci)
+        ctx.alpha = alpha
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad):
+        d, rv, ri, cv, ci = ctx.saved_tensors
+        return ops.batch_hard_bwd(d, rv, ri, cv, ci, grad.contiguous(), ctx.alpha), None
+
+
+def batch_hard_triplet_loss(distances, alpha=10.):
+    """Batch-hard soft-margin triplet loss (Hermans et al. 2017) over D [B,B], positives on the diagonal: every overhead anchor i
+    against its hardest negative surface min_{j != i} D[i,j], every surface anchor j against its hardest negative overhead
+    min_{i != j} D[i,j]; loss = (sum_i softplus(a(d_i - rv_i)) + sum_j softplus(a(d_j - cv_j))) / (2B). Ties go to the lowest
+    index, a NaN is a row's / column's minimum (torch.min). The mined indices are constants of the gradient. Differentiable
+    w.r.t. `distances` (dense gradient); the training path (sharded_match_loss(..., loss='batch_hard')) never builds it."""
+    return _BatchHardTripletLoss.apply(distances, float(alpha))
+
+
 def ranks(overhead_embed, surface_embed):
     """Ranking loop of test() (model/cvig_fov.py:543-552) for all queries at once: int64 [N] on
     the host, rank = #{gallery : d <= d_true} with gallery index == query index."""
@@ -1170,11 +1198,80 @@ class _ShardedMatchLossFn(torch.autograd.Function):
         return gov, gsu, None, None
 
 
-def sharded_match_loss(overhead_local, surface_local, alpha=10., _kernels=None):
+class _BatchHardMatchLossFn(torch.autograd.Function):
+    """match + batch-hard soft-margin triplet loss over the GLOBAL batch, fused: the backward never builds a dense dL/dD. The
+    mined pairs (at most 3B) go straight to the pair-list match backward (ops.match_bwd_pairs).
+    One rank: the full [B,B] matrix (ops.batch_hard_fwd). N ranks: the column slab of _ShardedMatchLossFn, and
+    forward = all-gather of the overhead embeddings, of the diagonal (B floats) and of the per-rank row minima ([w,B] values +
+    global column indices, reduced in rank order: the lowest index wins a tie), all-reduce of the loss partial (each rank: row
+    terms of the anchors it owns + column terms of its columns); backward = the pairs whose column this rank owns through
+    match_bwd_pairs, then the reduce-scatter of the overhead-embedding gradients.
+    Outputs: loss, orientation, distance, and the mined (rv [B], ri [B]) of every overhead anchor and (cv [b], ci [b]) of this
+    rank's surface anchors (global indices)."""
+
+    @staticmethod
+    def forward(ctx, overhead_local, surface_local, alpha, k):
+        from . import parallel
+        world = parallel.world()
+        b = surface_local.shape[0]
+        col0 = parallel.rank() * b if world > 1 else 0
+        su = surface_local.contiguous()
+        if world > 1:
+            with parallel.phase('overhead_all_gather'):
+                ov_all = parallel._all_gather_cat(overhead_local.contiguous())
+        else:
+            ov_all = overhead_local.contiguous()
+        with parallel.phase('slab_match'):
+            ori, dist, score, ws = k.match_fwd(ov_all, su, want_score=True, want_workspace=True)
+        B = ov_all.shape[0]
+        if world > 1:
+            with parallel.phase('diagonal_all_gather'):
+                diag = parallel._all_gather_cat(dist[col0:col0 + b].diagonal().contiguous())
+            with parallel.phase('row_minima_all_gather'):
+                rv_l, ri_l, cv, ci = k.batch_hard_slab_mine(dist, col0)
+                rv, ri = k.batch_hard_merge_rows(parallel._all_gather_cat(rv_l[None]), parallel._all_gather_cat(ri_l[None]))
+            with parallel.phase('loss_partial_all_reduce'):
+                part = k.batch_hard_slab_loss(dist, rv, cv, col0, alpha)
+                parallel.all_reduce_sum_(part)
+            loss = (part / (2. * B)).reshape(())
+        else:
+            diag = dist.diagonal().contiguous()
+            loss, rv, ri, cv, ci = k.batch_hard_fwd(dist, alpha)
+            loss = loss.reshape(())
+        ctx.save_for_backward(ov_all, su, ori, score, ws, diag, rv, ri, cv, ci)
+        ctx.cfg = (col0, b, world, float(alpha), k)
+        ctx.mark_non_differentiable(ori, dist, rv, ri, cv, ci)
+        ctx.set_materialize_grads(False)      # no zero gradients for the six non-differentiable outputs
+        return loss, ori, dist, rv, ri, cv, ci
+
+    @staticmethod
+    def backward(ctx, g_loss, *_g):
+        from . import parallel
+        if g_loss is None:
+            return None, None, None, None
+        ov_all, su, ori, score, ws, diag, rv, ri, cv, ci = ctx.saved_tensors
+        col0, b, world, alpha, k = ctx.cfg
+        with parallel.phase('slab_match_backward'):
+            po, ps, pw = k.batch_hard_pairs(diag, rv, ri, cv, ci, g_loss.contiguous(), col0, alpha)
+            gov_all, gsu = k.match_bwd_pairs(ov_all, su, ori, score, ws, po, ps, pw)
+        if world > 1:
+            with parallel.phase('overhead_grad_reduce_scatter'):
+                gov_all = parallel.reduce_scatter_rows(gov_all, b)
+        return gov_all, gsu, None, None
+
+
+def sharded_match_loss(overhead_local, surface_local, alpha=10., _kernels=None, loss='soft_margin', mined=False):
     """(loss, orientation [B,b], distance [B,b]) of the GLOBAL batch from this rank's b pairs; every rank must call it
     with the same b. On one rank it is match + triplet_loss. `_kernels` swaps the op set (CPU tests of the
-    collective algebra)."""
+    collective algebra). loss='batch_hard': the batch-hard soft-margin loss (batch_hard_triplet_loss) over the global batch,
+    through _BatchHardMatchLossFn (no dense loss gradient on any rank); mined=True appends the mined
+    (rv [B], ri [B], cv [b], ci [b]) of the global rows and this rank's columns."""
     from . import parallel
+    if loss == 'batch_hard':
+        out = _BatchHardMatchLossFn.apply(overhead_local, surface_local, float(alpha), _kernels or ops)
+        return out if mined else out[:3]
+    if loss != 'soft_margin':
+        raise _lib.WitwError("sharded_match_loss: loss must be 'soft_margin' or 'batch_hard', got %r" % (loss,))
     if parallel.world() == 1 and _kernels is None:
         ori, dist = match(overhead_local, surface_local)
         return triplet_loss(dist, alpha), ori, dist.detach()
@@ -1895,7 +1992,8 @@ def train(dataset='cvusa', fov=360, val_quantity=1000, batch_size=64, num_worker
                     # validation: PairEmbedder (small batches on two streams, bf16 as one hipGraph); training: the plain calls
                     surface_embed, overhead_embed = embed(surface, overhead)
                     # correlation -> crop_overhead -> l2_distance -> triplet_loss (:450-454) over the GLOBAL batch
-                    loss, orientation_estimate, distance = sharded_match_loss(overhead_embed, surface_embed)
+                    loss, orientation_estimate, distance = sharded_match_loss(overhead_embed, surface_embed,
+                                                                              loss=getattr(Globals, 'loss', 'soft_margin'))
                     if phase == 'train':
                         optimizer.zero_grad()
                         loss.backward()          # per-encoder gradient all-reduce overlapped with the other encoder's backward
@@ -2018,10 +2116,15 @@ def main(argv=None):
     parser.add_argument('--vgg16', default=None, metavar='PATH',
                         help='train mode: torchvision VGG16 state_dict file to start from (the reference downloads it through '
                              'torch.hub). [Default = seeded synthetic weights]')
+    parser.add_argument('--loss', default='soft_margin', choices=['soft_margin', 'batch_hard'],
+                        help='train mode (not in the reference): soft_margin = the reference\'s all-pairs soft-margin triplet loss, '
+                             'batch_hard = the soft-margin loss on each anchor\'s hardest negative in the global batch. '
+                             '[Default = soft_margin]')
     args = parser.parse_args(argv)
     print(args)
     Globals.precision = args.precision
     Globals.vgg16_weights = args.vgg16
+    Globals.loss = args.loss
     init_distributed()
     if args.mode == 'train':
         train(dataset=args.dataset, fov=args.fov)

@@ -120,10 +120,15 @@ def main(argv=None):
     parser.add_argument('--vgg16', default=None, metavar='PATH',
                         help='train mode: torchvision VGG16 state_dict file to start from (the RGB slice of the 5-channel first '
                              'conv takes the VGG filter, model/cvig_semantic.py:301-303). [Default = seeded synthetic weights]')
+    parser.add_argument('--loss', default='soft_margin', choices=['soft_margin', 'batch_hard'],
+                        help='train mode (not in the reference): soft_margin = the reference\'s all-pairs soft-margin triplet loss, '
+                             'batch_hard = the soft-margin loss on each anchor\'s hardest negative in the global batch. '
+                             '[Default = soft_margin]')
     args = parser.parse_args(argv)
     print(args)
     Globals.precision = args.precision
     Globals.vgg16_weights = args.vgg16
+    Globals.loss = args.loss
     _fov.init_distributed()
     if args.mode == 'train':
         train(dataset=args.dataset, fov=args.fov)

@@ -851,6 +851,153 @@ def triplet_loss_bwd(distance, ws, grad_loss, alpha=10.):
     return gd
 
 
+# ----------------------------------------------------------------------------- batch-hard soft-margin triplet loss
+def _dev_i64(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+        raise _lib.WitwError('%s must be a contiguous int64 GPU tensor' % name)
+    return t
+
+
+def _batch_hard_ws(Bo, Bs, device):
+    n = _lib.load().witw_batch_hard_workspace_bytes(Bo, Bs)
+    if n < 0:
+        raise _lib.WitwError('batch_hard: bad shape Bo=%d Bs=%d (a batch needs at least 2 pairs)' % (Bo, Bs))
+    return torch.empty((max(1, n),), dtype=torch.uint8, device=device)
+
+
+def batch_hard_fwd(distance, alpha=10.):
+    """Full form on D [B,B] -> (loss [1], rv [B], ri int64 [B], cv [B], ci int64 [B]): the hardest negative of every overhead
+    anchor (row minimum of D with its diagonal masked) and of every surface anchor (column minimum), and the loss."""
+    lib = _lib.load()
+    d = _dev_f32(distance, 'distance')
+    if d.dim() != 2 or d.shape[0] != d.shape[1]:
+        raise _lib.WitwError('batch_hard: distance matrix must be square, got %s' % (tuple(d.shape),))
+    B = d.shape[0]
+    if B < 2:
+        raise _lib.WitwError('batch_hard: batch %d < 2 (every anchor needs a negative)' % B)
+    f = lambda: torch.empty((B,), dtype=torch.float32, device=d.device)
+    i = lambda: torch.empty((B,), dtype=torch.int64, device=d.device)
+    rv, ri, cv, ci = f(), i(), f(), i()
+    loss = torch.empty((1,), dtype=torch.float32, device=d.device)
+    ws = _batch_hard_ws(B, B, d.device)
+    _lib.check(lib.witw_batch_hard_fwd(d.data_ptr(), B, float(alpha), rv.data_ptr(), ri.data_ptr(), cv.data_ptr(), ci.data_ptr(),
+                                       loss.data_ptr(), ws.data_ptr(), _stream()), 'witw_batch_hard_fwd')
+    return loss, rv, ri, cv, ci
+
+
+def batch_hard_slab_mine(distance_slab, col0):
+    """Column slab D [Bo,Bs] of the global columns [col0, col0+Bs) -> (rv [Bo], ri [Bo]: row minima over these columns only, with
+    global column indices; cv [Bs], ci [Bs]: complete column minima)."""
+    lib = _lib.load()
+    d = _dev_f32(distance_slab, 'distance_slab')
+    if d.dim() != 2:
+        raise _lib.WitwError('batch_hard_slab_mine: distance slab must be [Bo,Bs], got %s' % (tuple(d.shape),))
+    Bo, Bs = d.shape
+    rv = torch.empty((Bo,), dtype=torch.float32, device=d.device)
+    ri = torch.empty((Bo,), dtype=torch.int64, device=d.device)
+    cv = torch.empty((Bs,), dtype=torch.float32, device=d.device)
+    ci = torch.empty((Bs,), dtype=torch.int64, device=d.device)
+    ws = _batch_hard_ws(max(Bo, 2), max(Bs, 1), d.device)
+    _lib.check(lib.witw_batch_hard_slab_mine(d.data_ptr(), Bo, Bs, int(col0), rv.data_ptr(), ri.data_ptr(), cv.data_ptr(),
+                                             ci.data_ptr(), ws.data_ptr(), _stream()), 'witw_batch_hard_slab_mine')
+    return rv, ri, cv, ci
+
+
+def batch_hard_merge_rows(rv_parts, ri_parts):
+    """Per-rank row minima [w,B] (rank order) -> the global (rv [B], ri [B]); an earlier rank wins a tie."""
+    lib = _lib.load()
+    v = _dev_f32(rv_parts, 'rv_parts')
+    ix = _dev_i64(ri_parts, 'ri_parts')
+    if v.dim() != 2 or tuple(ix.shape) != tuple(v.shape):
+        raise _lib.WitwError('batch_hard_merge_rows: rv_parts %s and ri_parts %s must both be [w,B]' % (tuple(v.shape), tuple(ix.shape)))
+    w, B = v.shape
+    rv = torch.empty((B,), dtype=torch.float32, device=v.device)
+    ri = torch.empty((B,), dtype=torch.int64, device=v.device)
+    _lib.check(lib.witw_batch_hard_merge_rows(v.data_ptr(), ix.data_ptr(), w, B, rv.data_ptr(), ri.data_ptr(), _stream()),
+               'witw_batch_hard_merge_rows')
+    return rv, ri
+
+
+def batch_hard_slab_loss(distance_slab, rv, cv, col0, alpha=10.):
+    """Un-normalised loss partial [1] of a column slab: the row terms of anchors col0..col0+Bs-1 (rv = the GLOBAL row minima [Bo])
+    and the column terms of its columns. Summed over the ranks and divided by 2 Bo it is the loss."""
+    lib = _lib.load()
+    d = _dev_f32(distance_slab, 'distance_slab')
+    Bo, Bs = d.shape
+    if rv.numel() != Bo or cv.numel() != Bs:
+        raise _lib.WitwError('batch_hard_slab_loss: rv must have %d entries and cv %d' % (Bo, Bs))
+    out = torch.empty((1,), dtype=torch.float32, device=d.device)
+    _lib.check(lib.witw_batch_hard_slab_loss(d.data_ptr(), _dev_f32(rv, 'rv').data_ptr(), _dev_f32(cv, 'cv').data_ptr(), Bo, Bs,
+                                             int(col0), float(alpha), out.data_ptr(), _stream()), 'witw_batch_hard_slab_loss')
+    return out
+
+
+def batch_hard_pairs(diag, rv, ri, cv, ci, grad_loss, col0=0, alpha=10.):
+    """The gradient of the loss as a pair list over the columns [col0, col0+Bs) (Bs = cv.numel(); the whole matrix with col0 = 0
+    and Bs = B): (pair_o int32, pair_s int32 local column, pair_w f32), 2 Bs + B entries, unused ones (-1, -1, 0)."""
+    lib = _lib.load()
+    B, Bs = diag.numel(), cv.numel()
+    if rv.numel() != B or ri.numel() != B or ci.numel() != Bs:
+        raise _lib.WitwError('batch_hard_pairs: diag / rv / ri must have B entries, cv / ci Bs')
+    n = 2 * Bs + B
+    dev = diag.device
+    po = torch.empty((n,), dtype=torch.int32, device=dev)
+    ps = torch.empty((n,), dtype=torch.int32, device=dev)
+    pw = torch.empty((n,), dtype=torch.float32, device=dev)
+    g = _dev_f32(grad_loss.reshape(1).contiguous(), 'grad_loss')
+    _lib.check(lib.witw_batch_hard_pairs(_dev_f32(diag, 'diag').data_ptr(), _dev_f32(rv, 'rv').data_ptr(), _dev_i64(ri, 'ri').data_ptr(),
+                                         _dev_f32(cv, 'cv').data_ptr(), _dev_i64(ci, 'ci').data_ptr(), g.data_ptr(), B, Bs, int(col0),
+                                         float(alpha), po.data_ptr(), ps.data_ptr(), pw.data_ptr(), _stream()), 'witw_batch_hard_pairs')
+    return po, ps, pw
+
+
+def batch_hard_bwd(distance, rv, ri, cv, ci, grad_loss, alpha=10.):
+    """Dense dL/dD [B,B] of the full form (at most 3B non-zeros)."""
+    lib = _lib.load()
+    d = _dev_f32(distance, 'distance')
+    B = d.shape[0]
+    if d.dim() != 2 or d.shape[1] != B or any(t.numel() != B for t in (rv, ri, cv, ci)):
+        raise _lib.WitwError('batch_hard_bwd: distance must be [B,B] and rv / ri / cv / ci hold B entries')
+    gd = torch.empty_like(d)
+    g = _dev_f32(grad_loss.reshape(1).contiguous(), 'grad_loss')
+    _lib.check(lib.witw_batch_hard_bwd(d.data_ptr(), _dev_f32(rv, 'rv').data_ptr(), _dev_i64(ri, 'ri').data_ptr(),
+                                       _dev_f32(cv, 'cv').data_ptr(), _dev_i64(ci, 'ci').data_ptr(), g.data_ptr(), gd.data_ptr(), B,
+                                       float(alpha), _stream()), 'witw_batch_hard_bwd')
+    return gd
+
+
+def match_bwd_pairs(overhead_embed, surface_embed, orientation, score, workspace, pair_o, pair_s, pair_w):
+    """Backward of match_fwd for grad_distance given as a pair list (grad[o][s] = sum of pair_w over the pairs (o, s); pairs with
+    an index out of range are ignored) -> (grad_ov [Bo,16,4,64], grad_su [Bs,16,4,We]), rows without pairs zero. orientation /
+    score / workspace: match_fwd(..., want_score=True, want_workspace=True) on the same embeddings. Deterministic, no atomics."""
+    lib = _lib.load()
+    ov = _dev_f32(overhead_embed, 'overhead_embed')
+    su = _dev_f32(surface_embed, 'surface_embed')
+    Bo, Bs, We = ov.shape[0], su.shape[0], su.shape[3]
+    n = pair_o.numel()
+    for t, name in ((pair_o, 'pair_o'), (pair_s, 'pair_s')):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
+            raise _lib.WitwError('match_bwd_pairs: %s must be a contiguous int32 GPU tensor of %d entries' % (name, n))
+    pw = _dev_f32(pair_w, 'pair_w')
+    if pw.numel() != n:
+        raise _lib.WitwError('match_bwd_pairs: pair_w must have %d entries' % n)
+    if tuple(orientation.shape) != (Bo, Bs) or tuple(score.shape) != (Bo, Bs):
+        raise _lib.WitwError('match_bwd_pairs: orientation / score must be [%d,%d]' % (Bo, Bs))
+    if workspace.numel() < Bo * 64 + Bs:
+        raise _lib.WitwError('match_bwd_pairs: workspace must hold the [Bo,64] + [Bs] norms of match_fwd')
+    nb = lib.witw_match_bwd_pairs_scratch_bytes(n, Bo, Bs)
+    if nb < 0:
+        raise _lib.WitwError('match_bwd_pairs: %d pairs unsupported (1 .. 8192)' % n)
+    scratch = torch.empty((nb,), dtype=torch.uint8, device=ov.device)
+    gov = torch.empty_like(ov)
+    gsu = torch.empty_like(su)
+    _lib.check(lib.witw_match_bwd_pairs(ov.data_ptr(), su.data_ptr(), _dev_i64(orientation, 'orientation').data_ptr(),
+                                        _dev_f32(score, 'score').data_ptr(), _dev_f32(workspace, 'workspace').data_ptr(),
+                                        pair_o.data_ptr(), pair_s.data_ptr(), pw.data_ptr(), n, Bo, Bs, We, gov.data_ptr(),
+                                        gsu.data_ptr(), scratch.data_ptr(), _stream()), 'witw_match_bwd_pairs')
+    return gov, gsu
+
+
 # ----------------------------------------------------------------------------- data path
 def _host_floats(vals):
     import ctypes
