@@ -513,7 +513,8 @@ int witw_jpeg_huffman(const void* files, int n_files, int max_intervals, int* er
  * after a few dozen symbols; thread 0 starts at the true state, so the fixed point is the true decoding); a prefix sum numbers the
  * blocks, a last pass writes the coefficients and a per-component prefix sum turns DC differences into DC values. files: DEVICE int64
  * [n_files][6] = {file bytes, plan, coefficient area (zero-filled), file length, scratch of file length + 32 bytes (8-byte aligned),
- * 0}. Coefficients bit-identical to the host decoder's. */
+ * 0}; errors as above: 1 where the block count does not come out or where the writing pass meets, inside a block of the image, an
+ * invalid code, a run past coefficient 63 or a symbol that reads behind the data. Coefficients bit-identical to the host decoder's. */
 int witw_jpeg_huffman_selfsync(const void* files, int n_files, int* errors, void* stream);
 /* The same with the threads per file chosen by the caller (256, 512 or 1024; jpeg.decode_packed_multi: 1024 when the launch holds a file
  * of 48 KB or more, else 512 -- larger files gain from shorter subsequences, smaller ones lose to the extra rounds). */

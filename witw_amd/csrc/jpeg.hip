@@ -462,13 +462,13 @@ __global__ __launch_bounds__(HUFF_T) void jpeg_huffman_kernel(const JpegFileDev*
             r1 = iv_last < n_int ? min(ioff[iv_last], n_bytes) : end_all;
         }
         const bool staged = r1 > r0 && r1 - r0 + 24u <= (unsigned)HUFF_STAGE;
-        if (staged) {      // up to 16 bytes behind r1 are read ahead (the file has 24 readable bytes behind its end)
+        if (staged) {      // the 8-byte words that start in front of r1 + 16 (the readers' look-ahead): nothing past r1 + 22 is read, and
+                           // the file has 24 readable bytes behind its end
             const WITW_AS_GLOBAL unsigned char* src = (const WITW_AS_GLOBAL unsigned char*)f.bytes + r0;
-            for (unsigned o = (unsigned)lane * 16u; o < r1 - r0 + 16u; o += 1024u) {
-                const unsigned long long lo = *(GlobalWords)(src + o);
-                const unsigned long long hi = *(GlobalWords)(src + o + 8);
-                stage[wave][o >> 3] = lo;
-                stage[wave][(o >> 3) + 1] = hi;
+            const unsigned lim = r1 - r0 + 16u;
+            for (unsigned o = (unsigned)lane * 16u; o < lim; o += 1024u) {
+                stage[wave][o >> 3] = *(GlobalWords)(src + o);
+                if (o + 8u < lim) stage[wave][(o >> 3) + 1] = *(GlobalWords)(src + o + 8);
             }
         }
         __syncthreads();
@@ -506,8 +506,9 @@ __global__ __launch_bounds__(HUFF_T) void jpeg_huffman_kernel(const JpegFileDev*
 //   3 an exclusive prefix sum of the completed-block counts numbers every thread's first block; the threads decode once more, now
 //     WRITING: AC coefficients to their place, DC DIFFERENCES to slot 0 of their block;
 //   4 per component a prefix sum over its blocks in scan order turns the differences into DC values.
-// Bit-identical to witw_jpeg_decode_coef on valid files (tests/test_jpeg_gpu.py); a file whose block count does not come out as
-// MCUs x blocks per MCU is flagged in `errors`.
+// Bit-identical to witw_jpeg_decode_coef on valid files (tests/test_jpeg_gpu.py, tests/test_jpeg_damage_gpu.py); a file is flagged
+// in `errors` when its block count does not come out as MCUs x blocks per MCU, or when step 3 meets, inside a block of the image, an
+// invalid code, a run past coefficient 63 or a symbol that reads behind the data (the cases witw_jpeg_decode_coef refuses with -3).
 
 struct JpegSyncDev {               // int64 x 6 per file
     long long bytes, plan, coef, n_bytes;      // as JpegFileDev
@@ -648,7 +649,11 @@ __global__ __launch_bounds__(SS_T) void jpeg_selfsync_kernel(const JpegSyncDev* 
     if (L < 64u) L = 64u;
     const unsigned my_lo = min(total_bits, (unsigned)tid * L), my_hi = min(total_bits, ((unsigned)tid + 1u) * L);
 
-    // decode from `st` to the first symbol that starts at or behind `limit`; WRITE: store coefficients, first block = blk0
+    // decode from `st` to the first symbol that starts at or behind `limit`; WRITE: store coefficients, first block = blk0, and set
+    // `damaged` where a symbol of a block of the image is no code, runs past coefficient 63 or reads bits behind the data (in the WRITE
+    // pass every thread starts from the true state, so each of these is damage -- witw_jpeg_decode_coef: -3; the padding bits behind
+    // the last block decode with blk == nullptr and count for nothing)
+    bool damaged = false;
     auto run = [&](SyncState st, unsigned limit, auto write_c, long long blk0) -> SyncState {
         constexpr bool WRITE = decltype(write_c)::value;
         BitReaderT<false> b;
@@ -691,6 +696,7 @@ __global__ __launch_bounds__(SS_T) void jpeg_selfsync_kernel(const JpegSyncDev* 
             const unsigned at = kq + (unsigned)r;
             const int v = jpeg_extend0(b.take(sz), sz);
             if (WRITE && blk && !inval && (dc || (sz && at < 64u))) blk[dc ? 0 : zz[at]] = (short)v;
+            if (WRITE && blk && (inval || (sz && at > 63u) || b.bit_pos() > total_bits)) damaged = true;
             const unsigned nk = inval ? kq : dc ? 1u : sz ? at + 1u : (r == 15 ? kq + 16u : 64u);
             const bool finished = nk >= 64u;
             kq = finished ? 0u : nk;
@@ -742,6 +748,7 @@ __global__ __launch_bounds__(SS_T) void jpeg_selfsync_kernel(const JpegSyncDev* 
     int total_done = 0;
     const int first = block_scan_excl<SS_T>((int)nblk_s[tid], wave_tot, tid, total_done);
     if (entry.p < my_hi) run(entry, my_hi, std::true_type(), (long long)first);
+    if (damaged) errors[blockIdx.x] = 1;
     __syncthreads();
     const long long total_blocks = (long long)mcux * mcuy * nb;
     if (tid == 0 && (long long)total_done < total_blocks) errors[blockIdx.x] = 1;      // the data ended early (a trailing partial block of padding bits may add one)
@@ -779,7 +786,8 @@ extern "C" {
 // The same for files WITHOUT restart markers (plans of ONE interval): self-synchronising decode, one workgroup of 512 threads per file
 // (WITW_SELFSYNC_THREADS = 256 | 512 | 1024).
 // files: DEVICE int64 [n_files][6] = {file bytes, plan, coefficient area (zero-filled), file length, scratch of file length + 32
-// bytes (8-byte aligned), 0}; errors as above. Coefficients bit-identical to witw_jpeg_decode_coef.
+// bytes (8-byte aligned), 0}; errors as below (1: the block count does not come out, or the writing pass met an invalid code, a run
+// past coefficient 63 or a read behind the data inside a block of the image). Coefficients bit-identical to witw_jpeg_decode_coef.
 int witw_jpeg_huffman_selfsync_threads(const void* files, int n_files, int threads, int* errors, void* stream) {
     WITW_CHECK_ARG(files && errors, "jpeg_huffman_selfsync: null pointer");
     WITW_CHECK_ARG(n_files > 0, "jpeg_huffman_selfsync: %d files", n_files);

@@ -307,10 +307,14 @@ int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t
     int to_restart = P.restart, next_rst = 0;
     size_t rst_i = 0;
     const uint8_t* const limit = clean + w + 9;             // reading this far past the data means the stream was too short
+    // an interval whose symbols took bits behind its own data (the next interval's, across the RSTn marker, or the zeros behind the
+    // end) is damaged: libjpeg hits the marker there and decodes zeros (jdhuff.c, insufficient data); the device decoders flag it too
+    auto overran = [&](size_t seg_end) { return (size_t)(b.p - clean) * 8 - (size_t)b.n > seg_end * 8; };
     for (int my = 0; my < P.mcuy; ++my)
         for (int mx = 0; mx < P.mcux; ++mx) {
             if (P.restart && to_restart == 0) {
                 if (rst_i >= n_rst || (int)(rst_pos[rst_i] >> 29) != next_rst) return -3;
+                if (overran(rst_pos[rst_i] & 0x1fffffffu)) return -3;
                 b.init(clean + (rst_pos[rst_i] & 0x1fffffffu));
                 ++rst_i;
                 next_rst = (next_rst + 1) & 7;
@@ -358,6 +362,7 @@ int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t
             }
             if (P.restart) --to_restart;
         }
+    if (overran(w)) return -3;
     return 0;
 }
 

@@ -305,6 +305,10 @@ def decode_packed_multi(parts, defer=False):
     for k, (dbuf, desc, _hb) in enumerate(parts):
         dk = np.array(desc.numpy() if isinstance(desc, torch.Tensor) else desc, dtype=np.int64, copy=True)
         delta = int(dbuf.data_ptr()) - ref
+        if delta % 128:
+            # the back end addresses coefficient blocks and quantisation tables on a 128-byte grid from the lowest block
+            # (decode_tables): a part off that grid would decode with another file's tables
+            raise _lib.WitwError('jpeg: part %d of the batch sits %d bytes from the lowest, not a multiple of 128' % (k, delta))
         off0.append(dk[:, 0].copy())
         dk[:, 0] += delta
         dk[:, 1] += delta
@@ -420,7 +424,7 @@ def decode(images, device):
     one-off use; the data path goes through pack / decode_packed inside GpuPreprocess)."""
     buf, desc, _k = pack(images)
     dbuf = buf.to(device)
-    keep, table = decode_packed(dbuf, desc)
+    keep, table = decode_packed(dbuf, desc, host_buf=buf)      # files the device flags as damaged: Pillow, as on the data path
     torch.cuda.synchronize(device)
     out = []
     for i in range(len(images)):
@@ -428,5 +432,5 @@ def decode(images, device):
         src = next(t for t in [dbuf] + keep if t.dtype == torch.uint8 and t.data_ptr() <= int(table[i, 0]) < t.data_ptr() + max(1, t.numel())
                    and int(table[i, 0]) + H * W * C <= t.data_ptr() + t.numel() and (t is dbuf) == bool(desc[i, 24]))
         o = int(table[i, 0]) - src.data_ptr()
-        out.append(src[o:o + H * W * C].reshape(H, W, C).clone())
+        out.append(src.reshape(-1)[o:o + H * W * C].reshape(H, W, C).clone())      # (a repaired image is an H x W x C tensor)
     return out
