@@ -29,6 +29,9 @@ int witw_device_check(int device);    /* 0 iff `device` is a gfx950 part */
  * (e.g. "conv3x3_bf16_s16_kernel<false>"); "" before the first launch. Parity tests assert on it so that a change of the
  * launcher's thresholds cannot silently move a test onto another kernel. */
 const char* witw_last_kernel_variant(void);
+/* arithmetic form of the calling thread's last conv launch: "direct", or "wino_h2" when witw_conv3x3_fwd_wino ran the Winograd
+ * F(2,3)-along-H form of conv3x3_nhwc_f32_kernel (same instantiation name); "" before the first launch. */
+const char* witw_last_conv_form(void);
 
 /* ---- FOV_DSM encoder: Conv2d(3x3,pad 1) [+HorizCircPadding] [+Dropout2d] [+ReLU] [+MaxPool2d(2)]
  *      reference: model/cvig_fov.py:212-231 (padding), :234-245 (dropout), :256-294 (layer stack).
@@ -100,6 +103,21 @@ int witw_conv3x3_fwd_ex(const float* x, const float* wpk, const float* bias, con
  * 263-272 through autograd) on the 8-wave 128-channel tile skips the products whose input rows are the interleaved zeros -- half the
  * MFMAs, the same bits; 0: all products are issued. enable < 0 only queries; returns the previous setting. */
 int witw_conv3x3_dil_skip(int enable);
+/* Winograd F(2,3) along H (inference): the filter packed for it, [cdiv(cout,64)][cdiv(cin,8)][kw 3][t 4][quad 2][64][4] with
+ * U0 = g0, U1 = ((g0+g1)+g2)/2, U2 = ((g0-g1)+g2)/2, U3 = g2 per column tap (g = the 3 taps of the column); its size in floats. */
+long long witw_conv3x3_packed_floats_wino(int cout, int cin);
+int witw_conv3x3_pack_weights_wino(const float* w_kcrs, float* wpk_wino, int cout, int cin, void* stream);
+/* witw_conv3x3_fwd_ex with both packings of the filter: stride-1 launches with no gate / dilate_h / NCHW output / post affine,
+ * Cout % 4 == 0 and the wide geometry, of the classes conv3x3_nhwc_f32_kernel<128,1,*,*,0,9> and <64,1,true,*,0,9>, run the
+ * Winograd form (2/3 of the MFMAs; same instantiation name, witw_last_conv_form() == "wino_h2") while witw_conv3x3_wino is on;
+ * every other launch runs the direct form on wpk. */
+int witw_conv3x3_fwd_wino(const float* x, const float* wpk, const float* wpk_wino, const float* bias, const float* dropmask,
+                          const float* gate, const float* post_scale, const float* post_shift, float* y, unsigned char* pool_code,
+                          int B, int H, int W, int Cin, int Cout, int stride_h, int pad_circular, int relu, float lrelu_slope,
+                          int pool, int out_nchw, int dilate_h, void* stream);
+/* 1 (default, or WITW_CONV_WINO in the environment): witw_conv3x3_fwd_wino takes the Winograd form where it can; 0: always the
+ * direct form (A/B runs). enable < 0 only queries; returns the previous setting. */
+int witw_conv3x3_wino(int enable);
 /* backward of the fused MaxPool2d(2,2): pool_code (written by the forward when non-NULL: first arg-max position
  * dy*2+dx in torch's scan order) routes dy [B,Hp,Wp,C] into dx [B,H,W,C] (H>=2Hp, W>=2Wp). */
 int witw_maxpool2x2_bwd(const float* dy, const unsigned char* pool_code, float* dx, int B, int Hp, int Wp, int H, int W,

@@ -17,6 +17,7 @@ SIGNATURES = {
     'witw_last_error': (c_char_p, []),
     'witw_version': (c_int, []),
     'witw_last_kernel_variant': (c_char_p, []),
+    'witw_last_conv_form': (c_char_p, []),
     'witw_device_check': (c_int, [c_int]),
     'witw_conv3x3_tile_n': (c_int, [c_int]),
     'witw_conv3x3_workgroup_waves': (c_int, [c_int] * 5),
@@ -27,6 +28,10 @@ SIGNATURES = {
     'witw_conv3x3_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_void_p]),
     'witw_conv3x3_fwd_ex': (c_int, [c_void_p] * 9 + [c_int] * 8 + [c_float] + [c_int] * 3 + [c_void_p]),
     'witw_conv3x3_dil_skip': (c_int, [c_int]),
+    'witw_conv3x3_packed_floats_wino': (c_longlong, [c_int, c_int]),
+    'witw_conv3x3_pack_weights_wino': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'witw_conv3x3_fwd_wino': (c_int, [c_void_p] * 10 + [c_int] * 8 + [c_float] + [c_int] * 3 + [c_void_p]),
+    'witw_conv3x3_wino': (c_int, [c_int]),
     'witw_maxpool2x2_bwd': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     'witw_conv3x3_packed_floats_taps4': (c_longlong, [c_int, c_int]),
     'witw_conv3x3_pack_weights_taps4': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

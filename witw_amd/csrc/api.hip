@@ -13,13 +13,17 @@ void witw_set_error(const char* fmt, ...) {
 }
 
 static thread_local char g_variant[128] = "";
+static thread_local const char* g_conv_form = "";
 
 void witw_note_variant(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_variant, sizeof(g_variant), fmt, ap);
     va_end(ap);
+    g_conv_form = "direct";
 }
+
+void witw_note_conv_form(const char* form) { g_conv_form = form; }
 
 // Compute units of the CURRENT device (256 on MI355X), looked up once PER DEVICE (a process may drive several: the
 // --single-device rehearsals, mixed parts); 256 when the query fails. The cache slots are relaxed atomics: two threads that
@@ -58,6 +62,9 @@ const char* witw_last_error(void) { return g_err; }
 // Name of the kernel instantiation the calling thread's most recent conv launcher picked (template arguments as in the
 // rocprof kernel names), "" before the first launch. Lets a parity test assert WHICH kernel it compared with the oracle.
 const char* witw_last_kernel_variant(void) { return g_variant; }
+
+// Arithmetic form of that launch: "direct" or "wino_h2" (Winograd F(2,3) along H, witw_conv3x3_fwd_wino), "" before the first.
+const char* witw_last_conv_form(void) { return g_conv_form; }
 
 int witw_version(void) { return 200; }  // 0.2.0: batch-hard loss, pair-list match backward
 

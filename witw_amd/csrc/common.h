@@ -18,7 +18,8 @@ enum {
 };
 
 void witw_set_error(const char* fmt, ...);
-void witw_note_variant(const char* fmt, ...);   // records the launched instantiation (witw_last_kernel_variant)
+void witw_note_variant(const char* fmt, ...);   // records the launched instantiation (witw_last_kernel_variant); form "direct"
+void witw_note_conv_form(const char* form);     // overrides the recorded arithmetic form (witw_last_conv_form)
 
 #define WITW_CHECK_ARG(cond, ...)                \
     do {                                         \

@@ -57,10 +57,291 @@ struct ConvArgs {
     // [B, s2d_h, s2d_w, 4*Cout] with channel ((y&1)*2 + (x&1))*Cout + c; outputs at y >= valid_h or x >= valid_w are
     // written as 0 (the conv grid is padded to the tile; the next layer's window must read zeros there).
     int s2d, s2d_h, s2d_w, valid_h, valid_w;
+    // 1: Winograd F(2,3) along H (conv_wino_h2): wpk_wino is the filter of witw_conv3x3_pack_weights_wino, n_tiles counts
+    // 64-channel tiles. Set by the launcher only for stride 1, no gate / dil_h / NCHW output / post affine, geometry 0.
+    int wino;
+    const float* wpk_wino;
 #ifdef WITW_STAMPS
     unsigned long long* stamps;   // diagnostic build only (tools/conv_stamps.cpp)
 #endif
 };
+
+// ---- Winograd F(2,3) along H (inference, stride 1, 3x3, geometry 0; a per-launch mode of conv3x3_nhwc_f32_kernel)
+// For an output row pair (r, r+1) and one column tap kw, the 4 input rows d0..d3 = rows r-1..r+2 give
+//   V0 = d0-d2, V1 = d1+d2, V2 = d2-d1, V3 = d1-d3             (in registers, after the raw ds_read_b128)
+//   m_t += V_t . U_t  with  U0 = g0, U1 = ((g0+g1)+g2)/2, U2 = ((g0-g1)+g2)/2, U3 = g2   (packed once, pack_weights_wino_kernel)
+//   y0 = (m0+m1)+m2, y1 = (m1-m2)-m3                               (epilogue)
+// 4 products per (row pair, kw) instead of 6: 2/3 of the MFMAs of the direct form. Only H is transformed: W is the circularly
+// padded axis, whose outputs must not depend on which of them share a tile. Accumulators per output double, so a wave covers
+// half of what a direct wave covers: one row pair x 64 columns x 32 channels (acc[t][column half], 128 VGPRs); the workgroup
+// tile is NW rows x 64 columns x 64 channels whatever TN names, the halo tile is staged exactly as in the direct form and the
+// filter slab of a K chunk is [kw][t][quad][64] (12 slices instead of 9 of twice the width). Every output gets the same
+// arithmetic in the same order (chunk -> kw -> channel) at NW = 4 and 8.
+template <int NW, bool POOL>
+__device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
+    constexpr int TH = NW, TW = 64, IW = TW + 2, IH = TH + 2;
+    constexpr int NTHREADS = 64 * NW;
+    constexpr int WTN = 64;                    // output channels per workgroup
+    constexpr int IN_F4 = 2 * IH * IW;
+    constexpr int W_F4 = 12 * 2 * WTN;         // [kw][t][quad][n]
+    constexpr int STAGE_F4 = IN_F4 + W_F4;
+    constexpr int NIN = (IN_F4 + NTHREADS - 1) / NTHREADS;
+    constexpr int NWT = W_F4 / NTHREADS;
+    static_assert(NWT * NTHREADS == W_F4, "the filter slab splits evenly over the workgroup");
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int l31 = lane & 31;
+    const int hq = lane >> 5;
+
+    int ntile, sp;          // block -> (n tile, image, spatial tile): as in the direct form
+    if (p.xcd_map) {
+        const int g = blockIdx.x >> 3;
+        ntile = g % p.n_tiles;
+        sp = (blockIdx.x & 7) * p.sp_per_xcd + g / p.n_tiles;
+        if (sp >= p.sp_total) return;
+    } else {
+        ntile = blockIdx.x / p.sp_total;
+        sp = blockIdx.x - ntile * p.sp_total;
+    }
+    const int tiles_img = p.tiles_x * p.tiles_y;
+    const int b = sp / tiles_img;
+    sp -= b * tiles_img;
+    const int ty = sp / p.tiles_x;
+    const int tx = sp - ty * p.tiles_x;
+    const int oy0 = ty * TH;
+    const int ox0 = tx * TW;
+    const int n0 = ntile * WTN;
+    const int nkc = p.Cin >> 3;
+
+    constexpr unsigned OOR = 0x80000000u;
+    const size_t img_floats = (size_t)p.H * p.W * p.Cin;
+    __amdgpu_buffer_rsrc_t in_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b * img_floats), 0,
+                                                                     (unsigned)(img_floats * 4), 0x00020000);
+    __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(reinterpret_cast<const f32x4*>(p.wpk_wino) + (size_t)ntile * nkc * W_F4), 0, (unsigned)nkc * W_F4 * 16u, 0x00020000);
+    unsigned gin[NIN];
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) {
+        const int s = tid + i * NTHREADS;
+        const int pix = s >> 1, q = s & 1;
+        const int r = pix / IW, c = pix - r * IW;
+        const int gr = oy0 - 1 + r;
+        int gc = ox0 - 1 + c;
+        bool ok = (s < IN_F4) && gr >= 0 && gr < p.H;
+        if (p.circ) {
+            gc %= p.W;
+            if (gc < 0) gc += p.W;
+        } else {
+            ok = ok && gc >= 0 && gc < p.W;
+        }
+        gin[i] = ok ? (unsigned)((((size_t)gr * p.W + gc) * p.Cin + q * 4) * 4) : OOR;
+    }
+    const unsigned gwoff = (unsigned)tid * 16u;
+    f32x4 rin[NIN], rw[NWT];
+    auto load_stage = [&](int kc) {
+#pragma unroll
+        for (int i = 0; i < NIN; ++i)
+            rin[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rs, gin[i], (unsigned)kc * 32u, 0));
+        const unsigned wbase = (unsigned)kc * W_F4 * 16u;
+#pragma unroll
+        for (int i = 0; i < NWT; ++i)
+            rw[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rs, gwoff, wbase + (unsigned)i * (NTHREADS * 16u), 0));
+    };
+    auto store_stage = [&](int buf) {
+        f32x4* in_s = smem + buf * STAGE_F4;
+        f32x4* w_s = in_s + IN_F4;
+#pragma unroll
+        for (int i = 0; i < NIN; ++i) {
+            const int s = tid + i * NTHREADS;
+            f32x4* dst = (NIN * NTHREADS == IN_F4 || s < IN_F4) ? in_s + (s & 1) * (IH * IW) + (s >> 1) : smem + 2 * STAGE_F4;
+            *dst = rin[i];
+        }
+#pragma unroll
+        for (int i = 0; i < NWT; ++i) w_s[tid + i * NTHREADS] = rw[i];
+    };
+
+    // wave -> (row pair wm, channel half wn); step s = (kw = s >> 1, column half ct = s & 1), 6 steps per K chunk
+    const int wm = wave >> 1, wn = wave & 1;
+    const int abase = hq * (IH * IW) + 2 * wm * IW + l31;
+    const int wbase = hq * WTN + wn * 32 + l31;
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][ct][r] = 0.f;
+
+    // fa: input rows d0..d3 of a step, transformed in place into V0..V3 late in the step before; fb: filter slices U0..U3 of a kw
+    f32x4 fa[2][4], fb[2][4];
+    auto read_a = [&](int set, const f32x4* in_s, int s) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[set][i] = in_s[abase + i * IW + 32 * (s & 1) + (s >> 1)];
+    };
+    auto read_b = [&](int set, const f32x4* w_s, int kw) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) fb[set][t] = w_s[(kw * 4 + t) * 2 * WTN + wbase];
+    };
+    auto transform = [&](int set) {      // 16 single v_add_f32 / v_sub_f32 (packed f32 VALU beside MFMAs costs more)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float d0 = fa[set][0][j], d1 = fa[set][1][j], d2 = fa[set][2][j], d3 = fa[set][3][j];
+            fa[set][0][j] = d0 - d2;
+            fa[set][1][j] = d1 + d2;
+            fa[set][2][j] = d2 - d1;
+            fa[set][3][j] = d1 - d3;
+        }
+    };
+    auto mfma_step = [&](int set, int bset, int ct) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                acc[t][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][t][j], fb[bset][t][j], acc[t][ct], 0, 0, 0);
+    };
+
+    load_stage(0);
+    store_stage(0);
+    __syncthreads();
+    read_a(0, smem, 0);
+    read_b(0, smem + IN_F4, 0);
+    transform(0);
+
+    // Issue order per step (16 MFMAs): each LDS / global instruction alone behind an MFMA, the next step's fragment reads
+    // first; the transform of those fragments follows the step's MFMAs in program order.
+#define SG_STEP(NR, MASK, NX)                                           \
+    do {                                                                \
+        _Pragma("unroll") for (int i_ = 0; i_ < (NR); ++i_) {           \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          \
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);          \
+        }                                                               \
+        _Pragma("unroll") for (int i_ = 0; i_ < (NX); ++i_) {           \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          \
+            __builtin_amdgcn_sched_group_barrier(MASK, 1, 0);           \
+        }                                                               \
+        _Pragma("unroll") for (int i_ = 0; i_ < 16 - (NR) - (NX); ++i_) \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          \
+    } while (0)
+    static_assert(16 - 4 - (NIN + NWT) >= 0, "step too short to hide the staging instructions");
+
+    // B slices: kw 0 and 2 in set 0, kw 1 in set 1 (kw 2 read in step 2, behind the last use of kw 0); the next chunk's kw 0
+    // arrives in set 1 during step 5, behind the chunk's single barrier, and is moved to set 0. Next chunk: loads under step 0,
+    // LDS writes under step 3.
+    for (int kc = 0; kc < nkc; ++kc) {
+        const int cur = kc & 1;
+        const int kn = (kc + 1 < nkc) ? kc + 1 : kc;   // last chunk restages itself (never read)
+        const f32x4* in_s = smem + cur * STAGE_F4;
+        const f32x4* w_s = in_s + IN_F4;
+        const f32x4* in_n = smem + (cur ^ 1) * STAGE_F4;
+        read_a(1, in_s, 1);
+        load_stage(kn);
+        mfma_step(0, 0, 0);
+        transform(1);
+        SG_STEP(4, 0x020, NIN + NWT);
+        read_a(0, in_s, 2);
+        read_b(1, w_s, 1);
+        mfma_step(1, 0, 1);
+        transform(0);
+        SG_STEP(8, 0x020, 0);
+        read_a(1, in_s, 3);
+        read_b(0, w_s, 2);
+        mfma_step(0, 1, 0);
+        transform(1);
+        SG_STEP(8, 0x020, 0);
+        read_a(0, in_s, 4);
+        store_stage(cur ^ 1);
+        mfma_step(1, 1, 1);
+        transform(0);
+        SG_STEP(4, 0x200, NIN + NWT);
+        read_a(1, in_s, 5);
+        mfma_step(0, 0, 0);
+        transform(1);
+        SG_STEP(4, 0x020, 0);
+        __syncthreads();
+        read_a(0, in_n, 0);
+        read_b(1, in_n + IN_F4, 0);
+        mfma_step(1, 0, 1);
+        transform(0);
+        SG_STEP(8, 0x020, 0);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) fb[0][t] = fb[1][t];
+    }
+#undef SG_STEP
+
+    // ---- epilogue: output transform, bias, dropout scale, ReLU, optional 2x2 max pool (the wave's own row pair), 16-byte stores
+    // through a wave-private 4 KB LDS slab (32 pixels x 32 channels; the staging buffers are dead behind the loop's last barrier)
+    f32x16 yv[2][2];       // [output row of the pair][column half]
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float m0 = acc[0][ct][r], m1 = acc[1][ct][r], m2 = acc[2][ct][r], m3 = acc[3][ct][r];
+            yv[0][ct][r] = (m0 + m1) + m2;
+            yv[1][ct][r] = (m1 - m2) - m3;
+        }
+    const int nb = n0 + wn * 32;
+    const int nch = nb + l31;
+    const float bv = p.bias[nch];
+    const float dm = (p.dropmask != nullptr && nch < p.Cout) ? p.dropmask[(size_t)b * p.Cout + nch] : 1.f;
+    const int act = p.relu;
+    auto fin = [&](float v) {
+        v = (v + bv) * dm;
+        if (act == 1) v = fmaxf(v, 0.f);
+        else if (act == 2) v = v > 0.f ? v : v * p.lrelu;
+        return v;
+    };
+    const int Hy = POOL ? (p.Ho >> 1) : p.Ho;
+    const int Wy = POOL ? (p.Wo >> 1) : p.Wo;
+    float* slab = reinterpret_cast<float*>(smem) + wave * (32 * 32);
+    const int prow = lane >> 3, pc4 = (lane & 7) * 4;     // read-back role: pixel in a group of 8, channel quad
+    if constexpr (!POOL) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) slab[((r & 3) + 8 * (r >> 2) + 4 * hq) * 32 + l31] = fin(yv[k][ct][r]);
+                const int yy = oy0 + 2 * wm + k;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int m = g * 8 + prow;
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(slab + m * 32 + pc4);
+                    const int xx = ox0 + 32 * ct + m;
+                    if (yy < Hy && xx < Wy && nb + pc4 < p.Cout)
+                        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.y + (((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nb + pc4));
+                }
+            }
+    } else {
+        const int yy = (oy0 + 2 * wm) >> 1;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int r = 4 * g + 2 * e;
+                    const float a00 = yv[0][ct][r], a01 = yv[0][ct][r + 1], a10 = yv[1][ct][r], a11 = yv[1][ct][r + 1];
+                    const float m = fmaxf(fmaxf(a00, a01), fmaxf(a10, a11));
+                    const int pc = 16 * ct + 4 * g + 2 * hq + e;
+                    slab[pc * 32 + l31] = fin(m);
+                    const int xx = (ox0 >> 1) + pc;
+                    if (p.pool_code != nullptr && yy < Hy && xx < Wy && nch < p.Cout) {
+                        const int code = (a00 == m) ? 0 : (a01 == m) ? 1 : (a10 == m) ? 2 : 3;
+                        p.pool_code[(((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nch] = (unsigned char)code;
+                    }
+                }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int pc = g * 8 + prow;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(slab + pc * 32 + pc4);
+            const int xx = (ox0 >> 1) + pc;
+            if (yy < Hy && xx < Wy && nb + pc4 < p.Cout)
+                __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.y + (((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nb + pc4));
+        }
+    }
+}
 
 // NW = waves per workgroup (4: 4x64-pixel tile, one wave per SIMD; 8: 8x64-pixel tile, two waves per SIMD
 // sharing one weight slab: 40 % less staging and half the barriers per MFMA, used when the layer is tall
@@ -98,9 +379,19 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_f32_kernel(ConvArgs p) {
 
     // +1: dummy slot that absorbs out-of-tile staging stores. The epilogue re-uses the buffer as NW wave-private 8 KB slabs:
     // with 4 taps and TN = 64 two stages are smaller than 8 slabs (58.6 KB < 64 KB), so the array is sized for both uses.
-    constexpr int SMEM_F4 = (2 * STAGE_F4 + 1 > NW * 512) ? 2 * STAGE_F4 + 1 : NW * 512;
+    // WINO: the classes that also run the Winograd F(2,3)-along-H form (conv_wino_h2) when the launcher sets p.wino
+    constexpr bool WINO = SH == 1 && TAPS == 9 && GEO == 0 && (TN == 128 || POOL);
+    constexpr int WINO_F4 = WINO ? 2 * (2 * (NW + 2) * IW + 12 * 2 * 64) + 1 : 0;
+    constexpr int DIRECT_F4 = (2 * STAGE_F4 + 1 > NW * 512) ? 2 * STAGE_F4 + 1 : NW * 512;
+    constexpr int SMEM_F4 = DIRECT_F4 > WINO_F4 ? DIRECT_F4 : WINO_F4;
     __shared__ f32x4 smem[SMEM_F4];
     static_assert(SMEM_F4 * 16 >= NW * 32 * 64 * 4, "the buffer must hold one epilogue slab per wave");
+    if constexpr (WINO) {
+        if (p.wino) {
+            conv_wino_h2<NW, POOL>(p, smem);
+            return;
+        }
+    }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -623,6 +914,33 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restri
     reinterpret_cast<f32x4*>(wpk)[idx] = v;
 }
 
+// Winograd filter of conv_wino_h2, one thread per packed float4: wpk[nt][kc][kw][t][q][n][0..3] (64-channel tiles) from
+// w[cout][cin][3][3] (torch KCRS), per column tap kw with g_kh = w[..][kh][kw]:
+//   U0 = g0, U1 = ((g0+g1)+g2)*0.5, U2 = ((g0-g1)+g2)*0.5, U3 = g2   (exact x0.5; the library is built without contraction)
+__global__ void pack_weights_wino_kernel(const float* __restrict__ w, float* __restrict__ wpk, int Cout, int Cin, int nkc,
+                                         size_t total) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    size_t t = idx;
+    const int n = t % 64; t /= 64;
+    const int q = t % 2; t /= 2;
+    const int tr = t % 4; t /= 4;
+    const int kw = t % 3; t /= 3;
+    const int kc = t % nkc; t /= nkc;
+    const int co = (int)t * 64 + n;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int ci = kc * 8 + q * 4 + j;
+        if (co < Cout && ci < Cin) {
+            const float* g = w + ((size_t)co * Cin + ci) * 9 + kw;
+            const float g0 = g[0], g1 = g[3], g2 = g[6];
+            v[j] = tr == 0 ? g0 : tr == 1 ? ((g0 + g1) + g2) * 0.5f : tr == 2 ? ((g0 - g1) + g2) * 0.5f : g2;
+        }
+    }
+    reinterpret_cast<f32x4*>(wpk)[idx] = v;
+}
+
 // NCHW [B,C,H,W] -> NHWC8 [B,H,W,8], channels >= C zero filled (C <= 8).
 __global__ void nchw_to_nhwc8_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int C, int H, int W) {
     const size_t npix = (size_t)B * H * W;
@@ -653,7 +971,7 @@ int launch_conv_nw(ConvArgs a, hipStream_t st) {
     a.tiles_y = cdiv(a.Ho, GEO == 1 ? 4 * NW : NW);
     a.tiles_x = cdiv(a.Wo, GEO == 1 ? 16 : 64);
     const long long sp_total = (long long)a.B * a.tiles_x * a.tiles_y;
-    a.n_tiles = cdiv(a.Cout, TN);
+    a.n_tiles = cdiv(a.Cout, a.wino ? 64 : TN);      // the Winograd form tiles 64 output channels per workgroup
     a.sp_per_xcd = (int)((sp_total + 7) / 8);
     // fewer spatial tiles than XCDs: the XCD-aware order would put every workgroup (all n tiles and K slices of a spatial tile) on
     // sp_total of the 8 XCDs -- cvig_baseline's last block, 2 mosaics x 4 n tiles x 32 K slices, ran on 64 of the 256 CUs
@@ -668,6 +986,7 @@ int launch_conv_nw(ConvArgs a, hipStream_t st) {
     hipLaunchKernelGGL((conv3x3_nhwc_f32_kernel<TN, SH, POOL, NW, GEO, TAPS>), dim3((unsigned)grid, gy), dim3(64 * NW), 0, st, a);
     WITW_CHECK_LAUNCH("conv3x3_nhwc_f32");
     witw_note_variant("conv3x3_nhwc_f32_kernel<%d,%d,%s,%d,%d,%d>", TN, SH, POOL ? "true" : "false", NW, GEO, TAPS);
+    if (a.wino) witw_note_conv_form("wino_h2");
     return WITW_OK;
 }
 
@@ -698,8 +1017,26 @@ int dil_skip() {
     return g_dil_skip;
 }
 
+// 1 (default): a launch given a Winograd-packed filter runs the F(2,3)-along-H form where its class has one; 0: the direct form
+// (WITW_CONV_WINO=0 / witw_conv3x3_wino(0): A/B runs)
+int g_wino = -1;
+int wino_on() {
+    if (g_wino < 0) {
+        const char* e = getenv("WITW_CONV_WINO");
+        g_wino = e ? (atoi(e) != 0) : 1;
+    }
+    return g_wino;
+}
+
 template <int TN, int SH, bool POOL>
-int launch_conv(const ConvArgs& a, hipStream_t st) {
+int launch_conv(ConvArgs a, hipStream_t st) {
+    // the Winograd form: stride 1, 3x3, wide geometry, plain inference epilogue (no gate / dil_h / NCHW / affine), Cout % 4 == 0
+    const bool wino = SH == 1 && (TN == 128 || POOL) && a.wpk_wino != nullptr && wino_on() && a.gate == nullptr && !a.dil_h &&
+                      !a.out_nchw && a.post_scale == nullptr && (a.Cout & 3) == 0 && a.force_geo != 1 &&
+                      !choose_narrow(a.Wo, a.force_geo);
+    a.wino = wino ? 1 : 0;
+    if (wino) return choose_waves(a.B, a.Ho, a.Wo, a.Cout, a.force_nw) == 8 ? launch_conv_nw<TN, SH, POOL, 8, 0>(a, st)
+                                                                          : launch_conv_nw<TN, SH, POOL, 4, 0>(a, st);
 #ifndef WITW_NO_NARROW
     if (choose_narrow(a.Wo, a.force_geo)) return launch_conv_nw<TN, SH, POOL, 4, 1>(a, st);
 #endif
@@ -854,6 +1191,7 @@ int witw_conv3x3_fwd_taps4_ex(const float* x, const float* wpk4, const float* bi
     a.xcd_map = env_int("WITW_CONV_XCD", 1) != 0;
     a.circ = 0; a.relu = relu; a.out_nchw = 0; a.dil_h = 0; a.tap_base = tap_base;
     a.ksplit = ksplit;
+    a.wino = 0; a.wpk_wino = nullptr;
     a.kc_per_split = cdiv(Cin >> 3, ksplit);
     WITW_CHECK_ARG((long long)(ksplit - 1) * a.kc_per_split < (Cin >> 3), "conv3x3_fwd_taps4: ksplit=%d leaves an empty K slice", ksplit);
     a.split_stride = (size_t)B * H * W * Cout;
@@ -894,10 +1232,14 @@ int witw_nchw_to_nhwc(const float* x, float* y, int B, int C, int H, int W, int 
     return WITW_OK;
 }
 
-int witw_conv3x3_fwd_ex(const float* x, const float* wpk, const float* bias, const float* dropmask, const float* gate,
-                        const float* post_scale, const float* post_shift, float* y, unsigned char* pool_code, int B, int H,
-                        int W, int Cin, int Cout, int stride_h, int pad_circular, int relu, float lrelu_slope, int pool,
-                        int out_nchw, int dilate_h, void* stream) {
+}  // extern "C"
+
+namespace {
+
+int conv3x3_fwd_any(const float* x, const float* wpk, const float* wpk_wino, const float* bias, const float* dropmask,
+                    const float* gate, const float* post_scale, const float* post_shift, float* y, unsigned char* pool_code, int B,
+                    int H, int W, int Cin, int Cout, int stride_h, int pad_circular, int relu, float lrelu_slope, int pool,
+                    int out_nchw, int dilate_h, void* stream) {
     WITW_CHECK_ARG(x && wpk && bias && y, "conv3x3_fwd: null pointer");
     WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cout > 0, "conv3x3_fwd: bad shape B=%d H=%d W=%d Cout=%d", B, H, W, Cout);
     WITW_CHECK_ARG(Cin > 0 && (Cin % 8) == 0, "conv3x3_fwd: Cin=%d must be a positive multiple of 8", Cin);
@@ -923,6 +1265,7 @@ int witw_conv3x3_fwd_ex(const float* x, const float* wpk, const float* bias, con
     a.xcd_map = env_int("WITW_CONV_XCD", 1) != 0;      // 0: plain n-tile-major order (A/B timing)
     a.circ = pad_circular; a.relu = relu; a.out_nchw = out_nchw; a.dil_h = dilate_h; a.tap_base = 0;
     a.ksplit = 1; a.kc_per_split = 0; a.split_stride = 0; a.s2d = 0; a.s2d_h = a.s2d_w = a.valid_h = a.valid_w = 0;
+    a.wino = 0; a.wpk_wino = wpk_wino;      // the launcher decides the form
 #ifdef WITW_STAMPS
     a.stamps = witw_conv_stamps_ptr;
 #endif
@@ -934,6 +1277,53 @@ int witw_conv3x3_fwd_ex(const float* x, const float* wpk, const float* bias, con
     }
     if (stride_h == 2) return launch_conv<64, 2, false>(a, st);
     return pool ? launch_conv<64, 1, true>(a, st) : launch_conv<64, 1, false>(a, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int witw_conv3x3_fwd_ex(const float* x, const float* wpk, const float* bias, const float* dropmask, const float* gate,
+                        const float* post_scale, const float* post_shift, float* y, unsigned char* pool_code, int B, int H,
+                        int W, int Cin, int Cout, int stride_h, int pad_circular, int relu, float lrelu_slope, int pool,
+                        int out_nchw, int dilate_h, void* stream) {
+    return conv3x3_fwd_any(x, wpk, nullptr, bias, dropmask, gate, post_scale, post_shift, y, pool_code, B, H, W, Cin, Cout,
+                           stride_h, pad_circular, relu, lrelu_slope, pool, out_nchw, dilate_h, stream);
+}
+
+// witw_conv3x3_fwd_ex with both packings of the filter: the launch runs the Winograd F(2,3)-along-H form (wpk_wino) where its class
+// and arguments allow it and witw_conv3x3_wino() is on, the direct form (wpk) otherwise; witw_last_conv_form() says which.
+int witw_conv3x3_fwd_wino(const float* x, const float* wpk, const float* wpk_wino, const float* bias, const float* dropmask,
+                          const float* gate, const float* post_scale, const float* post_shift, float* y, unsigned char* pool_code,
+                          int B, int H, int W, int Cin, int Cout, int stride_h, int pad_circular, int relu, float lrelu_slope,
+                          int pool, int out_nchw, int dilate_h, void* stream) {
+    WITW_CHECK_ARG(wpk_wino, "conv3x3_fwd_wino: null Winograd filter");
+    return conv3x3_fwd_any(x, wpk, wpk_wino, bias, dropmask, gate, post_scale, post_shift, y, pool_code, B, H, W, Cin, Cout,
+                           stride_h, pad_circular, relu, lrelu_slope, pool, out_nchw, dilate_h, stream);
+}
+
+// 1 (default): launches given a Winograd-packed filter run the Winograd form where they can; 0: the direct form. enable < 0 only
+// queries. Returns the previous setting.
+int witw_conv3x3_wino(int enable) {
+    const int prev = wino_on();
+    if (enable >= 0) g_wino = enable != 0;
+    return prev;
+}
+
+long long witw_conv3x3_packed_floats_wino(int cout, int cin) {
+    if (cout <= 0 || cin <= 0) return -1;
+    return (long long)cdiv(cout, 64) * cdiv(cin, 8) * 12 * 2 * 64 * 4;
+}
+
+int witw_conv3x3_pack_weights_wino(const float* w_kcrs, float* wpk_wino, int cout, int cin, void* stream) {
+    WITW_CHECK_ARG(w_kcrs && wpk_wino, "pack_weights_wino: null pointer");
+    WITW_CHECK_ARG(cout > 0 && cin > 0, "pack_weights_wino: bad shape cout=%d cin=%d", cout, cin);
+    const int n_tiles = cdiv(cout, 64), nkc = cdiv(cin, 8);
+    const size_t total = (size_t)n_tiles * nkc * 12 * 2 * 64;
+    hipLaunchKernelGGL(pack_weights_wino_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       w_kcrs, wpk_wino, cout, cin, nkc, total);
+    WITW_CHECK_LAUNCH("pack_weights_wino");
+    return WITW_OK;
 }
 
 // 1 (default): a zero-interleaved launch (dilate_h) on the 8-wave 128-channel tile does not issue the MFMAs whose input rows are

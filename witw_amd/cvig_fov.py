@@ -156,14 +156,17 @@ class FOV_DSM(torch.nn.Module):
         self.dropout_stream = 1 if circ_padding else 0
         self._drop_step = 0
 
-    def _pack(self, idx):
+    def _pack(self, idx, wino=False):
+        """packed filter of layer idx; wino=True: with the Winograd F(2,3)-along-H filter too (inference launches only: the
+        training forward keeps the direct form whose activations the backward reconciles with)"""
         conv = _conv_of(self.model.features[idx])
         key = (conv.weight.data_ptr(), conv.weight._version, conv.bias._version, getattr(conv.weight, '_witw_version', 0),
                getattr(conv.bias, '_witw_version', 0))
-        hit = self._packed.get(idx)
+        slot = ('w', idx) if wino else idx
+        hit = self._packed.get(slot)
         if hit is None or hit[0] != key:
-            hit = (key, ops.PackedConv(conv.weight, conv.bias, reuse=hit[1] if hit else None))
-            self._packed[idx] = hit
+            hit = (key, ops.PackedConv(conv.weight, conv.bias, reuse=hit[1] if hit else None, wino=wino))
+            self._packed[slot] = hit
         return hit[1]
 
     def _pack_t(self, idx):
@@ -210,7 +213,9 @@ class FOV_DSM(torch.nn.Module):
                 h = ops.conv3x3_first_fwd(h, self._pack_first(False), circular=self.circ_padding, relu=relu)
                 continue
             keep = keep_from is not None and idx >= keep_from
-            out = ops.conv3x3_fwd(h, self._pack(idx), stride_h=sh, circular=self.circ_padding, relu=relu, pool=pool,
+            # no backward consumes an inference pass: its stride-1 layers may run the Winograd form
+            pk = self._pack(idx, wino=keep_from is None and sh == 1)
+            out = ops.conv3x3_fwd(h, pk, stride_h=sh, circular=self.circ_padding, relu=relu, pool=pool,
                                   out_nchw=(idx == last), drop_scale=scales.get(idx), want_pool_code=(keep and pool))
             y, code = out if (keep and pool) else (out, None)
             if keep:

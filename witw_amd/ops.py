@@ -38,10 +38,14 @@ class PackedConv:
     2x2 sub-window that is live in a filter whose first tap row/column are zero (cvig_baseline's 4x4/s2 convs over the
     space-to-depth image; with transpose_flip: the dgrad filter, whose LAST row/column are zero) for the 4-tap kernels."""
 
-    def __init__(self, weight, bias, transpose_flip=False, taps4=False, reuse=None):
+    def __init__(self, weight, bias, transpose_flip=False, taps4=False, reuse=None, wino=False):
         """reuse: a PackedConv of the same layer and mode whose device buffers are overwritten in place (re-packing
-        after an optimizer step without allocating or zero-filling; stream order keeps earlier launches safe)."""
+        after an optimizer step without allocating or zero-filling; stream order keeps earlier launches safe).
+        wino: also pack the Winograd F(2,3)-along-H filter (wpk_wino); conv3x3_fwd then lets the launcher run that form
+        where it applies (inference launches; witw_conv3x3_fwd_wino)."""
         lib = _lib.load()
+        if wino and (transpose_flip or taps4):
+            raise _lib.WitwError('PackedConv: the Winograd filter is packed for forward 3x3 launches only')
         w = _dev_f32(weight.detach(), 'weight')
         if transpose_flip:
             cin, cout = w.shape[0], w.shape[1]   # packed filter maps grad_out (w.shape[0]) -> grad_in
@@ -63,6 +67,13 @@ class PackedConv:
             self.wpk = reuse.wpk if reuse is not None else torch.empty(n_pk, dtype=torch.float32, device=w.device)
             _lib.check(lib.witw_conv3x3_pack_weights(w.data_ptr(), self.wpk.data_ptr(), cout, cin, int(transpose_flip),
                                                      _stream()), 'witw_conv3x3_pack_weights')
+        self.wpk_wino = None
+        if wino:
+            n_w = lib.witw_conv3x3_packed_floats_wino(cout, cin)
+            old = getattr(reuse, 'wpk_wino', None)
+            self.wpk_wino = old if old is not None and old.numel() == n_w else torch.empty(n_w, dtype=torch.float32, device=w.device)
+            _lib.check(lib.witw_conv3x3_pack_weights_wino(w.data_ptr(), self.wpk_wino.data_ptr(), cout, cin, _stream()),
+                       'witw_conv3x3_pack_weights_wino')
         nb = lib.witw_conv3x3_bias_floats(cout)
         self.bias = reuse.bias if reuse is not None else torch.zeros(nb, dtype=torch.float32, device=w.device)
         if bias is not None and not transpose_flip:
@@ -263,6 +274,11 @@ def conv3x3_fwd(x_nhwc, packed, stride_h=1, circular=False, relu=True, pool=Fals
         _lib.check(lib.witw_conv3x3_fwd_taps4(x.data_ptr(), packed.wpk.data_ptr(), packed.bias.data_ptr(), _p(gate),
                                               _p(post_scale), _p(post_shift), y.data_ptr(), B, H, W, C, packed.cout, act,
                                               float(lrelu_slope or 0.), packed.tap_base, _stream()), 'witw_conv3x3_fwd_taps4')
+    elif getattr(packed, 'wpk_wino', None) is not None:
+        _lib.check(lib.witw_conv3x3_fwd_wino(x.data_ptr(), packed.wpk.data_ptr(), packed.wpk_wino.data_ptr(), packed.bias.data_ptr(),
+                                             _p(drop_scale), _p(gate), _p(post_scale), _p(post_shift), y.data_ptr(), _p(code), B, H,
+                                             W, C, packed.cout, stride_h, int(circular), act, float(lrelu_slope or 0.), int(pool),
+                                             int(out_nchw), int(bool(dilate_h)), _stream()), 'witw_conv3x3_fwd_wino')
     else:
         _lib.check(lib.witw_conv3x3_fwd_ex(x.data_ptr(), packed.wpk.data_ptr(), packed.bias.data_ptr(), _p(drop_scale),
                                            _p(gate), _p(post_scale), _p(post_shift), y.data_ptr(), _p(code), B, H, W, C,
@@ -1296,6 +1312,17 @@ def exhaustive_triplet_loss(D, soft_margin=False, alpha=10., margin=1.):
     _lib.check(lib.witw_exhaustive_triplet_loss(D.data_ptr(), B, int(soft_margin), float(alpha), float(margin),
                                                 loss.data_ptr(), ws.data_ptr(), _stream()), 'witw_exhaustive_triplet_loss')
     return loss.reshape(())
+
+
+def last_conv_form():
+    """Arithmetic form of the calling thread's last conv launch: 'direct' or 'wino_h2' (witw_last_conv_form)."""
+    v = _lib.load().witw_last_conv_form()
+    return v.decode() if v else ''
+
+
+def conv_wino(enable=None):
+    """Query (enable=None) or set the Winograd switch of witw_conv3x3_fwd_wino; returns the previous setting."""
+    return bool(_lib.load().witw_conv3x3_wino(-1 if enable is None else int(bool(enable))))
 
 
 def last_kernel_variant():
