@@ -145,6 +145,14 @@ int witw_adam_step_multi(float* const* param, const float* const* grad, float* c
 long long witw_match_workspace_floats(int Bo, int Bs);
 int witw_match_fwd(const float* ov, const float* su, int Bo, int Bs, int We, long long* orientation, float* distance,
                    float* score, float* workspace, void* stream);
+/* witw_match_fwd with an orientation prior: shift_mask [Bs] (device, may be NULL = witw_match_fwd) holds one 64-bit word per surface
+ * embedding, bit k set = shift k may be chosen. orientation[o][s] = the FIRST maximum of the correlation over the allowed shifts of
+ * s; distance and score are taken at that shift, as in witw_match_fwd. A word of 0 means "no prior" and behaves like all 64 bits
+ * set, so no shift outside [0,64) can reach the window norms or the backward; an all-ones mask gives the bits of witw_match_fwd.
+ * The mask never changes which kernel runs for a shape. witw_match_bwd takes orientation as a constant of the graph and is the
+ * backward of this entry as it is. */
+int witw_match_fwd_masked(const float* ov, const float* su, int Bo, int Bs, int We, long long* orientation, float* distance,
+                          float* score, float* workspace, const unsigned long long* shift_mask, void* stream);
 /* The same match through the row spectra (retrieval, BASELINE config 5: every gallery row against every query). The orientation
  * search is a circular cross-correlation along the 64 columns: with the 64-point DFT of every (channel,row) line of both sides it
  * costs 21k FLOP per pair instead of 524k. witw_match_spectrum: emb [B,64 lines,W] (overhead: W = 64; surface: W = We, zero-

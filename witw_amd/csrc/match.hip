@@ -31,11 +31,24 @@ struct MatchArgs {
     float* distance;         // [Bo,Bs] or null
     float* score;            // [Bo,Bs] or null (max correlation)
     int Bo, Bs, We;
+    const unsigned long long* mask;   // [Bs] or null: bit k of mask[s] set = shift k may be chosen for surface s (0 = no prior)
 };
+
+// ---- shift masks (the MASKED instantiations; the unmasked ones compile to what they were without them). The 64 scores are
+// formed as ever; in the epilogue a lane whose shift the surface's mask forbids enters the arg-max with -inf and its index
+// + 64, so it loses against every allowed lane on value and, should an allowed score ever be -inf itself, on index. A word of 0
+// counts as all ones, so at least one lane is allowed and the winner's index, taken & 63, is a shift the mask allows.
+__device__ __forceinline__ unsigned long long load_shift_mask(const unsigned long long* mask, int srow, int Bs) {
+    const unsigned long long m = (srow < Bs) ? mask[srow] : 0ull;
+    return m ? m : ~0ull;
+}
+__device__ __forceinline__ void mask_shift(unsigned long long m, float& v, int& idx) {
+    if (!((m >> idx) & 1ull)) { v = -__builtin_inff(); idx += 64; }
+}
 
 // OPW = overhead images per wave (1 or 2), MT = 32-surface M-tiles per wave (2, or 1 for batches too small to fill the
 // chip with 128-surface blocks); a block covers 2*OPW overheads x 64*MT surfaces.
-template <int OPW, int MT>
+template <int OPW, int MT, bool MASKED>
 __global__ __launch_bounds__(NT) void match_kernel(MatchArgs p) {
     constexpr int MO = 2 * OPW;
     constexpr int MSB = 64 * MT;         // surfaces per block
@@ -128,7 +141,13 @@ __global__ __launch_bounds__(NT) void match_kernel(MatchArgs p) {
 
     // ---- epilogue: arg-max over the 64 shifts (2 N-tiles x 32 lanes), first index wins ties
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
+    for (int mt = 0; mt < MT; ++mt) {
+        unsigned long long msk[16];      // MASKED: the mask words of the 16 surface rows this lane holds in an accumulator tile
+        if (MASKED) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                msk[r] = load_shift_mask(p.mask, s0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hk, p.Bs);
+        }
 #pragma unroll
         for (int o = 0; o < OPW; ++o) {
             const int og = o0 + OPW * wo + o;
@@ -136,14 +155,17 @@ __global__ __launch_bounds__(NT) void match_kernel(MatchArgs p) {
             for (int r = 0; r < 16; ++r) {
                 float v = acc[mt][o][0][r];
                 int idx = l31;
-                const float v1 = acc[mt][o][1][r];
-                if (v1 > v) { v = v1; idx = 32 + l31; }
+                float v1 = acc[mt][o][1][r];
+                int i1 = 32 + l31;
+                if (MASKED) { mask_shift(msk[r], v, idx); mask_shift(msk[r], v1, i1); }
+                if (v1 > v || (MASKED && v1 == v && i1 < idx)) { v = v1; idx = i1; }
 #pragma unroll
                 for (int d = 1; d < 32; d <<= 1) {
                     const float vo = __shfl_xor(v, d, 64);
                     const int io = __shfl_xor(idx, d, 64);
                     if (vo > v || (vo == v && io < idx)) { v = vo; idx = io; }
                 }
+                if (MASKED) idx &= 63;
                 const int srow = s0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hk;
                 if (l31 == r && og < p.Bo && srow < p.Bs) {
                     const size_t off = (size_t)og * p.Bs + srow;
@@ -153,6 +175,7 @@ __global__ __launch_bounds__(NT) void match_kernel(MatchArgs p) {
                 }
             }
         }
+    }
 }
 
 
@@ -162,7 +185,7 @@ __global__ __launch_bounds__(NT) void match_kernel(MatchArgs p) {
 // wave. The two shift halves of a (surface, overhead) pair meet in the epilogue through LDS: larger score wins, the lower
 // half (smaller shift) on a tie -- the first-index rule of torch.argmax. Every score is the same k-ordered fma chain as in
 // match_kernel (K is not split), so orientation / score / distance carry the same bits.
-template <int WP, int RPC>      // WP: surface columns per row, zero-padded: 16, 32 or 64 (every k-loop fully unrolled); RPC: rows per LDS stage
+template <int WP, int RPC, bool MASKED>      // WP: surface columns per row, zero-padded: 16, 32 or 64 (every k-loop fully unrolled); RPC: rows per LDS stage
 __global__ __launch_bounds__(NT) void match_kernel_nsplit(MatchArgs p) {
     constexpr int MSB = 64;              // surfaces per block
     constexpr int SUC = RPC * 64 + 1;    // LDS stride of a surface's RPC rows (odd: conflict-free ds_read_b32 down the surfaces)
@@ -307,8 +330,10 @@ __global__ __launch_bounds__(NT) void match_kernel_nsplit(MatchArgs p) {
     int bi[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * hk;      // surface row inside this wave's half
         float v = acc[r];
         int idx = 32 * wn + l31;
+        if (MASKED) mask_shift(load_shift_mask(p.mask, s0 + 32 * wm + row, p.Bs), v, idx);
 #pragma unroll
         for (int d = 1; d < 32; d <<= 1) {
             const float vo = __shfl_xor(v, d, 64);
@@ -317,7 +342,6 @@ __global__ __launch_bounds__(NT) void match_kernel_nsplit(MatchArgs p) {
         }
         bv[r] = v;
         bi[r] = idx;
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * hk;      // surface row inside this wave's half
         if (wn == 1 && l31 == r) {
             xv[32 * wm + row] = v;
             xi[32 * wm + row] = idx;
@@ -333,7 +357,8 @@ __global__ __launch_bounds__(NT) void match_kernel_nsplit(MatchArgs p) {
                 float v = bv[r];
                 int idx = bi[r];
                 const float v1 = xv[32 * wm + row];
-                if (v1 > v) { v = v1; idx = xi[32 * wm + row]; }
+                if (v1 > v || (MASKED && v1 == v && xi[32 * wm + row] < idx)) { v = v1; idx = xi[32 * wm + row]; }
+                if (MASKED) idx &= 63;       // a half none of whose shifts is allowed brought -inf and an index + 64
                 const size_t off = (size_t)og * p.Bs + srow;
                 if (p.orientation) p.orientation[off] = idx;
                 if (p.score) p.score[off] = v;
@@ -353,6 +378,7 @@ __global__ __launch_bounds__(NT) void match_kernel_nsplit(MatchArgs p) {
 // operands arrive behind it.
 typedef unsigned int u32x1;
 
+template <bool MASKED>
 __global__ __launch_bounds__(NT, 2) void match_kernel_w64(MatchArgs p) {
     constexpr int OPW = 2, MO = 4, KS = 32;
     constexpr int SU_F = MS * SUS;
@@ -479,7 +505,13 @@ __global__ __launch_bounds__(NT, 2) void match_kernel_w64(MatchArgs p) {
 
     // ---- epilogue: identical to match_kernel
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
+    for (int mt = 0; mt < 2; ++mt) {
+        unsigned long long msk[16];      // MASKED: the mask words of the 16 surface rows this lane holds in an accumulator tile
+        if (MASKED) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                msk[r] = load_shift_mask(p.mask, s0 + 64 * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hk, p.Bs);
+        }
 #pragma unroll
         for (int o = 0; o < OPW; ++o) {
             const int og = o0 + OPW * wo + o;
@@ -487,14 +519,17 @@ __global__ __launch_bounds__(NT, 2) void match_kernel_w64(MatchArgs p) {
             for (int r = 0; r < 16; ++r) {
                 float v = acc[mt][o][0][r];
                 int idx = l31;
-                const float v1 = acc[mt][o][1][r];
-                if (v1 > v) { v = v1; idx = 32 + l31; }
+                float v1 = acc[mt][o][1][r];
+                int i1 = 32 + l31;
+                if (MASKED) { mask_shift(msk[r], v, idx); mask_shift(msk[r], v1, i1); }
+                if (v1 > v || (MASKED && v1 == v && i1 < idx)) { v = v1; idx = i1; }
 #pragma unroll
                 for (int d = 1; d < 32; d <<= 1) {
                     const float vo = __shfl_xor(v, d, 64);
                     const int io = __shfl_xor(idx, d, 64);
                     if (vo > v || (vo == v && io < idx)) { v = vo; idx = io; }
                 }
+                if (MASKED) idx &= 63;
                 const int srow = s0 + 64 * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hk;
                 if (l31 == r && og < p.Bo && srow < p.Bs) {
                     const size_t off = (size_t)og * p.Bs + srow;
@@ -504,6 +539,7 @@ __global__ __launch_bounds__(NT, 2) void match_kernel_w64(MatchArgs p) {
                 }
             }
         }
+    }
 }
 
 // ---- narrower surfaces (We < 63: fov < 355): the same pipelined loop as match_kernel_w64, but one LDS stage holds
@@ -512,7 +548,7 @@ __global__ __launch_bounds__(NT, 2) void match_kernel_w64(MatchArgs p) {
 // stage = rr*WP + k; the B operand of (rr, k) is overhead row rr at column k + shift, overhead rows are stored
 // 64 + WP floats long (the window never wraps). Zero columns add exact zeros: scores are bit-identical to the
 // other kernels.
-template <int R>
+template <int R, bool MASKED>
 __global__ __launch_bounds__(NT, 2) void match_kernel_rows(MatchArgs p) {
     constexpr int OPW = 2, MO = 4, KS = 32, WP = 64 / R, OVS = 64 + WP;
     constexpr int SU_F = MS * SUS;
@@ -646,7 +682,13 @@ __global__ __launch_bounds__(NT, 2) void match_kernel_rows(MatchArgs p) {
 
     // ---- epilogue: identical to match_kernel
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
+    for (int mt = 0; mt < 2; ++mt) {
+        unsigned long long msk[16];      // MASKED: the mask words of the 16 surface rows this lane holds in an accumulator tile
+        if (MASKED) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                msk[r] = load_shift_mask(p.mask, s0 + 64 * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hk, p.Bs);
+        }
 #pragma unroll
         for (int o = 0; o < OPW; ++o) {
             const int og = o0 + OPW * wo + o;
@@ -654,14 +696,17 @@ __global__ __launch_bounds__(NT, 2) void match_kernel_rows(MatchArgs p) {
             for (int r = 0; r < 16; ++r) {
                 float v = acc[mt][o][0][r];
                 int idx = l31;
-                const float v1 = acc[mt][o][1][r];
-                if (v1 > v) { v = v1; idx = 32 + l31; }
+                float v1 = acc[mt][o][1][r];
+                int i1 = 32 + l31;
+                if (MASKED) { mask_shift(msk[r], v, idx); mask_shift(msk[r], v1, i1); }
+                if (v1 > v || (MASKED && v1 == v && i1 < idx)) { v = v1; idx = i1; }
 #pragma unroll
                 for (int d = 1; d < 32; d <<= 1) {
                     const float vo = __shfl_xor(v, d, 64);
                     const int io = __shfl_xor(idx, d, 64);
                     if (vo > v || (vo == v && io < idx)) { v = vo; idx = io; }
                 }
+                if (MASKED) idx &= 63;
                 const int srow = s0 + 64 * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hk;
                 if (l31 == r && og < p.Bo && srow < p.Bs) {
                     const size_t off = (size_t)og * p.Bs + srow;
@@ -671,6 +716,7 @@ __global__ __launch_bounds__(NT, 2) void match_kernel_rows(MatchArgs p) {
                 }
             }
         }
+    }
 }
 
 // wn[o][shift] = sqrt(sum_{ch} sum_{k<We} ov[o][ch][(k+shift)%64]^2): the L2 norm of the window
@@ -1097,12 +1143,10 @@ __global__ __launch_bounds__(256) void rank_band_kernel(const float* __restrict_
 
 static int g_match_pairs_impl = 1;      // witw_match_pairs_impl
 
-extern "C" {
-
-long long witw_match_workspace_floats(int Bo, int Bs) { return (long long)Bo * 64 + Bs; }
-
-int witw_match_fwd(const float* ov, const float* su, int Bo, int Bs, int We, long long* orientation, float* distance,
-                   float* score, float* workspace, void* stream) {
+// MASKED = a shift mask was given: the same choice among the four kernel forms by shape, in their masked instantiations
+template <bool MASKED>
+static int match_fwd_launch(const float* ov, const float* su, int Bo, int Bs, int We, long long* orientation, float* distance,
+                            float* score, float* workspace, const unsigned long long* shift_mask, void* stream) {
     WITW_CHECK_ARG(ov && su && workspace, "match_fwd: null pointer");
     WITW_CHECK_ARG(Bo > 0 && Bs > 0, "match_fwd: empty batch Bo=%d Bs=%d", Bo, Bs);
     WITW_CHECK_ARG(We >= 1 && We <= 64, "match_fwd: surface embedding width %d outside [1,64]", We);
@@ -1115,41 +1159,59 @@ int witw_match_fwd(const float* ov, const float* su, int Bo, int Bs, int We, lon
     a.ov = ov; a.su = su; a.wn = wn; a.sn = sn;
     a.orientation = orientation; a.distance = distance; a.score = score;
     a.Bo = Bo; a.Bs = Bs; a.We = We;
+    a.mask = shift_mask;
     const int gx = cdiv(Bs, MS);
     // small problems: 2 overheads per block (more blocks); large: 4 per block (less staging per FLOP)
     const char* force = getenv("WITW_MATCH_GENERIC");       // A/B aid: 1 = never use the pipelined kernels
     const bool pipelined = (long long)gx * cdiv(Bo, 4) >= 256 && !(force && atoi(force) != 0);
     if (pipelined && We >= 63) {
-        hipLaunchKernelGGL(match_kernel_w64, dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
+        hipLaunchKernelGGL((match_kernel_w64<MASKED>), dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
     } else if (pipelined && We <= 16) {
-        hipLaunchKernelGGL((match_kernel_rows<4>), dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
+        hipLaunchKernelGGL((match_kernel_rows<4, MASKED>), dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
     } else if (pipelined && We <= 32) {
-        hipLaunchKernelGGL((match_kernel_rows<2>), dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
+        hipLaunchKernelGGL((match_kernel_rows<2, MASKED>), dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
     } else if (pipelined) {      // 33..62 columns: one row per stage, zero-padded to 64
-        hipLaunchKernelGGL((match_kernel_rows<1>), dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
+        hipLaunchKernelGGL((match_kernel_rows<1, MASKED>), dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
     } else if ((long long)gx * cdiv(Bo, 4) >= 512) {
-        hipLaunchKernelGGL((match_kernel<2, 2>), dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
+        hipLaunchKernelGGL((match_kernel<2, 2, MASKED>), dim3(gx, cdiv(Bo, 4)), dim3(NT), 0, st, a);
     } else if ((long long)gx * cdiv(Bo, 2) >= 256) {
-        hipLaunchKernelGGL((match_kernel<1, 2>), dim3(gx, cdiv(Bo, 2)), dim3(NT), 0, st, a);
+        hipLaunchKernelGGL((match_kernel<1, 2, MASKED>), dim3(gx, cdiv(Bo, 2)), dim3(NT), 0, st, a);
     } else if ((long long)cdiv(Bs, 64) * cdiv(Bo, 2) >= 96) {      // a single minibatch (128 x 128): one overhead per workgroup, the
         const dim3 g2(cdiv(Bs, 64), Bo);                                       // waves split the shifts: a wave on every SIMD
         constexpr int RPC = NSPLIT_RPC;                                        // embedding rows per LDS stage and barrier
         constexpr size_t lds = 2 * (64 * (RPC * 64 + 1) + RPC * 128) * sizeof(float);
         static bool attr_set = false;
         if (!attr_set && lds > 64 * 1024) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_kernel_nsplit<16, RPC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_kernel_nsplit<32, RPC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_kernel_nsplit<64, RPC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_kernel_nsplit<16, RPC, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_kernel_nsplit<32, RPC, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_kernel_nsplit<64, RPC, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             attr_set = true;
         }
-        if (We <= 16) hipLaunchKernelGGL((match_kernel_nsplit<16, RPC>), g2, dim3(NT), lds, st, a);
-        else if (We <= 32) hipLaunchKernelGGL((match_kernel_nsplit<32, RPC>), g2, dim3(NT), lds, st, a);
-        else hipLaunchKernelGGL((match_kernel_nsplit<64, RPC>), g2, dim3(NT), lds, st, a);
+        if (We <= 16) hipLaunchKernelGGL((match_kernel_nsplit<16, RPC, MASKED>), g2, dim3(NT), lds, st, a);
+        else if (We <= 32) hipLaunchKernelGGL((match_kernel_nsplit<32, RPC, MASKED>), g2, dim3(NT), lds, st, a);
+        else hipLaunchKernelGGL((match_kernel_nsplit<64, RPC, MASKED>), g2, dim3(NT), lds, st, a);
     } else {        // smaller still: 64-surface blocks of two overheads
-        hipLaunchKernelGGL((match_kernel<1, 1>), dim3(cdiv(Bs, 64), cdiv(Bo, 2)), dim3(NT), 0, st, a);
+        hipLaunchKernelGGL((match_kernel<1, 1, MASKED>), dim3(cdiv(Bs, 64), cdiv(Bo, 2)), dim3(NT), 0, st, a);
     }
     WITW_CHECK_LAUNCH("match_fwd");
     return WITW_OK;
+}
+
+extern "C" {
+
+long long witw_match_workspace_floats(int Bo, int Bs) { return (long long)Bo * 64 + Bs; }
+
+int witw_match_fwd(const float* ov, const float* su, int Bo, int Bs, int We, long long* orientation, float* distance,
+                   float* score, float* workspace, void* stream) {
+    return match_fwd_launch<false>(ov, su, Bo, Bs, We, orientation, distance, score, workspace, nullptr, stream);
+}
+
+// witw_match_fwd with the shift search of every surface s restricted to the set bits of shift_mask[s] ([Bs], device; a word of
+// 0 = all 64 shifts; null = witw_match_fwd). An all-ones mask gives the bits of witw_match_fwd in every kernel form.
+int witw_match_fwd_masked(const float* ov, const float* su, int Bo, int Bs, int We, long long* orientation, float* distance,
+                          float* score, float* workspace, const unsigned long long* shift_mask, void* stream) {
+    if (!shift_mask) return match_fwd_launch<false>(ov, su, Bo, Bs, We, orientation, distance, score, workspace, nullptr, stream);
+    return match_fwd_launch<true>(ov, su, Bo, Bs, We, orientation, distance, score, workspace, shift_mask, stream);
 }
 
 // grad_distance [Bo,Bs] -> grad_ov [Bo,16,4,64], grad_su [Bs,16,4,We]. orientation / score / workspace are

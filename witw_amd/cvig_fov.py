@@ -703,9 +703,49 @@ class PolarTransform(object):
 
 
 # ----------------------------------------------------------------------------- matching + loss
-def correlation(overhead_embed, surface_embed):
-    """model/cvig_fov.py:297-315 -> int64 [Bo,Bs]."""
-    return ops.match_fwd(overhead_embed.contiguous(), surface_embed.contiguous())[0]
+def orientation_mask(center_deg, half_width_deg, output_width_max=64):
+    """An orientation prior as the shift masks of the matching functions (`shift_mask=`): int64 [Bs], one 64-bit word per query,
+    bit k set = shift k may be chosen. center_deg / half_width_deg: scalars or [Bs] tensors / arrays, broadcast against each other
+    (two scalars give one word, shape [1]). Degrees are those of the heat-map CSV's `orientation` column (sweep_scores):
+    deg(k) = k * 360 / output_width_max - 180. Shift k is allowed when the circular distance between deg(k) and center_deg is
+    <= half_width_deg; the shift nearest to the centre (the lower one of two equally near) is always allowed, so a word is
+    never 0 (which the kernels read as "no prior"); half_width_deg >= 180 allows every shift. Computed on the host in fp64;
+    the result is a CPU tensor (the matching functions move it to the embeddings' device)."""
+    import numpy as np
+    W = int(output_width_max)
+    if not 1 <= W <= 64:
+        raise _lib.WitwError('orientation_mask: output_width_max must lie in [1, 64], got %r' % (output_width_max,))
+    as_np = lambda v: np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+    c, hw = np.broadcast_arrays(np.atleast_1d(as_np(center_deg)), np.atleast_1d(as_np(half_width_deg)))
+    if c.ndim != 1:
+        raise _lib.WitwError('orientation_mask: center_deg / half_width_deg must be scalars or [Bs], got shape %s' % (c.shape,))
+    if not (np.isfinite(c).all() and (hw >= 0).all()):
+        raise _lib.WitwError('orientation_mask: center_deg must be finite and half_width_deg >= 0')
+    deg = np.arange(W, dtype=np.float64) * 360. / W - 180.
+    dist = np.abs((deg[None, :] - c[:, None] + 180.) % 360. - 180.)          # [Bs, W] circular distance, in [0, 180]
+    allowed = dist <= hw[:, None]
+    allowed[np.arange(len(c)), dist.argmin(axis=1)] = True
+    words = (allowed.astype(np.uint64) << np.arange(W, dtype=np.uint64)[None, :]).sum(axis=1, dtype=np.uint64)
+    return torch.from_numpy(words.view(np.int64).copy())
+
+
+def _query_mask(shift_mask, surface_embed):
+    """`shift_mask` of a matching function as ops.match_fwd wants it: int64 [Bs], contiguous, on the queries' device."""
+    if shift_mask is None:
+        return None
+    if not (isinstance(shift_mask, torch.Tensor) and shift_mask.dtype == torch.int64 and shift_mask.dim() == 1
+            and shift_mask.shape[0] == surface_embed.shape[0]):
+        raise _lib.WitwError('shift_mask must be an int64 tensor with one word per query ([%d]), got %s' % (
+            surface_embed.shape[0], (tuple(shift_mask.shape), shift_mask.dtype) if isinstance(shift_mask, torch.Tensor)
+            else type(shift_mask)))
+    return shift_mask.to(surface_embed.device).contiguous()
+
+
+def correlation(overhead_embed, surface_embed, shift_mask=None):
+    """model/cvig_fov.py:297-315 -> int64 [Bo,Bs]. shift_mask (int64 [Bs], see orientation_mask): the arg-max runs over the
+    shifts the query's word allows."""
+    return ops.match_fwd(overhead_embed.contiguous(), surface_embed.contiguous(),
+                         shift_mask=_query_mask(shift_mask, surface_embed))[0]
 
 
 def crop_overhead(overhead_embed, orientation, surface_width):
@@ -720,9 +760,9 @@ def l2_distance(overhead_cropped, surface_embed):
 
 class _MatchFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, overhead_embed, surface_embed):
+    def forward(ctx, overhead_embed, surface_embed, shift_mask=None):
         ov, su = overhead_embed.contiguous(), surface_embed.contiguous()
-        ori, dist, score, ws = ops.match_fwd(ov, su, want_score=True, want_workspace=True)
+        ori, dist, score, ws = ops.match_fwd(ov, su, want_score=True, want_workspace=True, shift_mask=shift_mask)
         ctx.save_for_backward(ov, su, ori, score, ws)
         ctx.mark_non_differentiable(ori)
         return ori, dist
@@ -732,15 +772,18 @@ class _MatchFn(torch.autograd.Function):
         ov, su, ori, score, ws = ctx.saved_tensors
         gov, gsu = ops.match_bwd(ov, su, ori, score, ws, g_dist.contiguous(), ctx.needs_input_grad[0],
                                  ctx.needs_input_grad[1])
-        return gov, gsu
+        return gov, gsu, None
 
 
-def match(overhead_embed, surface_embed):
+def match(overhead_embed, surface_embed, shift_mask=None):
     """correlation -> crop_overhead -> l2_distance fused (no crop tensor): (orientation, distance).
-    Differentiable w.r.t. both embeddings (the arg-max orientation is a constant, as in the reference)."""
+    Differentiable w.r.t. both embeddings (the arg-max orientation is a constant, as in the reference).
+    shift_mask (int64 [Bs], see orientation_mask): the orientation is the first maximum over the shifts the query's word allows,
+    the distance is taken there; the backward consumes that orientation as it does the unrestricted one."""
+    shift_mask = _query_mask(shift_mask, surface_embed)
     if torch.is_grad_enabled() and (overhead_embed.requires_grad or surface_embed.requires_grad):
-        return _MatchFn.apply(overhead_embed, surface_embed)
-    return ops.match_fwd(overhead_embed.contiguous(), surface_embed.contiguous())
+        return _MatchFn.apply(overhead_embed, surface_embed, shift_mask)
+    return ops.match_fwd(overhead_embed.contiguous(), surface_embed.contiguous(), shift_mask=shift_mask)
 
 
 class Adam(object):
@@ -831,45 +874,54 @@ def batch_hard_triplet_loss(distances, alpha=10.):
     return _BatchHardTripletLoss.apply(distances, float(alpha))
 
 
-def ranks(overhead_embed, surface_embed):
+def ranks(overhead_embed, surface_embed, shift_mask=None):
     """Ranking loop of test() (model/cvig_fov.py:543-552) for all queries at once: int64 [N] on
-    the host, rank = #{gallery : d <= d_true} with gallery index == query index."""
-    _, dist = match(overhead_embed, surface_embed)
+    the host, rank = #{gallery : d <= d_true} with gallery index == query index. shift_mask: see match()."""
+    _, dist = match(overhead_embed, surface_embed, shift_mask)
     return ops.rank_count(dist, 0).cpu().numpy().astype('int64')
 
 
 SPECTRAL_FROM = 8192      # evaluation sets from this many pairs on rank through the spectral pass under match_method 'auto'
 
 
-def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, method='auto'):
+def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, method='auto', shift_mask=None):
     """The ranks test() tabulates (model/cvig_fov.py:543-552), int64 [N] on the host, identical on every rank. `overhead_embed` /
     `surface_embed` are THIS rank's rows (world > 1: queries are replicated, gallery rows stay sharded). method:
     'direct' = the fused correlation kernel on every (gallery, query) pair (2*64*E FLOP each); 'dft' = the spectral pass
     (21 k FLOP per pair) with the exact re-scoring of retrieve(): the SAME ranks (index-exact, tests/test_match_dft_gpu.py) about
     17x faster at retrieval sizes; 'auto' = 'dft' from SPECTRAL_FROM pairs on. 8,884 CVUSA test pairs: 0.55 s direct, 10^5 pairs:
-    36 s direct / 2 s spectral."""
+    36 s direct / 2 s spectral.
+    shift_mask: int64, one word per query of the WHOLE evaluation set (all ranks' rows, in order), see orientation_mask. The
+    spectral pass has no masked form: 'auto' then means 'direct', an explicit 'dft' is an error."""
     from . import parallel
     if method not in ('auto', 'direct', 'dft'):
         raise _lib.WitwError("match_method must be 'auto', 'direct' or 'dft', got %r" % (method,))
+    if shift_mask is not None:
+        if method == 'dft':
+            raise _lib.WitwError("evaluation_ranks: shift_mask is not supported by the spectral pass (method='dft'); use "
+                                 "'direct' or 'auto'")
+        method = 'direct'
     surface_all = parallel.all_gather_ragged(surface_embed) if world > 1 else surface_embed
     if method == 'auto':
         method = 'dft' if surface_all.shape[0] >= SPECTRAL_FROM else 'direct'
     if method == 'dft':
         return retrieve(overhead_embed, surface_all, k=1, shard_begin=shard_begin, method='dft')[0]
     if world > 1:
-        return sharded_ranks(overhead_embed, surface_all, shard_begin)
-    return ranks(overhead_embed, surface_embed)
+        return sharded_ranks(overhead_embed, surface_all, shard_begin, shift_mask=shift_mask)
+    return ranks(overhead_embed, surface_embed, shift_mask)
 
 
-def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _match=None, _count=None):
+def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _match=None, _count=None, shift_mask=None):
     """Ranking with the GALLERY sharded by rows across ranks: this rank holds
     overhead_shard = gallery rows [shard_begin, shard_begin+n); queries (replicated) match gallery row
     == query index. The owner of each true row publishes its distance (all-reduce of a vector that is
     zero elsewhere), every rank counts d <= d_true over its shard, counts are summed. Returns int64 [N]
-    on the host, identical on every rank and identical to ranks() on one GPU."""
+    on the host, identical on every rank and identical to ranks() on one GPU. shift_mask (int64 [N], one word per query, see
+    orientation_mask): every query chunk is matched under its own slice of it."""
     from . import parallel
     _match = _match or ops.match_fwd                 # injectable so the collective algebra is testable on CPU/gloo
     _count = _count or ops.rank_count_thresh
+    shift_mask = _query_mask(shift_mask, surface_all)
     n_q = surface_all.shape[0]
     n_g = overhead_shard.shape[0]
     out = torch.zeros((n_q,), dtype=torch.int32, device=surface_all.device)
@@ -878,7 +930,8 @@ def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _m
         if n_g == 0:         # a rank without gallery rows still takes part in the exchanges
             parallel.all_reduce_sum_(torch.zeros((q1 - q0,), dtype=torch.float32, device=surface_all.device))
             continue
-        _, dist = _match(overhead_shard.contiguous(), surface_all[q0:q1].contiguous())   # [n_g, q]
+        masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
+        _, dist = _match(overhead_shard.contiguous(), surface_all[q0:q1].contiguous(), **masked)   # [n_g, q]
         qi = torch.arange(q0, q1, device=dist.device)
         own = (qi >= shard_begin) & (qi < shard_begin + n_g)
         row = (qi - shard_begin).clamp(0, n_g - 1)
@@ -889,12 +942,14 @@ def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _m
     return out.cpu().numpy().astype('int64')
 
 
-def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='direct', _kernels=None):
+def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='direct', _kernels=None,
+                  shift_mask=None):
     """Top-k retrieval (BASELINE config C5): for every query the k nearest gallery rows by the fused
     orientation-search chord distance, ordered by (distance, gallery index). With the gallery sharded over
     ranks each rank ranks its shard, the [N,k] candidate lists are all-gathered and merged by the same kernel.
-    -> (distances f32 [N,k], gallery indices int64 [N,k]) on the device, identical on every rank."""
-    return retrieve(overhead_shard, surface_all, k, shard_begin, query_chunk, method, _kernels, _want_ranks=False)[1:]
+    -> (distances f32 [N,k], gallery indices int64 [N,k]) on the device, identical on every rank. shift_mask: see retrieve()."""
+    return retrieve(overhead_shard, surface_all, k, shard_begin, query_chunk, method, _kernels, _want_ranks=False,
+                    shift_mask=shift_mask)[1:]
 
 
 def _merge_topk(v, i, k, _kernels=None):
@@ -918,7 +973,7 @@ def _merge_topk(v, i, k, _kernels=None):
 
 
 def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='direct', _kernels=None,
-             _want_ranks=True):
+             _want_ranks=True, shift_mask=None):
     """sharded_ranks + retrieve_topk from ONE matching pass per query chunk (config C5: the pass is
     2*64*E FLOP per (gallery row, query) and dominates). -> (ranks int64 [N] on the host, distances f32 [N,k],
     gallery indices int64 [N,k] on the device), identical on every rank. The gallery may be sharded raggedly (any
@@ -926,9 +981,17 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     method='dft': the pass runs through the row spectra (21k instead of 524k FLOP per pair) and every decision that the
     spectral distances leave within fp32 rounding -- a row within DISTANCE_EPS of a query's true-match distance, neighbours
     in a top-k list closer than 2 DISTANCE_EPS -- is re-made on distances from ops.match_pairs, which are bit-identical to the
-    direct kernel's: ranks and top-k INDICES equal method='direct' exactly (the listed distances agree to DISTANCE_EPS)."""
+    direct kernel's: ranks and top-k INDICES equal method='direct' exactly (the listed distances agree to DISTANCE_EPS).
+    shift_mask (int64 [N], one word per query, see orientation_mask): every query chunk is matched under its own slice of it;
+    method 'direct' (or 'auto', which a mask resolves to 'direct') only -- the spectral pass has no masked form."""
     from . import parallel
     kn = _kernels or ops
+    if shift_mask is not None:
+        if method == 'dft':
+            raise _lib.WitwError("retrieve: shift_mask is not supported by the spectral pass (method='dft'); use 'direct'")
+        if method == 'auto':
+            method = 'direct'
+        shift_mask = _query_mask(shift_mask, surface_all)
     if method == 'dft' and k + DFT_MARGIN > 32:      # no room for the candidate margin in a 32-wide list: the top-k comes from the
         ranks_dft = None                              # direct pass, the rank counts (no list involved) still from the spectral one
         if _want_ranks:
@@ -949,7 +1012,8 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
         if n_g == 0:        # a rank without gallery rows (more ranks than rows): nothing to match, empty candidate lists
             dist = torch.empty((0, nq), dtype=torch.float32, device=surface_all.device)
         else:
-            _, dist = kn.match_fwd(gallery, surface_all[q0:q1].contiguous())            # [n_g, q]
+            masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
+            _, dist = kn.match_fwd(gallery, surface_all[q0:q1].contiguous(), **masked)            # [n_g, q]
         if _want_ranks:
             qi = torch.arange(q0, q1, device=dist.device)
             own = (qi >= shard_begin) & (qi < shard_begin + n_g)
@@ -2032,9 +2096,12 @@ def train(dataset='cvusa', fov=360, val_quantity=1000, batch_size=64, num_worker
     return best_loss
 
 
-def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, _mod=None):
+def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, _mod=None, orientation_window=None):
     """model/cvig_fov.py:490-575: embed the test set, rank every query against the whole gallery (all
-    queries at once on the GPU instead of the O(N) Python loop), print the recall table."""
+    queries at once on the GPU instead of the O(N) Python loop), print the recall table.
+    orientation_window (not in the reference): (center_deg, half_width_deg) of orientation_mask, applied to every query --
+    the "orientation known" protocol, e.g. north-aligned panoramas cropped with Globals.test_random_orientation = False.
+    None: the unrestricted search over all 64 shifts."""
     import sys
     from datetime import datetime
     m = _mod or sys.modules[__name__]
@@ -2084,7 +2151,11 @@ def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, 
     if Globals.precision == 'fp16x3' and ops.f16x3_overflowed(surface_embed.device):
         raise _lib.WitwError("an activation left the fp16 range (|v| > 65504) on the fp16x3 kernels: evaluate these weights with "
                              "precision 'fp32'")
-    rk = evaluation_ranks(overhead_embed, surface_embed, shard_begin, world, getattr(Globals, 'match_method', 'auto'))
+    shift_mask = None
+    if orientation_window is not None:
+        shift_mask = orientation_mask(orientation_window[0], orientation_window[1]).expand(len(test_set)).contiguous()
+    rk = evaluation_ranks(overhead_embed, surface_embed, shard_begin, world, getattr(Globals, 'match_method', 'auto'),
+                          shift_mask=shift_mask)
     t = recall_table(rk)
     count = len(rk)
     if rank != 0:
@@ -2098,13 +2169,26 @@ def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, 
     return t
 
 
-def sweep_scores(overhead_embed, surface_embed, output_width_max=64):
+def sweep_scores(overhead_embed, surface_embed, output_width_max=64, shift_mask=None):
     """The scoring block of tools/heatmap/heatmap.py:172-178 (one photo against N satellite tiles):
-    -> (orientation in degrees, dissimilarity, score = exp(10*(1-d))), each [N] (or [N,Bs])."""
-    ori, dist = match(overhead_embed, surface_embed)
+    -> (orientation in degrees, dissimilarity, score = exp(10*(1-d))), each [N] (or [N,Bs]). shift_mask: see match(); the
+    degrees returned here are the ones orientation_mask takes."""
+    ori, dist = match(overhead_embed, surface_embed, shift_mask)
     orientations = torch.squeeze(ori) * 360 / output_width_max - 180
     distances = torch.squeeze(dist)
     return orientations, distances, torch.exp(10. * (1. - distances))
+
+
+def parse_orientation_window(text):
+    """'CENTER,HALFWIDTH' (degrees) of the --orientation-window option -> (center_deg, half_width_deg)."""
+    import argparse
+    try:
+        center, half = (float(v) for v in text.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected CENTER,HALFWIDTH in degrees, got %r' % (text,))
+    if half < 0:
+        raise argparse.ArgumentTypeError('HALFWIDTH must be >= 0, got %r' % (half,))
+    return center, half
 
 
 def main(argv=None):
@@ -2125,6 +2209,10 @@ def main(argv=None):
                         help='train mode (not in the reference): soft_margin = the reference\'s all-pairs soft-margin triplet loss, '
                              'batch_hard = the soft-margin loss on each anchor\'s hardest negative in the global batch. '
                              '[Default = soft_margin]')
+    parser.add_argument('--orientation-window', default=None, type=parse_orientation_window, metavar='CENTER,HALFWIDTH',
+                        help='test mode (not in the reference): restrict every query\'s orientation search to the shifts within '
+                             'HALFWIDTH degrees of CENTER (degrees of the heat-map CSV: shift k = k*360/64 - 180). '
+                             '[Default = all 64 shifts]')
     args = parser.parse_args(argv)
     print(args)
     Globals.precision = args.precision
@@ -2134,7 +2222,7 @@ def main(argv=None):
     if args.mode == 'train':
         train(dataset=args.dataset, fov=args.fov)
     elif args.mode == 'test':
-        test(dataset=args.dataset, fov=args.fov)
+        test(dataset=args.dataset, fov=args.fov, orientation_window=args.orientation_window)
 
 
 def init_distributed(backend='nccl'):

@@ -101,10 +101,11 @@ def train(dataset='cvusa', fov=360, val_quantity=1000, batch_size=32, num_worker
     return _fov.train(dataset, fov, val_quantity, batch_size, num_workers, num_epochs, csv_path, seed, _mod=sys.modules[__name__])
 
 
-def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None):
-    """model/cvig_semantic.py:521-606."""
+def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, orientation_window=None):
+    """model/cvig_semantic.py:521-606. orientation_window: see cvig_fov.test."""
     import sys
-    return _fov.test(dataset, fov, batch_size, num_workers, csv_path, _mod=sys.modules[__name__])
+    return _fov.test(dataset, fov, batch_size, num_workers, csv_path, _mod=sys.modules[__name__],
+                     orientation_window=orientation_window)
 
 
 def main(argv=None):
@@ -124,6 +125,9 @@ def main(argv=None):
                         help='train mode (not in the reference): soft_margin = the reference\'s all-pairs soft-margin triplet loss, '
                              'batch_hard = the soft-margin loss on each anchor\'s hardest negative in the global batch. '
                              '[Default = soft_margin]')
+    parser.add_argument('--orientation-window', default=None, type=_fov.parse_orientation_window, metavar='CENTER,HALFWIDTH',
+                        help='test mode (not in the reference): restrict every query\'s orientation search to the shifts within '
+                             'HALFWIDTH degrees of CENTER, see cvig_fov. [Default = all 64 shifts]')
     args = parser.parse_args(argv)
     print(args)
     Globals.precision = args.precision
@@ -133,7 +137,7 @@ def main(argv=None):
     if args.mode == 'train':
         train(dataset=args.dataset, fov=args.fov)
     elif args.mode == 'test':
-        test(dataset=args.dataset, fov=args.fov)
+        test(dataset=args.dataset, fov=args.fov, orientation_window=args.orientation_window)
 
 
 if __name__ == '__main__':

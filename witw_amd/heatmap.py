@@ -190,11 +190,39 @@ def embed_tiles(overhead_encoder, source, windows, batch_size=64):
     return torch.cat(parts, dim=0)
 
 
+DEFAULT_HEADING_TOLERANCE = 15.      # degrees either side of `heading` when only the heading is given: a phone compass
+                                     # (the source of EXIF GPSImgDirection) is usually good to 5-15 degrees
+
+
+def heading_window(heading, fov, heading_tolerance=None):
+    """Compass bearing of the photo's optical axis -> (center_deg, half_width_deg) of cvig_fov.orientation_mask.
+
+    For a north-up tile, polar column x of 512 looks along bearing 180 + 360 * x / 512 degrees (a blob due south / west / north /
+    east of the tile centre lands in column 0 / 128 / 256 / 384 of the polar image, give or take two columns with the blob's
+    place inside its pixel). The shift the match chooses is the polar
+    column, in units of 512 / 64, where the photo's LEFT edge lies, so the CSV's `orientation` = shift * 360 / 64 - 180 is the
+    bearing of the left edge wrapped to [-180, 180). The optical axis is fov / 2 to the right of the left edge, hence
+        center_deg     = heading - fov / 2   (wrapped to [-180, 180))
+        half_width_deg = heading_tolerance   (DEFAULT_HEADING_TOLERANCE when None)."""
+    if heading is None:
+        if heading_tolerance is not None:
+            raise ValueError('heading_tolerance needs a heading')
+        return None
+    tol = DEFAULT_HEADING_TOLERANCE if heading_tolerance is None else float(heading_tolerance)
+    if tol < 0:
+        raise ValueError('heading_tolerance must be >= 0 degrees, got %r' % (heading_tolerance,))
+    return (float(heading) - fov / 2. + 180.) % 360. - 180., tol
+
+
 def sweep(aoi, bounds, edge, offset, fov, sat_dir, photo_path, csv_path, tile_source=None, surface_encoder=None,
-          overhead_encoder=None, weights_dir='../../model', photo=None, batch_size=64):
+          overhead_encoder=None, weights_dir='../../model', photo=None, batch_size=64, heading=None, heading_tolerance=None):
     """tools/heatmap/heatmap.py:113-187. Extra keyword arguments inject the raster source, already-loaded encoders
-    or an in-memory photo (tests, services); by default everything is read from the reference's paths."""
+    or an in-memory photo (tests, services); by default everything is read from the reference's paths.
+    heading (not in the reference): compass bearing of the photo's optical axis in degrees (EXIF GPSImgDirection); every tile's
+    orientation search is then restricted to the shifts within heading_tolerance degrees (default DEFAULT_HEADING_TOLERANCE)
+    of it -- see heading_window for the geometry. heading_tolerance without heading is an error."""
     import pandas as pd
+    window = heading_window(heading, fov, heading_tolerance)
     center_eastings, center_northings, windows = tile_windows(bounds, edge, offset)
     if tile_source is None:
         tile_source = GdalTileSource(os.path.join(sat_dir, names[aoi - 1] + '.tif'))
@@ -212,7 +240,8 @@ def sweep(aoi, bounds, edge, offset, fov, sat_dir, photo_path, csv_path, tile_so
         photo = cvig.ImagePairDataset._read(photo_path)
     surface_embed = embed_photo(surface_encoder, photo, fov)
     overhead_embed = embed_tiles(overhead_encoder, tile_source, windows, batch_size)
-    orientations, distances, scores = cvig.sweep_scores(overhead_embed, surface_embed)
+    shift_mask = None if window is None else cvig.orientation_mask(window[0], window[1])     # one photo: one word
+    orientations, distances, scores = cvig.sweep_scores(overhead_embed, surface_embed, shift_mask=shift_mask)
     df = pd.DataFrame({'x': center_eastings, 'y': center_northings, 'orientation': orientations.cpu().numpy().reshape(-1),
                        'dissimilarity': distances.cpu().numpy().reshape(-1), 'score': scores.cpu().numpy().reshape(-1)})
     df.to_csv(csv_path, index=False)
@@ -232,8 +261,16 @@ def main(argv=None):
     parser.add_argument('-s', '--satdir', default='/local_data/geoloc/sat/utm', help='Folder containing satellite images')
     parser.add_argument('-p', '--photopath', default='img.jpg', help='Path to surface photo to analyze')
     parser.add_argument('-c', '--csvpath', default='./geomatch.csv', help='Path to output CSV file path')
+    parser.add_argument('--heading', type=float, default=None,
+                        help='Compass bearing of the photo\'s optical axis (deg, e.g. EXIF GPSImgDirection): restricts the '
+                             'orientation search [Default = search all orientations]')
+    parser.add_argument('--heading-tolerance', type=float, default=None,
+                        help='Half width of the orientation window around --heading (deg) [Default = %g]' % DEFAULT_HEADING_TOLERANCE)
     args = parser.parse_args(argv)
-    sweep(args.aoi, args.bounds, args.edge, args.offset, args.fov, args.satdir, args.photopath, args.csvpath)
+    if args.heading_tolerance is not None and args.heading is None:
+        parser.error('--heading-tolerance needs --heading')
+    sweep(args.aoi, args.bounds, args.edge, args.offset, args.fov, args.satdir, args.photopath, args.csvpath,
+          heading=args.heading, heading_tolerance=args.heading_tolerance)
 
 
 if __name__ == '__main__':

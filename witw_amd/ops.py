@@ -503,10 +503,13 @@ def match_bwd(overhead_embed, surface_embed, orientation, score, workspace, grad
     return gov, gsu
 
 
-def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=False):
+def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=False, shift_mask=None):
     """Fused correlation -> argmax -> window norm -> chord distance (no crop tensor).
     overhead_embed [Bo,16,4,64], surface_embed [Bs,16,4,We] -> (orientation int64 [Bo,Bs],
-    distance f32 [Bo,Bs][, max score f32 [Bo,Bs]])."""
+    distance f32 [Bo,Bs][, max score f32 [Bo,Bs]]).
+    shift_mask: None, or an int64 [Bs] device tensor, one 64-bit word per surface embedding: bit k set = shift k may be
+    chosen (bit 63 makes the word negative; that is fine), 0 = no prior for that query. The arg-max is then the first maximum
+    over the allowed shifts (witw_match_fwd_masked); cvig_fov.orientation_mask builds the words from degrees."""
     lib = _lib.load()
     ov = _dev_f32(overhead_embed, 'overhead_embed')
     su = _dev_f32(surface_embed, 'surface_embed')
@@ -515,6 +518,12 @@ def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=Fa
     if su.shape[1] != ov.shape[1] or su.shape[2] != ov.shape[2]:
         raise _lib.WitwError('match_fwd: surface embedding %s does not match overhead %s' % (tuple(su.shape), tuple(ov.shape)))
     Bo, Bs, We = ov.shape[0], su.shape[0], su.shape[3]
+    if shift_mask is not None:
+        if not (isinstance(shift_mask, torch.Tensor) and shift_mask.dtype == torch.int64 and shift_mask.device == ov.device
+                and tuple(shift_mask.shape) == (Bs,) and shift_mask.is_contiguous()):
+            raise _lib.WitwError('match_fwd: shift_mask must be a contiguous int64 [%d] tensor on %s, got %s'
+                                 % (Bs, ov.device, (tuple(shift_mask.shape), shift_mask.dtype, shift_mask.device)
+                                    if isinstance(shift_mask, torch.Tensor) else type(shift_mask)))
     ori = torch.empty((Bo, Bs), dtype=torch.int64, device=ov.device)
     dist = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device)
     score = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device) if want_score else None
@@ -523,8 +532,12 @@ def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=Fa
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    _lib.check(lib.witw_match_fwd(ov.data_ptr(), su.data_ptr(), Bo, Bs, We, ori.data_ptr(), dist.data_ptr(), _p(score),
-                                  ws.data_ptr(), _stream()), 'witw_match_fwd')
+    if shift_mask is None:
+        _lib.check(lib.witw_match_fwd(ov.data_ptr(), su.data_ptr(), Bo, Bs, We, ori.data_ptr(), dist.data_ptr(), _p(score),
+                                      ws.data_ptr(), _stream()), 'witw_match_fwd')
+    else:
+        _lib.check(lib.witw_match_fwd_masked(ov.data_ptr(), su.data_ptr(), Bo, Bs, We, ori.data_ptr(), dist.data_ptr(), _p(score),
+                                             ws.data_ptr(), shift_mask.data_ptr(), _stream()), 'witw_match_fwd_masked')
     if prof is not None:      # the launch = two small norm kernels + the match kernel
         e1.record()
         prof.append((('match', We), 2.0 * 64 * (64 * We) * Bo * Bs, e0, e1))
