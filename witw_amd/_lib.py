@@ -200,7 +200,7 @@ def load():
 
 def guards():
     """The register-allocation guards of build.py as this process sees them: name -> {'hand_scheduled_kernel': in use?, 'forced',
-    'detail'}. 's16' / 'wres' act inside the library (switches set by load()); 'first2' is read by FOV_DSM.forward_bf16."""
+    'detail'}. 's16' / 'wres' act inside the library (switches set by load()); 'first2' is read by FOV_DSM._run (bf16)."""
     load()
     return _GUARDS
 

@@ -99,6 +99,43 @@ def _conv_of(m):
     return m
 
 
+class _Precision(object):
+    """What the arithmetic paths of FOV_DSM differ in; everything else is one layer walk (FOV_DSM._run, _EncoderFn).
+    A feature that one path has and another lacks is a field here, not a second copy of the loop."""
+
+    def __init__(self, slot, cpad, image_in, to_layout, packed, conv_fwd, nchw_kw, wgrad, slice_wgrad, pool_bwd, first_cin,
+                 first_bf16, first_kw, wino=False, direct=None, overrides=False):
+        self.slot = slot                    # prefix of this path's slots in FOV_DSM._packed
+        self.cpad = cpad                    # channel padding of an activation / gradient in this path's layout
+        self.image_in = image_in            # NCHW fp32 image -> the layout, at the first layer's padding
+        self.to_layout = to_layout          # (NCHW fp32, padded channels) -> the layout (the embedding's gradient)
+        self.packed = packed                # packed-filter class
+        self.conv_fwd = conv_fwd            # conv forward op (the data gradient is the same op on the transposed filter), by name:
+                                            # looked up in ops at every call, as a direct ops.<name>(...) would be
+        self.nchw_kw = nchw_kw              # its keyword for "write the fp32 NCHW embedding"
+        self.wgrad = wgrad                  # weight-gradient op ...
+        self.slice_wgrad = slice_wgrad      # ... whose results carry padded output channels: cut to out_channels
+        self.pool_bwd = pool_bwd            # max-pool arg-max scatter
+        self.first_cin = first_cin          # the first-layer kernel takes an image of up to this many channels ...
+        self.first_bf16 = first_bf16        # ... with the filter FOV_DSM._pack_first(first_bf16) ...
+        self.first_kw = first_kw            # ... and these flags
+        self.wino = wino                    # inference launches of stride-1 layers may run the Winograd form
+        self.direct = direct                # None: never write into a parallel.GradBucket; else encoder -> may this one?
+        self.overrides = overrides          # the backward honours FOV_DSM._bwd_override and records _last_kept
+
+
+_FP32 = _Precision('f32', 8, ops.nchw_to_nhwc8, ops.nchw_to_nhwc, ops.PackedConv, 'conv3x3_fwd', 'out_nchw', ops.conv3x3_wgrad,
+                   False, ops.maxpool2x2_bwd, 4, False, {}, wino=True, direct=lambda enc: True, overrides=True)
+# direct writes: only when no layer's gradient tensor carries padded output channels (bf16 activations come in multiples of 16)
+_BF16 = _Precision('bf16', 16, lambda x: ops.nchw_to_nhwc_bf16(x, 16), ops.nchw_to_nhwc_bf16, ops.PackedConvBf16,
+                   'conv3x3_bf16_fwd', 'out_nchw_f32', ops.conv3x3_wgrad_bf16, True, ops.maxpool2x2_bwd_bf16, 8, True, {},
+                   direct=lambda enc: all(c.out_channels % 16 == 0 for _i, c in enc.trainable_convs()))
+_F16X3 = _Precision('f16x3', 8, lambda x: ops.nchw_to_split_f16(x, 8), ops.nchw_to_split_f16, ops.PackedConvF16x3,
+                    'conv3x3_f16x3_fwd', 'out_nchw_f32', ops.conv3x3_wgrad_f16x3, True, ops.maxpool2x2_bwd_split, 4, False,
+                    {'split_f16': True})
+_PRECISIONS = {'fp32': _FP32, 'bf16': _BF16, 'fp16x3': _F16X3}
+
+
 class FOV_DSM(torch.nn.Module):
     """VGG16 features[:23] + 3 extra convs (model/cvig_fov.py:248-294), forward on HIP kernels.
 
@@ -156,28 +193,38 @@ class FOV_DSM(torch.nn.Module):
         self.dropout_stream = 1 if circ_padding else 0
         self._drop_step = 0
 
-    def _pack(self, idx, wino=False):
-        """packed filter of layer idx; wino=True: with the Winograd F(2,3)-along-H filter too (inference launches only: the
-        training forward keeps the direct form whose activations the backward reconciles with)"""
+    @staticmethod
+    def _pack_key(conv, bias=True):
+        """what a packed image of `conv` was made from: the parameter versions (torch's, and the one cvig_fov.Adam bumps)"""
+        key = (conv.weight.data_ptr(), conv.weight._version, getattr(conv.weight, '_witw_version', 0))
+        return key + (conv.bias._version, getattr(conv.bias, '_witw_version', 0)) if bias else key
+
+    def _packed_image(self, slot, idx, make, bias=True):
+        """The pack cache: the image in `slot`, re-made by make(conv, reuse) -- reuse = the stale image, whose buffers may be
+        overwritten, or None -- when layer idx's weight (bias=True: or bias) has changed since it was packed."""
         conv = _conv_of(self.model.features[idx])
-        key = (conv.weight.data_ptr(), conv.weight._version, conv.bias._version, getattr(conv.weight, '_witw_version', 0),
-               getattr(conv.bias, '_witw_version', 0))
-        slot = ('w', idx) if wino else idx
+        key = self._pack_key(conv, bias)
         hit = self._packed.get(slot)
         if hit is None or hit[0] != key:
-            hit = (key, ops.PackedConv(conv.weight, conv.bias, reuse=hit[1] if hit else None, wino=wino))
+            hit = (key, make(conv, hit[1] if hit else None))
             self._packed[slot] = hit
         return hit[1]
 
-    def _pack_t(self, idx):
+    def _pack(self, idx, precision=_FP32, wino=False):
+        """packed filter of layer idx; wino=True: with the Winograd F(2,3)-along-H filter too (inference launches only: the
+        training forward keeps the direct form whose activations the backward reconciles with)"""
+        if wino:
+            return self._packed_image((precision.slot + '_w', idx), idx,
+                                      lambda conv, reuse: precision.packed(conv.weight, conv.bias, reuse=reuse, wino=True))
+        return self._packed_image((precision.slot, idx), idx, lambda conv, reuse: precision.packed(conv.weight, conv.bias, reuse=reuse))
+
+    def _pack_t(self, idx, precision=_FP32):
         """dgrad filter (transpose + 180-degree tap rotation) of layer idx."""
-        conv = _conv_of(self.model.features[idx])
-        key = (conv.weight.data_ptr(), conv.weight._version, getattr(conv.weight, '_witw_version', 0))
-        hit = self._packed.get(('t', idx))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.PackedConv(conv.weight, None, transpose_flip=True, reuse=hit[1] if hit else None))
-            self._packed[('t', idx)] = hit
-        return hit[1]
+        return self._packed_image((precision.slot + '_t', idx), idx, bias=False,
+                                  make=lambda conv, reuse: precision.packed(conv.weight, None, transpose_flip=True, reuse=reuse))
+
+    def _pack_first(self, bf16):
+        return self._packed_image(('first', bf16), 0, lambda conv, _reuse: ops.PackedFirstConv(conv.weight, conv.bias, bf16=bf16))
 
     def _draw_scales(self, x, dropout_scales):
         """Dropout2d(p=0.2) scales of this call (whole channels, 1/(1-p) on the kept ones; reference :241,288): injected, or
@@ -201,131 +248,84 @@ class FOV_DSM(torch.nn.Module):
         self._drop_step += 1
         return {idx: sc[i] for i, idx in enumerate(layers)}
 
-    def _run(self, x, scales, keep_from=None):
-        """Layer stack. Returns (embedding NCHW, kept) where kept[idx] = (layer input NHWC, layer output NHWC,
-        max-pool arg-max codes or None) for every layer idx >= keep_from (what the backward needs)."""
-        fast0 = self.in_channels <= 4 and (keep_from is None or keep_from > 0)
-        h = x.contiguous() if fast0 else ops.nchw_to_nhwc8(x.contiguous())
-        last = self.layer_specs[-1][0]
-        kept = {}
-        for (idx, sh, relu, pool, drop) in self.layer_specs:
-            if idx == 0 and fast0:     # C<=4 -> 64 straight from NCHW (layer 0 is frozen: nothing to keep)
-                h = ops.conv3x3_first_fwd(h, self._pack_first(False), circular=self.circ_padding, relu=relu)
-                continue
-            keep = keep_from is not None and idx >= keep_from
-            # no backward consumes an inference pass: its stride-1 layers may run the Winograd form
-            pk = self._pack(idx, wino=keep_from is None and sh == 1)
-            out = ops.conv3x3_fwd(h, pk, stride_h=sh, circular=self.circ_padding, relu=relu, pool=pool,
-                                  out_nchw=(idx == last), drop_scale=scales.get(idx), want_pool_code=(keep and pool))
-            y, code = out if (keep and pool) else (out, None)
-            if keep:
-                kept[idx] = (h, y, code)
-            h = y
-        return h, kept
-
-    def _pack_first(self, bf16):
-        conv = _conv_of(self.model.features[0])
-        key = (conv.weight.data_ptr(), conv.weight._version, conv.bias._version, getattr(conv.weight, '_witw_version', 0),
-               getattr(conv.bias, '_witw_version', 0))
-        hit = self._packed.get(('first', bf16))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.PackedFirstConv(conv.weight, conv.bias, bf16=bf16))
-            self._packed[('first', bf16)] = hit
-        return hit[1]
-
-    def _pack_bf16(self, idx):
-        conv = _conv_of(self.model.features[idx])
-        key = (conv.weight.data_ptr(), conv.weight._version, conv.bias._version, getattr(conv.weight, '_witw_version', 0),
-               getattr(conv.bias, '_witw_version', 0))
-        hit = self._packed.get(('bf16', idx))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.PackedConvBf16(conv.weight, conv.bias, reuse=hit[1] if hit else None))
-            self._packed[('bf16', idx)] = hit
-        return hit[1]
-
-    def _pack_t_bf16(self, idx):
-        """bf16 dgrad filter (transpose + 180-degree tap rotation) of layer idx."""
-        conv = _conv_of(self.model.features[idx])
-        key = (conv.weight.data_ptr(), conv.weight._version, getattr(conv.weight, '_witw_version', 0))
-        hit = self._packed.get(('t_bf16', idx))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.PackedConvBf16(conv.weight, None, transpose_flip=True, reuse=hit[1] if hit else None))
-            self._packed[('t_bf16', idx)] = hit
-        return hit[1]
-
     def _refresh_packed_bf16(self, first):
         """Every STALE bf16 filter image the step from layer `first` on will use -- forward images of all layers, dgrad images
         (transposed, tap-rotated) of the layers behind `first` -- re-packed by one launch (ops.PackedConvBf16.batch) instead of one
-        launch + one bias copy per image as _pack_bf16 / _pack_t_bf16 would do them on first use: after an Adam update that is
-        11 images per encoder (model/cvig_fov.py:275-278: the trainable layers). The cache keys are those of the lazy methods."""
+        launch + one bias copy per image as _pack / _pack_t would do them on first use: after an Adam update that is
+        11 images per encoder (model/cvig_fov.py:275-278: the trainable layers). Slots and keys are those of _pack / _pack_t."""
         todo = []
         for (idx, sh, relu, pool, drop) in self.layer_specs:
             conv = _conv_of(self.model.features[idx])
-            fkey = (conv.weight.data_ptr(), conv.weight._version, conv.bias._version, getattr(conv.weight, '_witw_version', 0),
-                    getattr(conv.bias, '_witw_version', 0))
-            hit = self._packed.get(('bf16', idx))
-            if (hit is None or hit[0] != fkey) and not (idx == 0 and self.in_channels <= 8):     # layer 0 runs on the first-layer kernels: _pack_first
-                todo.append((('bf16', idx), fkey, (conv.weight, conv.bias, False, hit[1] if hit else None)))
-            if idx > first:
-                tkey = (conv.weight.data_ptr(), conv.weight._version, getattr(conv.weight, '_witw_version', 0))
-                hit = self._packed.get(('t_bf16', idx))
-                if hit is None or hit[0] != tkey:
-                    todo.append((('t_bf16', idx), tkey, (conv.weight, None, True, hit[1] if hit else None)))
+            for slot, transposed, used in (((_BF16.slot, idx), False, not (idx == 0 and self.in_channels <= _BF16.first_cin)),
+                                           ((_BF16.slot + '_t', idx), True, idx > first)):      # layer 0 of a small image: _pack_first
+                key = self._pack_key(conv, bias=not transposed)
+                hit = self._packed.get(slot)
+                if used and (hit is None or hit[0] != key):
+                    todo.append((slot, key, (conv.weight, None if transposed else conv.bias, transposed, hit[1] if hit else None)))
         if len(todo) > 1:
             for (slot, key, _item), pk in zip(todo, ops.PackedConvBf16.batch([t[2] for t in todo])):
                 self._packed[slot] = (key, pk)
 
-    def _run_bf16(self, x, scales, keep_from=None):
-        """The layer stack on the bf16 MFMA kernels (bf16 NHWC activations, fp32 accumulate, fp32 NCHW embedding).
-        Returns (embedding, kept) with kept[idx] = (layer input, layer output, max-pool arg-max codes or None) bf16 NHWC
-        for idx >= keep_from."""
-        fast0 = self.in_channels <= 8 and (keep_from is None or keep_from > 0)      # the bf16 first-layer kernel takes up to 8 channels
+    def _run(self, x, scales, keep_from=None, precision=_FP32):
+        """Layer stack in the arithmetic of `precision` (fp32 NHWC, bf16 NHWC or split-fp16 activations; fp32 NCHW embedding).
+        Returns (embedding, kept) where kept[idx] = (layer input, layer output, max-pool arg-max codes or None) in that layout
+        for every layer idx >= keep_from (what the backward needs)."""
+        p = precision
+        fast0 = self.in_channels <= p.first_cin and (keep_from is None or keep_from > 0)     # straight from NCHW on the first-layer kernel
         x_nchw = x.contiguous()
-        h = x_nchw if fast0 else ops.nchw_to_nhwc_bf16(x_nchw, 16)
-        sp0 = self.layer_specs[0]
-        first_direct = (not fast0 and self.in_channels <= 8 and sp0[0] == 0 and sp0[1] == 1 and not sp0[3] and 0 not in scales
-                        and keep_from is not None and keep_from <= 0)
+        h = x_nchw if fast0 else p.image_in(x_nchw)
+        circ = self.circ_padding
         last = self.layer_specs[-1][0]
         kept = {}
-        # layers 0 and 2 in one kernel, as forward_bf16 runs them, when neither is kept for a backward (cvig_fov: the frozen trunk,
-        # model/cvig_fov.py:275-278 -- the backward starts at layer 17) nor carries a Dropout2d scale: the same bits as the two launches
-        fuse = _lib.guards()['first2']['hand_scheduled_kernel'] if self.fuse_first2 is None else self.fuse_first2
-        fused = (fast0 and fuse and (keep_from is None or keep_from > 2) and 0 not in scales and 2 not in scales and
-                 self.layer_specs[0][:4] == (0, 1, True, False) and self.layer_specs[1][:4] == (2, 1, True, True))
-        # ... and when the backward DOES cross both layers (layer 0 trains: cvig_semantic, model/cvig_semantic.py:301-309) the training
-        # form of the same kernel: neither 64-channel activation is written -- the backward gets the max-pool's arg-max codes, layer
-        # 2's gate is its pooled output, layer 0's gate one bit per output (67 MB instead of the 1.07 GB map at 128 images). Needs
-        # the data gradient of layer 2 on the weight-resident kernel (the one that reads bit gates); smaller batches keep the two launches.
-        B_, _C, H_, W_ = x_nchw.shape
-        fused_train = (first_direct and fuse and keep_from == 0 and 2 not in scales and H_ % 2 == 0 and W_ % 2 == 0 and
-                       self.layer_specs[0][:4] == (0, 1, True, False) and self.layer_specs[1][:4] == (2, 1, True, True) and
-                       not _conv_of(self.model.features[2]).weight.requires_grad and ops.gatebits_dgrad_ok(B_, H_, W_, 64, 64))
+        first_direct = fused = fused_train = False
+        conv_fwd = getattr(ops, p.conv_fwd)
+        if p is _BF16:      # ---- bf16 only: the forms the first two layers can take
+            sp0 = self.layer_specs[0]
+            first_direct = (not fast0 and self.in_channels <= 8 and sp0[0] == 0 and sp0[1] == 1 and not sp0[3] and 0 not in scales
+                            and keep_from is not None and keep_from <= 0)
+            # layers 0 and 2 in one kernel when neither is kept for a backward (inference; cvig_fov: the frozen trunk,
+            # model/cvig_fov.py:275-278 -- the backward starts at layer 17) nor carries a Dropout2d scale: the same bits as the two
+            # launches, the 64-channel map between them stays on the chip (csrc/conv_first2_bf16.hip)
+            fuse = _lib.guards()['first2']['hand_scheduled_kernel'] if self.fuse_first2 is None else self.fuse_first2
+            fused = (fast0 and fuse and (keep_from is None or keep_from > 2) and 0 not in scales and 2 not in scales and
+                     self.layer_specs[0][:4] == (0, 1, True, False) and self.layer_specs[1][:4] == (2, 1, True, True))
+            # ... and when the backward DOES cross both layers (layer 0 trains: cvig_semantic, model/cvig_semantic.py:301-309) the training
+            # form of the same kernel: neither 64-channel activation is written -- the backward gets the max-pool's arg-max codes, layer
+            # 2's gate is its pooled output, layer 0's gate one bit per output (67 MB instead of the 1.07 GB map at 128 images). Needs
+            # the data gradient of layer 2 on the weight-resident kernel (the one that reads bit gates); smaller batches keep the two launches.
+            B_, _C, H_, W_ = x_nchw.shape
+            fused_train = (first_direct and fuse and keep_from == 0 and 2 not in scales and H_ % 2 == 0 and W_ % 2 == 0 and
+                           self.layer_specs[0][:4] == (0, 1, True, False) and self.layer_specs[1][:4] == (2, 1, True, True) and
+                           not _conv_of(self.model.features[2]).weight.requires_grad and ops.gatebits_dgrad_ok(B_, H_, W_, 64, 64))
         for (idx, sh, relu, pool, drop) in self.layer_specs:
             if idx == 0 and fused:
-                h = ops.conv_first2_bf16(h, self._pack_first(True), self._pack_bf16(2), circular=self.circ_padding)
+                h = ops.conv_first2_bf16(h, self._pack_first(True), self._pack(2, p), circular=circ)
                 continue
             if idx == 2 and (fused or fused_train):
                 continue
             if idx == 0 and fused_train:
-                y2, code2, bits0 = ops.conv_first2_bf16_train(x_nchw, self._pack_first(True), self._pack_bf16(2), circular=self.circ_padding)
+                y2, code2, bits0 = ops.conv_first2_bf16_train(x_nchw, self._pack_first(True), self._pack(2, p), circular=circ)
                 kept[0] = (h, _GateBits(bits0), None)                      # h: the NHWC bf16 image, what layer 0's weight gradient reads
                 kept[2] = (_ShapeOnly((B_, H_, W_, 64)), y2, code2)         # layer 2 is frozen: nobody reads its input
                 h = y2
                 continue
-            if idx == 0 and fast0:
-                h = ops.conv3x3_first_fwd(h, self._pack_first(True), circular=self.circ_padding, relu=relu)
-                continue
-            keep = keep_from is not None and idx >= keep_from
             if idx == 0 and first_direct:
                 # a TRAINABLE layer 0 (cvig_semantic, model/cvig_semantic.py:301-309): its forward still runs on the first-layer kernel
                 # straight from the NCHW image (the generic kernel on the 16-channel NHWC copy is bound by that copy's pixel stride:
                 # 628 against ~300 us at 128 images); the NHWC bf16 copy h is only what the weight gradient reads
-                y = ops.conv3x3_first_fwd(x_nchw, self._pack_first(True), circular=self.circ_padding, relu=relu)
+                y = ops.conv3x3_first_fwd(x_nchw, self._pack_first(True), circular=circ, relu=relu)
                 kept[idx] = (h, y, None)
                 h = y
                 continue
-            out = ops.conv3x3_bf16_fwd(h, self._pack_bf16(idx), stride_h=sh, circular=self.circ_padding, relu=relu, pool=pool,
-                                       out_nchw_f32=(idx == last), drop_scale=scales.get(idx), want_pool_code=(keep and pool))
+            # ---- every precision
+            if idx == 0 and fast0:     # layer 0 is frozen here: nothing to keep
+                h = ops.conv3x3_first_fwd(h, self._pack_first(p.first_bf16), circular=circ, relu=relu, **p.first_kw)
+                continue
+            keep = keep_from is not None and idx >= keep_from
+            # no backward consumes an inference pass: its stride-1 layers may run the Winograd form (fp32 only)
+            pk = self._pack(idx, p, wino=p.wino and keep_from is None and sh == 1)
+            out = conv_fwd(h, pk, stride_h=sh, circular=circ, relu=relu, pool=pool, drop_scale=scales.get(idx),
+                           want_pool_code=(keep and pool), **{p.nchw_kw: idx == last})
             y, code = out if (keep and pool) else (out, None)
             if keep:
                 kept[idx] = (h, y, code)
@@ -341,57 +341,7 @@ class FOV_DSM(torch.nn.Module):
         if self.training:
             raise _lib.WitwError('forward_bf16 is an inference path; call .eval()')
         with torch.no_grad():
-            fast0 = self.in_channels <= 8
-            h = x.contiguous() if fast0 else ops.nchw_to_nhwc_bf16(x.contiguous(), 16)
-            last = self.layer_specs[-1][0]
-            # layers 0 and 2 in one kernel (the 64-channel map between them stays on the chip): csrc/conv_first2_bf16.hip
-            fuse = _lib.guards()['first2']['hand_scheduled_kernel'] if self.fuse_first2 is None else self.fuse_first2
-            fused = fast0 and fuse and self.layer_specs[0][:4] == (0, 1, True, False) and self.layer_specs[1][:4] == (2, 1, True, True)
-            for (idx, sh, relu, pool, drop) in self.layer_specs:
-                if idx == 0 and fused:
-                    h = ops.conv_first2_bf16(h, self._pack_first(True), self._pack_bf16(2), circular=self.circ_padding)
-                    continue
-                if idx == 2 and fused:
-                    continue
-                if idx == 0 and fast0:
-                    h = ops.conv3x3_first_fwd(h, self._pack_first(True), circular=self.circ_padding, relu=relu)
-                    continue
-                h = ops.conv3x3_bf16_fwd(h, self._pack_bf16(idx), stride_h=sh, circular=self.circ_padding, relu=relu,
-                                         pool=pool, out_nchw_f32=(idx == last))
-        return h
-
-    def _pack_f16x3(self, idx, transpose_flip=False):
-        conv = _conv_of(self.model.features[idx])
-        key = (conv.weight.data_ptr(), conv.weight._version, conv.bias._version, getattr(conv.weight, '_witw_version', 0),
-               getattr(conv.bias, '_witw_version', 0))
-        slot = ('f16x3_t' if transpose_flip else 'f16x3', idx)
-        hit = self._packed.get(slot)
-        if hit is None or hit[0] != key:
-            hit = (key, ops.PackedConvF16x3(conv.weight, None if transpose_flip else conv.bias, transpose_flip=transpose_flip,
-                                            reuse=hit[1] if hit else None))
-            self._packed[slot] = hit
-        return hit[1]
-
-    def _run_f16x3(self, x, scales, keep_from=None):
-        """The layer stack on the fp16x3 kernels (split-fp16 activations, fp32-grade products, fp32 NCHW embedding).
-        Returns (embedding, kept) with kept[idx] = (layer input, layer output, max-pool arg-max codes or None) in the split
-        layout for idx >= keep_from."""
-        fast0 = self.in_channels <= 4 and (keep_from is None or keep_from > 0)
-        h = x.contiguous() if fast0 else ops.nchw_to_split_f16(x.contiguous(), 8)
-        last = self.layer_specs[-1][0]
-        kept = {}
-        for (idx, sh, relu, pool, drop) in self.layer_specs:
-            if idx == 0 and fast0:      # C<=4 -> 64 in exact fp32 straight from NCHW, output already split
-                h = ops.conv3x3_first_fwd(h, self._pack_first(False), circular=self.circ_padding, relu=relu, split_f16=True)
-                continue
-            keep = keep_from is not None and idx >= keep_from
-            out = ops.conv3x3_f16x3_fwd(h, self._pack_f16x3(idx), stride_h=sh, circular=self.circ_padding, relu=relu, pool=pool,
-                                        out_nchw_f32=(idx == last), drop_scale=scales.get(idx), want_pool_code=(keep and pool))
-            y, code = out if (keep and pool) else (out, None)
-            if keep:
-                kept[idx] = (h, y, code)
-            h = y
-        return h, kept
+            return self._run(x, {}, precision=_BF16)[0]
 
     def forward_f16x3(self, x):
         """Inference with fp32-grade accuracy on the fp16 MFMA (csrc/conv3x3_f16x3.hip): every activation and filter
@@ -402,7 +352,7 @@ class FOV_DSM(torch.nn.Module):
         if self.training:
             raise _lib.WitwError('forward_f16x3 is an inference path; call .eval()')
         with torch.no_grad():
-            return self._run_f16x3(x, {})[0]
+            return self._run(x, {}, precision=_F16X3)[0]
 
     def trainable_convs(self):
         return [(idx, _conv_of(self.model.features[idx])) for (idx, *_r) in self.layer_specs
@@ -431,18 +381,15 @@ class FOV_DSM(torch.nn.Module):
             params = []
             for _i, c in tr:
                 params += [c.weight, c.bias]
-            fn = _EncoderFnBf16 if self.precision == 'bf16' else _EncoderFnF16x3 if self.precision == 'fp16x3' else _EncoderFn
             # the dicts are read when the backward runs, so a caller may fill them between forward and backward
             self._bwd_override = ({} if relu_gates is None else relu_gates, {} if pool_codes is None else pool_codes)
             bucket = getattr(self, '_grad_bucket', None)
             if bucket is not None:      # parallel.GradBucket: how many backward nodes of this encoder the step will run
                 bucket.nodes += 1
-            return fn.apply(x, self, scales, *params)
-        if self.precision == 'fp16x3' and not self.training:
-            return self.forward_f16x3(x)
-        if self.precision == 'bf16':
-            return self._run_bf16(x, scales)[0]
-        return self._run(x, scales)[0]
+            return _EncoderFn.apply(x, self, _PRECISIONS.get(self.precision, _FP32), scales, *params)
+        if self.precision == 'fp16x3':      # without autograd fp16x3 is an evaluation path (forward_f16x3); in train() mode: fp32
+            return self.forward_f16x3(x) if not self.training else self._run(x, scales)[0]
+        return self._run(x, scales, precision=_PRECISIONS.get(self.precision, _FP32))[0]
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -450,96 +397,71 @@ class _EncoderFn(torch.autograd.Function):
     27 down to the first trainable one: per trainable layer one wgrad launch, per layer one dgrad launch (the
     forward kernel on the transposed, tap-rotated filter with the previous layer's ReLU / Dropout2d gate fused
     into its epilogue, zero-interleaved rows for the stride-(2,1) layers) and, behind a fused max-pool, the
-    arg-max scatter. cvig_fov stops at layer 17; cvig_semantic (layer 0 trainable) goes all the way down."""
+    arg-max scatter. cvig_fov stops at layer 17; cvig_semantic (layer 0 trainable) goes all the way down.
+
+    `precision` (a _Precision) names the kernels and the activation layout. 'fp32' is the parity path. 'bf16' is the
+    mixed-precision step: bf16 activations / filters / activation gradients, fp32 accumulation, fp32 weight gradients (the
+    fp32 master weights and Adam are untouched); no reference counterpart -- parity is stated against the fp32 HIP path in
+    tests/test_bf16_train_gpu.py. 'fp16x3' has fp32-grade products on the fp16 MFMA with split-fp16 activations and gradients,
+    its weight gradients come from witw_conv3x3_wgrad_f16x3 over the batch-octet layout (tests/test_f16x3_gpu.py)."""
 
     @staticmethod
-    def forward(ctx, x, enc, scales, *params):
+    def forward(ctx, x, enc, precision, scales, *params):
         first = min(i for i, _c in enc.trainable_convs())
-        out, kept = enc._run(x, scales, keep_from=first)
-        ctx.enc, ctx.scales, ctx.kept, ctx.first = enc, scales, kept, first
-        ctx.override = getattr(enc, '_bwd_override', ({}, {}))
-        enc._bwd_override = ({}, {})
-        enc._last_kept = kept if getattr(enc, 'keep_activations', False) else None      # diagnostics: gates of the last call
+        if precision is _BF16:      # all stale filter images of the step in one launch instead of one each on first use
+            enc._refresh_packed_bf16(first)
+        out, kept = enc._run(x, scales, keep_from=first, precision=precision)
+        ctx.enc, ctx.precision, ctx.scales, ctx.kept, ctx.first = enc, precision, scales, kept, first
+        if precision.overrides:
+            ctx.override = getattr(enc, '_bwd_override', ({}, {}))
+            enc._bwd_override = ({}, {})
+            enc._last_kept = kept if getattr(enc, 'keep_activations', False) else None      # diagnostics: gates of the last call
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        enc, scales, kept = ctx.enc, ctx.scales, ctx.kept
+        enc, p, scales, kept = ctx.enc, ctx.precision, ctx.scales, ctx.kept
         specs = [sp for sp in enc.layer_specs if sp[0] >= ctx.first]
         circ = enc.circ_padding
         last = specs[-1][0]
         cout_last = _conv_of(enc.model.features[last]).out_channels
-        dz = ops.nchw_to_nhwc(grad_out.contiguous(), (cout_last + 7) // 8 * 8)   # layer 27 has no ReLU
+        dz = p.to_layout(grad_out.contiguous(), (cout_last + p.cpad - 1) // p.cpad * p.cpad)   # layer 27 has no ReLU
         grads = {}
+        conv_fwd = getattr(ops, p.conv_fwd)
         bucket = getattr(enc, '_grad_bucket', None)      # parallel.GradBucket: the wgrad kernels write into its views
-        direct = bucket is not None and bucket.direct()
+        direct = p.direct is not None and bucket is not None and bucket.direct() and p.direct(enc)
         for n in range(len(specs) - 1, -1, -1):
             idx, sh, relu, pool, drop = specs[n]
             x_in = kept[idx][0]
             conv = _conv_of(enc.model.features[idx])
             if conv.weight.requires_grad:
-                out = (conv.weight._witw_grad_view, conv.bias._witw_grad_view) if direct else None
-                grads[idx] = ops.conv3x3_wgrad(x_in, dz, conv.in_channels, stride_h=sh, circular=circ, out=out)
+                if direct:
+                    grads[idx] = p.wgrad(x_in, dz, conv.in_channels, stride_h=sh, circular=circ,
+                                         out=(conv.weight._witw_grad_view, conv.bias._witw_grad_view))
+                else:
+                    dw, db = p.wgrad(x_in, dz, conv.in_channels, stride_h=sh, circular=circ)
+                    grads[idx] = (dw[:conv.out_channels].contiguous(), db[:conv.out_channels].contiguous()) if p.slice_wgrad else (dw, db)
             if n > 0:   # gradient at the previous layer's conv output
                 pidx, _psh, _prelu, ppool, _pdrop = specs[n - 1]
-                p_in, p_out, p_code = kept[pidx]
-                p_gate = ctx.override[0].get(pidx, p_out)
-                p_code = ctx.override[1].get(pidx, p_code)
-                dy = ops.conv3x3_fwd(dz, enc._pack_t(idx), stride_h=1, circular=circ, relu=False, pool=False,
-                                     drop_scale=scales.get(pidx), gate=p_gate, dilate_h=(sh == 2),
-                                     out_h=x_in.shape[1] if sh == 2 else None)
-                dz = ops.maxpool2x2_bwd(dy, p_code, (p_in.shape[1], p_in.shape[2])) if ppool else dy
+                p_in, p_gate, p_code = kept[pidx]
+                if p.overrides:
+                    p_gate = ctx.override[0].get(pidx, p_gate)
+                    p_code = ctx.override[1].get(pidx, p_code)
+                if p is _BF16 and isinstance(p_gate, _GateBits):      # the fused first-two-layers forward kept this gate as bits
+                    dy = ops.conv3x3_bf16_dgrad_gatebits(dz, enc._pack_t(idx, p), p_gate.bits, circular=circ)
+                else:
+                    dy = conv_fwd(dz, enc._pack_t(idx, p), stride_h=1, circular=circ, relu=False, pool=False,
+                                    drop_scale=scales.get(pidx), gate=p_gate, dilate_h=(sh == 2),
+                                    out_h=x_in.shape[1] if sh == 2 else None)
+                dz = p.pool_bwd(dy, p_code, (p_in.shape[1], p_in.shape[2])) if ppool else dy
         ctx.kept = None
         if direct:      # the gradients already sit in the parameters' .grad views: nothing for autograd to accumulate
             bucket.notify()
-            return (None, None, None) + (None,) * (2 * len(enc.trainable_convs()))
+            return (None, None, None, None) + (None,) * (2 * len(enc.trainable_convs()))
         flat = []
         for (idx, _c) in enc.trainable_convs():
             flat += [grads[idx][0], grads[idx][1]]
-        return (None, None, None) + tuple(flat)
-
-
-class _EncoderFnF16x3(torch.autograd.Function):
-    """_EncoderFn with fp32-grade products on the fp16 MFMA (FOV_DSM.precision = 'fp16x3'): the forward (frozen trunk and
-    trainable layers, Dropout2d scale in the epilogue) and every dgrad launch run on the fp16x3 kernels with split-fp16
-    activations and activation gradients; the weight gradients come from witw_conv3x3_wgrad_f16x3 (the same split
-    products over the batch-octet layout), in fp32. Parity: tests/test_f16x3_gpu.py against the fp32 path."""
-
-    @staticmethod
-    def forward(ctx, x, enc, scales, *params):
-        first = min(i for i, _c in enc.trainable_convs())
-        out, kept = enc._run_f16x3(x, scales, keep_from=first)
-        ctx.enc, ctx.scales, ctx.kept, ctx.first = enc, scales, kept, first
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        enc, scales, kept = ctx.enc, ctx.scales, ctx.kept
-        specs = [sp for sp in enc.layer_specs if sp[0] >= ctx.first]
-        circ = enc.circ_padding
-        last = specs[-1][0]
-        cout_last = _conv_of(enc.model.features[last]).out_channels
-        dz = ops.nchw_to_split_f16(grad_out.contiguous(), (cout_last + 7) // 8 * 8)      # layer 27 has no ReLU
-        grads = {}
-        for n in range(len(specs) - 1, -1, -1):
-            idx, sh, relu, pool, drop = specs[n]
-            x_in = kept[idx][0]
-            conv = _conv_of(enc.model.features[idx])
-            if conv.weight.requires_grad:
-                dw, db = ops.conv3x3_wgrad_f16x3(x_in, dz, conv.in_channels, stride_h=sh, circular=circ)
-                grads[idx] = (dw[:conv.out_channels].contiguous(), db[:conv.out_channels].contiguous())
-            if n > 0:   # gradient at the previous layer's conv output
-                pidx, _psh, _prelu, ppool, _pdrop = specs[n - 1]
-                p_in, p_out, p_code = kept[pidx]
-                dy = ops.conv3x3_f16x3_fwd(dz, enc._pack_f16x3(idx, transpose_flip=True), stride_h=1, circular=circ, relu=False,
-                                           pool=False, drop_scale=scales.get(pidx), gate=p_out, dilate_h=(sh == 2),
-                                           out_h=x_in.shape[1] if sh == 2 else None)
-                dz = ops.maxpool2x2_bwd_split(dy, p_code, (p_in.shape[1], p_in.shape[2])) if ppool else dy
-        ctx.kept = None
-        flat = []
-        for (idx, _c) in enc.trainable_convs():
-            flat += [grads[idx][0], grads[idx][1]]
-        return (None, None, None) + tuple(flat)
+        return (None, None, None, None) + tuple(flat)
 
 
 class _GateBits(object):
@@ -556,65 +478,6 @@ class _ShapeOnly(object):
 
     def __init__(self, shape):
         self.shape = tuple(shape)
-
-
-class _EncoderFnBf16(torch.autograd.Function):
-    """_EncoderFn on the bf16 MFMA kernels (FOV_DSM.precision = 'bf16'): mixed-precision training step with bf16
-    activations / filters / activation gradients, fp32 accumulation, fp32 weight gradients (the fp32 master weights and
-    Adam are untouched). Per trainable layer one witw_conv3x3_wgrad_bf16 (operands re-laid out to the batch-octet
-    layout), per layer one dgrad launch = the bf16 forward kernel on the transposed, tap-rotated filter with the
-    ReLU / Dropout2d gate in its epilogue. No reference counterpart (the reference trains in fp32 only): parity is
-    stated against the fp32 HIP path in tests/test_bf16_train_gpu.py."""
-
-    @staticmethod
-    def forward(ctx, x, enc, scales, *params):
-        first = min(i for i, _c in enc.trainable_convs())
-        enc._refresh_packed_bf16(first)
-        out, kept = enc._run_bf16(x, scales, keep_from=first)
-        ctx.enc, ctx.scales, ctx.kept, ctx.first = enc, scales, kept, first
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        enc, scales, kept = ctx.enc, ctx.scales, ctx.kept
-        specs = [sp for sp in enc.layer_specs if sp[0] >= ctx.first]
-        circ = enc.circ_padding
-        last = specs[-1][0]
-        cout_last = _conv_of(enc.model.features[last]).out_channels
-        dz = ops.nchw_to_nhwc_bf16(grad_out.contiguous(), (cout_last + 15) // 16 * 16)   # layer 27 has no ReLU
-        grads = {}
-        bucket = getattr(enc, '_grad_bucket', None)      # parallel.GradBucket: the wgrad kernels write into its views (as _EncoderFn)
-        # ... when no layer's gradient tensor carries padded output channels (bf16 activations are stored in multiples of 16)
-        direct = bucket is not None and bucket.direct() and all(c.out_channels % 16 == 0 for _i, c in enc.trainable_convs())
-        for n in range(len(specs) - 1, -1, -1):
-            idx, sh, relu, pool, drop = specs[n]
-            x_in = kept[idx][0]
-            conv = _conv_of(enc.model.features[idx])
-            if conv.weight.requires_grad:
-                if direct:
-                    grads[idx] = ops.conv3x3_wgrad_bf16(x_in, dz, conv.in_channels, stride_h=sh, circular=circ,
-                                                        out=(conv.weight._witw_grad_view, conv.bias._witw_grad_view))
-                else:
-                    dw, db = ops.conv3x3_wgrad_bf16(x_in, dz, conv.in_channels, stride_h=sh, circular=circ)
-                    grads[idx] = (dw[:conv.out_channels].contiguous(), db[:conv.out_channels].contiguous())
-            if n > 0:   # gradient at the previous layer's conv output
-                pidx, _psh, _prelu, ppool, _pdrop = specs[n - 1]
-                p_in, p_out, p_code = kept[pidx]
-                if isinstance(p_out, _GateBits):      # the fused first-two-layers forward kept this gate as bits
-                    dy = ops.conv3x3_bf16_dgrad_gatebits(dz, enc._pack_t_bf16(idx), p_out.bits, circular=circ)
-                else:
-                    dy = ops.conv3x3_bf16_fwd(dz, enc._pack_t_bf16(idx), stride_h=1, circular=circ, relu=False, pool=False,
-                                              drop_scale=scales.get(pidx), gate=p_out, dilate_h=(sh == 2),
-                                              out_h=x_in.shape[1] if sh == 2 else None)
-                dz = ops.maxpool2x2_bwd_bf16(dy, p_code, (p_in.shape[1], p_in.shape[2])) if ppool else dy
-        ctx.kept = None
-        if direct:      # the gradients already sit in the parameters' .grad views: nothing for autograd to accumulate
-            bucket.notify()
-            return (None, None, None) + (None,) * (2 * len(enc.trainable_convs()))
-        flat = []
-        for (idx, _c) in enc.trainable_convs():
-            flat += [grads[idx][0], grads[idx][1]]
-        return (None, None, None) + tuple(flat)
 
 
 # ----------------------------------------------------------------------------- transforms

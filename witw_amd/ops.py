@@ -32,7 +32,100 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
-class PackedConv:
+def _prof_begin():
+    """Open a PROFILE bracket on the launch stream: None when nobody measures, else the (start, end) events, start recorded."""
+    if PROFILE is None:
+        return None
+    ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev[0].record()
+    return ev
+
+
+def _prof_end(ev, variant, flop, kernel=None):
+    """Close the bracket `ev` around the launch(es) since _prof_begin and append (variant, flop, start, end) to PROFILE. `variant` may
+    be a callable: it is evaluated after the end event is recorded, for tuples that ask the library what the launcher picked.
+    kernel: also file (flop, start, end) in PROFILE_BY_KERNEL under this name; True = last_kernel_variant()."""
+    ev[1].record()
+    PROFILE.append((variant() if callable(variant) else variant, flop) + ev)
+    if kernel is not None and PROFILE_BY_KERNEL is not None:
+        PROFILE_BY_KERNEL.setdefault(last_kernel_variant() if kernel is True else kernel, []).append((flop,) + ev)
+
+
+def _conv_fwd_setup(name, x, C, packed, stride_h, pool, nchw, dilate_h, out_h, drop_scale, gate):
+    """What conv3x3_fwd, conv3x3_bf16_fwd and conv3x3_f16x3_fwd share. x: the input in its layout ([B,H,W,...], C = its padded
+    channels); the output takes x's layout and dtype, or is the fp32 NCHW map with `nchw`. Checks the channel count, dilate_h /
+    out_h, drop_scale and gate, and returns (H, flop_rows, y, drop_scale): the logical (zero-interleaved) input height, the rows
+    of the launch's algorithmic FLOP count, the empty output and the checked drop_scale."""
+    B, H, W = x.shape[:3]
+    if C != packed.cin_pad:
+        raise _lib.WitwError('%s: input has %d channels, packed weights expect %d' % (name, C, packed.cin_pad))
+    h_phys = H
+    if dilate_h:
+        if out_h is None or (out_h - 1) // 2 + 1 != H:
+            raise _lib.WitwError('%s: dilate_h needs out_h with (out_h-1)//2+1 == %d physical rows' % (name, H))
+        H = out_h          # logical (zero-interleaved) height
+    Ho = (H + 2 - 3) // stride_h + 1
+    # a zero-interleaved launch is the data gradient of a stride-(2,1) conv, whose multiply-adds are those of that conv's forward
+    # (one per real input row), not one per interleaved row
+    flop_rows = h_phys if dilate_h else Ho
+    Hy, Wy = (Ho // 2, W // 2) if pool else (Ho, W)
+    if nchw:
+        y = torch.empty((B, packed.cout, Hy, Wy), dtype=torch.float32, device=x.device)
+    elif x.dtype == torch.float32:
+        y = torch.empty((B, Hy, Wy, packed.cout), dtype=torch.float32, device=x.device)
+    elif x.dtype == torch.bfloat16:
+        if packed.cout % 16:
+            raise _lib.WitwError('%s: a bf16 NHWC output needs Cout %% 16 == 0 (next layer\'s K chunk)' % name)
+        y = torch.empty((B, Hy, Wy, packed.cout), dtype=torch.bfloat16, device=x.device)
+    else:
+        if packed.cout % 8:
+            raise _lib.WitwError('%s: a split-fp16 output needs Cout %% 8 == 0' % name)
+        y = torch.empty((B, Hy, Wy, packed.cout // 8, 2, 8), dtype=torch.float16, device=x.device)
+    if drop_scale is not None:
+        drop_scale = _dev_f32(drop_scale, 'drop_scale')
+        if tuple(drop_scale.shape) != (B, packed.cout):
+            raise _lib.WitwError('drop_scale must be [B,Cout]')
+    if gate is not None:
+        if x.dtype == torch.float32:
+            if tuple(_dev_f32(gate, 'gate').shape) != tuple(y.shape):
+                raise _lib.WitwError('gate must have the output shape %s, got %s' % (tuple(y.shape), tuple(gate.shape)))
+        elif x.dtype == torch.bfloat16:
+            if not (gate.is_cuda and gate.dtype == torch.bfloat16 and gate.is_contiguous() and tuple(gate.shape) == tuple(y.shape)):
+                raise _lib.WitwError('gate must be a contiguous bfloat16 GPU tensor with the output shape %s' % (tuple(y.shape),))
+        elif not (_is_split(gate) and tuple(gate.shape) == tuple(y.shape)):
+            raise _lib.WitwError('gate must be a split-fp16 GPU tensor with the output shape %s' % (tuple(y.shape),))
+    return H, flop_rows, y, drop_scale
+
+
+class _Packed(object):
+    """What PackedConv, PackedConvBf16 and PackedConvF16x3 share: the geometry (cout, cin, cin_pad) and the device buffers (wpk,
+    bias), fresh or those of `reuse` -- an image of the same layer and mode that is overwritten in place (re-packing after an
+    optimizer step without allocating or zero-filling; stream order keeps earlier launches safe)."""
+    CPAD = 8                # channel padding of the kernel's activations
+    DTYPE = torch.float32   # of wpk
+
+    def _filter_buffer(self, weight, transpose_flip, reuse, n_elems):
+        """-> (weight checked, reuse or None if it does not fit); n_elems(cout, cin): size of wpk"""
+        w = _dev_f32(weight.detach(), 'weight')
+        # transpose_flip: the dgrad filter w_t[ci][co][kh][kw] = w[co][ci][2-kh][2-kw] maps grad_out (w.shape[0]) -> grad_in
+        self.cout, self.cin = (w.shape[1], w.shape[0]) if transpose_flip else (w.shape[0], w.shape[1])
+        self.cin_pad = (self.cin + self.CPAD - 1) // self.CPAD * self.CPAD
+        n_pk = n_elems(self.cout, self.cin)
+        if reuse is not None and not (reuse.wpk.numel() == n_pk and reuse.wpk.device == w.device and reuse.cout == self.cout):
+            reuse = None
+        self.wpk = reuse.wpk if reuse is not None else torch.empty(n_pk, dtype=self.DTYPE, device=w.device)
+        return w, reuse
+
+    def _bias_buffer(self, reuse, bias=None, floats=None):
+        """the fp32 bias padded to the channel tile (floats: its size, if the caller has asked the library already): zeros, then
+        `bias` in the real entries"""
+        self.bias = reuse.bias if reuse is not None else torch.zeros(
+            _lib.load().witw_conv3x3_bias_floats(self.cout) if floats is None else floats, dtype=torch.float32, device=self.wpk.device)
+        if bias is not None:
+            self.bias[:self.cout].copy_(bias.detach())
+
+
+class PackedConv(_Packed):
     """Weights of one 3x3 conv packed for the MFMA kernel ([n_tile][cin/8][tap][quad][TN][4])
     plus the zero-padded bias. `transpose_flip` packs the dgrad filter of the same weights. `taps4` packs only the
     2x2 sub-window that is live in a filter whose first tap row/column are zero (cvig_baseline's 4x4/s2 convs over the
@@ -46,27 +139,16 @@ class PackedConv:
         lib = _lib.load()
         if wino and (transpose_flip or taps4):
             raise _lib.WitwError('PackedConv: the Winograd filter is packed for forward 3x3 launches only')
-        w = _dev_f32(weight.detach(), 'weight')
-        if transpose_flip:
-            cin, cout = w.shape[0], w.shape[1]   # packed filter maps grad_out (w.shape[0]) -> grad_in
-        else:
-            cout, cin = w.shape[0], w.shape[1]
-        self.cout, self.cin = cout, cin
-        self.cin_pad = (cin + 7) // 8 * 8
         self.taps4 = bool(taps4)
         self.tap_base = 0 if transpose_flip else 1
-        n_pk = lib.witw_conv3x3_packed_floats_taps4(cout, cin) if taps4 else lib.witw_conv3x3_packed_floats(cout, cin)
-        if reuse is not None and not (reuse.wpk.numel() == n_pk and reuse.wpk.device == w.device and reuse.cout == cout
-                                      and reuse.taps4 == self.taps4):
+        if reuse is not None and reuse.taps4 != self.taps4:
             reuse = None
-        if taps4:
-            self.wpk = reuse.wpk if reuse is not None else torch.empty(n_pk, dtype=torch.float32, device=w.device)
-            _lib.check(lib.witw_conv3x3_pack_weights_taps4(w.data_ptr(), self.wpk.data_ptr(), cout, cin, int(transpose_flip),
-                                                           _stream()), 'witw_conv3x3_pack_weights_taps4')
-        else:
-            self.wpk = reuse.wpk if reuse is not None else torch.empty(n_pk, dtype=torch.float32, device=w.device)
-            _lib.check(lib.witw_conv3x3_pack_weights(w.data_ptr(), self.wpk.data_ptr(), cout, cin, int(transpose_flip),
-                                                     _stream()), 'witw_conv3x3_pack_weights')
+        w, reuse = self._filter_buffer(weight, transpose_flip, reuse,
+                                       lib.witw_conv3x3_packed_floats_taps4 if taps4 else lib.witw_conv3x3_packed_floats)
+        cout, cin = self.cout, self.cin
+        pack, what = (lib.witw_conv3x3_pack_weights_taps4, 'witw_conv3x3_pack_weights_taps4') if taps4 else \
+            (lib.witw_conv3x3_pack_weights, 'witw_conv3x3_pack_weights')
+        _lib.check(pack(w.data_ptr(), self.wpk.data_ptr(), cout, cin, int(transpose_flip), _stream()), what)
         self.wpk_wino = None
         if wino:
             n_w = lib.witw_conv3x3_packed_floats_wino(cout, cin)
@@ -74,10 +156,7 @@ class PackedConv:
             self.wpk_wino = old if old is not None and old.numel() == n_w else torch.empty(n_w, dtype=torch.float32, device=w.device)
             _lib.check(lib.witw_conv3x3_pack_weights_wino(w.data_ptr(), self.wpk_wino.data_ptr(), cout, cin, _stream()),
                        'witw_conv3x3_pack_weights_wino')
-        nb = lib.witw_conv3x3_bias_floats(cout)
-        self.bias = reuse.bias if reuse is not None else torch.zeros(nb, dtype=torch.float32, device=w.device)
-        if bias is not None and not transpose_flip:
-            self.bias[:cout].copy_(bias.detach())
+        self._bias_buffer(reuse, None if transpose_flip else bias, floats=lib.witw_conv3x3_bias_floats(cout))
 
 
 class PackedFirstConv:
@@ -109,16 +188,12 @@ def conv3x3_first_fwd(x_nchw, packed, circular=False, relu=True, split_f16=False
         y = torch.empty((B, H, W, 8, 2, 8), dtype=torch.float16, device=x.device)
     else:
         y = torch.empty((B, H, W, 64), dtype=torch.bfloat16 if packed.bf16 else torch.float32, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     _lib.check(lib.witw_conv3x3_first_fwd(x.data_ptr(), packed.wf.data_ptr(), packed.bias.data_ptr(), y.data_ptr(), B, C, H, W,
                                           int(circular), int(relu), 2 if split_f16 else int(packed.bf16), _stream()),
                'witw_conv3x3_first_fwd')
     if prof is not None:
-        e1.record()
-        prof.append((('first', packed.bf16), 2.0 * C * 64 * 9 * H * W * B, e0, e1))
+        _prof_end(prof, ('first', packed.bf16), 2.0 * C * 64 * 9 * H * W * B)
     return y
 
 
@@ -131,18 +206,12 @@ def conv_first2_bf16(x_nchw, packed_first, packed_second, circular=False):
     if not packed_first.bf16 or C != packed_first.cin or packed_second.cin != 64 or packed_second.cout != 64:
         raise _lib.WitwError('conv_first2_bf16: needs a bf16-packed C -> 64 first filter and a 64 -> 64 second one')
     y = torch.empty((B, H // 2, W // 2, 64), dtype=torch.bfloat16, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     _lib.check(lib.witw_conv_first2_bf16_fwd(x.data_ptr(), packed_first.wf.data_ptr(), packed_first.bias.data_ptr(),
                                              packed_second.wpk.data_ptr(), packed_second.bias.data_ptr(), y.data_ptr(), B, C, H, W,
                                              int(circular), _stream()), 'witw_conv_first2_bf16_fwd')
     if prof is not None:
-        e1.record()
-        prof.append((('first2', True), 2.0 * (C + 64) * 64 * 9 * H * W * B, e0, e1))
-        if PROFILE_BY_KERNEL is not None:
-            PROFILE_BY_KERNEL.setdefault('conv_first2_bf16_kernel', []).append((prof[-1][1], e0, e1))
+        _prof_end(prof, ('first2', True), 2.0 * (C + 64) * 64 * 9 * H * W * B, kernel='conv_first2_bf16_kernel')
     return y
 
 
@@ -161,19 +230,13 @@ def conv_first2_bf16_train(x_nchw, packed_first, packed_second, circular=False):
     y = torch.empty((B, H // 2, W // 2, 64), dtype=torch.bfloat16, device=x.device)
     code = torch.empty((B, H // 2, W // 2, 64), dtype=torch.uint8, device=x.device)
     bits = torch.empty((B, H, W, 8), dtype=torch.uint8, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     _lib.check(lib.witw_conv_first2_bf16_fwd_train(x.data_ptr(), packed_first.wf.data_ptr(), packed_first.bias.data_ptr(),
                                                    packed_second.wpk.data_ptr(), packed_second.bias.data_ptr(), y.data_ptr(),
                                                    code.data_ptr(), bits.data_ptr(), B, C, H, W, int(circular), _stream()),
                'witw_conv_first2_bf16_fwd_train')
     if prof is not None:
-        e1.record()
-        prof.append((('first2', True), 2.0 * (C + 64) * 64 * 9 * H * W * B, e0, e1))
-        if PROFILE_BY_KERNEL is not None:
-            PROFILE_BY_KERNEL.setdefault('conv_first2_bf16_kernel<train>', []).append((prof[-1][1], e0, e1))
+        _prof_end(prof, ('first2', True), 2.0 * (C + 64) * 64 * 9 * H * W * B, kernel='conv_first2_bf16_kernel<train>')
     return y, code, bits
 
 
@@ -196,18 +259,13 @@ def conv3x3_bf16_dgrad_gatebits(dz_nhwc, packed_t, gate_bits, circular=False):
             and tuple(gate_bits.shape) == (B, H, W, packed_t.cout // 8)):
         raise _lib.WitwError('conv3x3_bf16_dgrad_gatebits: gate_bits must be uint8 [%d,%d,%d,%d]' % (B, H, W, packed_t.cout // 8))
     y = torch.empty((B, H, W, packed_t.cout), dtype=torch.bfloat16, device=dz_nhwc.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     _lib.check(lib.witw_conv3x3_bf16_fwd_gatebits(dz_nhwc.data_ptr(), packed_t.wpk.data_ptr(), packed_t.bias.data_ptr(), gate_bits.data_ptr(),
                                                   y.data_ptr(), B, H, W, C, packed_t.cout, int(circular), 0, _stream()),
                'witw_conv3x3_bf16_fwd_gatebits')
     if prof is not None:
-        e1.record()
-        prof.append((('bf16_wres', lib.witw_conv3x3_tile_n(packed_t.cout), 1, False), 2.0 * packed_t.cin * packed_t.cout * 9 * H * W * B, e0, e1))
-        if PROFILE_BY_KERNEL is not None:
-            PROFILE_BY_KERNEL.setdefault(last_kernel_variant(), []).append((prof[-1][1], e0, e1))
+        _prof_end(prof, lambda: ('bf16_wres', lib.witw_conv3x3_tile_n(packed_t.cout), 1, False),
+                  2.0 * packed_t.cin * packed_t.cout * 9 * H * W * B, kernel=True)
     return y
 
 
@@ -235,39 +293,15 @@ def conv3x3_fwd(x_nhwc, packed, stride_h=1, circular=False, relu=True, pool=Fals
     """x_nhwc [B,H,W,Cin_pad] -> NHWC [B,Hy,Wy,Cout] (or NCHW [B,Cout,Hy,Wy])."""
     lib = _lib.load()
     x = _dev_f32(x_nhwc, 'x')
-    B, H, W, C = x.shape
-    if C != packed.cin_pad:
-        raise _lib.WitwError('conv3x3_fwd: input has %d channels, packed weights expect %d' % (C, packed.cin_pad))
-    h_phys = H
-    if dilate_h:
-        if out_h is None or (out_h - 1) // 2 + 1 != H:
-            raise _lib.WitwError('conv3x3_fwd: dilate_h needs out_h with (out_h-1)//2+1 == %d physical rows' % H)
-        H = out_h          # logical (zero-interleaved) height
-    Ho = (H + 2 - 3) // stride_h + 1
-    # algorithmic rows of the launch's FLOP count: a zero-interleaved launch is the data gradient of a stride-(2,1) conv, whose
-    # multiply-adds are those of that conv's forward (one per real input row), not one per interleaved row
-    flop_rows = h_phys if dilate_h else Ho
-    Hy, Wy = (Ho // 2, W // 2) if pool else (Ho, W)
-    shape = (B, packed.cout, Hy, Wy) if out_nchw else (B, Hy, Wy, packed.cout)
-    y = torch.empty(shape, dtype=torch.float32, device=x.device)
-    if drop_scale is not None:
-        drop_scale = _dev_f32(drop_scale, 'drop_scale')
-        if tuple(drop_scale.shape) != (B, packed.cout):
-            raise _lib.WitwError('drop_scale must be [B,Cout]')
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if gate is not None:
-        gate = _dev_f32(gate, 'gate')
-        if tuple(gate.shape) != shape:
-            raise _lib.WitwError('gate must have the output shape %s, got %s' % (shape, tuple(gate.shape)))
+    B, _h, W, C = x.shape
+    H, flop_rows, y, drop_scale = _conv_fwd_setup('conv3x3_fwd', x, C, packed, stride_h, pool, out_nchw, dilate_h, out_h, drop_scale, gate)
     act = 2 if lrelu_slope is not None else int(bool(relu))
     if post_scale is not None:
         post_scale, post_shift = _dev_f32(post_scale, 'post_scale'), _dev_f32(post_shift, 'post_shift')
         if post_scale.numel() != packed.cout or post_shift.numel() != packed.cout:
             raise _lib.WitwError('post_scale/post_shift must have Cout entries')
-    code = torch.empty(shape, dtype=torch.uint8, device=x.device) if (pool and want_pool_code) else None
+    code = torch.empty(y.shape, dtype=torch.uint8, device=x.device) if (pool and want_pool_code) else None
+    prof = _prof_begin()
     if getattr(packed, 'taps4', False):
         if stride_h != 1 or circular or pool or out_nchw or dilate_h or drop_scale is not None:
             raise _lib.WitwError('conv3x3_fwd: a taps4-packed filter runs stride 1, zero padding, NHWC out, no pool / dropout')
@@ -285,14 +319,10 @@ def conv3x3_fwd(x_nhwc, packed, stride_h=1, circular=False, relu=True, pool=Fals
                                            packed.cout, stride_h, int(circular), act, float(lrelu_slope or 0.), int(pool),
                                            int(out_nchw), int(bool(dilate_h)), _stream()), 'witw_conv3x3_fwd_ex')
     if prof is not None:
-        e1.record()
-        variant = (lib.witw_conv3x3_tile_n(packed.cout), stride_h, bool(pool),
-                   lib.witw_conv3x3_workgroup_waves(B, H, W, packed.cout, stride_h))
-        if dilate_h:      # the zero-row-skipping instantiation (GEO = 2) is a launch class of its own: credited its real input rows
-            variant = variant + ('dil',)
-        prof.append((variant, 2.0 * packed.cin * packed.cout * (4 if getattr(packed, 'taps4', False) else 9) * flop_rows * W * B, e0, e1))
-        if PROFILE_BY_KERNEL is not None:
-            PROFILE_BY_KERNEL.setdefault(last_kernel_variant(), []).append((prof[-1][1], e0, e1))
+        # the zero-row-skipping instantiation (GEO = 2) is a launch class of its own ('dil'): credited its real input rows
+        _prof_end(prof, lambda: (lib.witw_conv3x3_tile_n(packed.cout), stride_h, bool(pool),
+                                 lib.witw_conv3x3_workgroup_waves(B, H, W, packed.cout, stride_h)) + (('dil',) if dilate_h else ()),
+                  2.0 * packed.cin * packed.cout * (4 if getattr(packed, 'taps4', False) else 9) * flop_rows * W * B, kernel=True)
     if want_pool_code:
         return y, code
     return y
@@ -321,17 +351,13 @@ def conv_taps4_s2d(x_nhwc, packed, valid_hw, lrelu_slope=None, post_scale=None, 
     B, H, W, C = x.shape
     vh, vw = valid_hw
     y = torch.empty((B, (vh + 1) // 2, (vw + 1) // 2, 4 * packed.cout), dtype=torch.float32, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     _lib.check(lib.witw_conv3x3_fwd_taps4_ex(x.data_ptr(), packed.wpk.data_ptr(), packed.bias.data_ptr(), None, _p(post_scale),
                                              _p(post_shift), y.data_ptr(), B, H, W, C, packed.cout, act, float(lrelu_slope or 0.),
                                              packed.tap_base, 1, 1, vh, vw, _stream()), 'witw_conv3x3_fwd_taps4_ex')
     if prof is not None:
-        e1.record()
-        prof.append(((lib.witw_conv3x3_tile_n(packed.cout), 1, False, lib.witw_conv3x3_workgroup_waves(B, H, W, packed.cout, 1)),
-                     2.0 * packed.cin * packed.cout * 4 * vh * vw * B, e0, e1))
+        _prof_end(prof, lambda: (lib.witw_conv3x3_tile_n(packed.cout), 1, False, lib.witw_conv3x3_workgroup_waves(B, H, W, packed.cout, 1)),
+                  2.0 * packed.cin * packed.cout * 4 * vh * vw * B)
     return y
 
 
@@ -351,15 +377,11 @@ def conv4x4s2_first(x_nchw, weight, bias, post_scale=None, post_shift=None, norm
         post_scale, post_shift = _dev_f32(post_scale, 'post_scale'), _dev_f32(post_shift, 'post_shift')
     vh, vw = (H - 4) // 2 + 1, (W - 4) // 2 + 1
     y = torch.empty((B, (vh + 1) // 2, (vw + 1) // 2, 256), dtype=torch.float32, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     _lib.check(lib.witw_conv4x4s2_first_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), _p(post_scale), _p(post_shift), y.data_ptr(),
                                             B, C, H, W, int(bool(normalize)), float(lrelu_slope), _stream()), 'witw_conv4x4s2_first_fwd')
     if prof is not None:
-        e1.record()
-        prof.append((('first4x4', 64, 2, False), 2.0 * C * 64 * 16 * vh * vw * B, e0, e1))
+        _prof_end(prof, ('first4x4', 64, 2, False), 2.0 * C * 64 * 16 * vh * vw * B)
     return y
 
 
@@ -376,10 +398,7 @@ def conv_taps4_splitk(x_mosaic, packed, n_images, g, valid_hw, lrelu_slope=None,
     S = ksplit or lib.witw_conv3x3_taps4_ksplit(Bm, H, W, C, packed.cout)
     ws = torch.empty((S, Bm, H, W, packed.cout), dtype=torch.float32, device=x.device)
     y = torch.empty((n_images, vh, vw, packed.cout), dtype=torch.float32, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     if S > 1:
         _lib.check(lib.witw_conv3x3_fwd_taps4_ex(x.data_ptr(), packed.wpk.data_ptr(), packed.bias.data_ptr(), None, None, None,
                                                  ws.data_ptr(), Bm, H, W, C, packed.cout, 0, 0., packed.tap_base, S, 0, 0, 0,
@@ -396,9 +415,8 @@ def conv_taps4_splitk(x_mosaic, packed, n_images, g, valid_hw, lrelu_slope=None,
         _lib.check(lib.witw_taps4_splitk_finish(ws.data_ptr(), 1, zero.data_ptr(), 0, 0., None, None, y.data_ptr(), n_images, g, h,
                                                 w, vh, vw, packed.cout, _stream()), 'witw_taps4_splitk_finish')
     if prof is not None:
-        e1.record()
-        prof.append(((lib.witw_conv3x3_tile_n(packed.cout), 1, False, lib.witw_conv3x3_workgroup_waves(Bm, H, W, packed.cout, 1)),
-                     2.0 * packed.cin * packed.cout * 4 * vh * vw * n_images, e0, e1))
+        _prof_end(prof, lambda: (lib.witw_conv3x3_tile_n(packed.cout), 1, False, lib.witw_conv3x3_workgroup_waves(Bm, H, W, packed.cout, 1)),
+                  2.0 * packed.cin * packed.cout * 4 * vh * vw * n_images)
     return y
 
 
@@ -528,10 +546,7 @@ def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=Fa
     dist = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device)
     score = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device) if want_score else None
     ws = torch.empty(lib.witw_match_workspace_floats(Bo, Bs), dtype=torch.float32, device=ov.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     if shift_mask is None:
         _lib.check(lib.witw_match_fwd(ov.data_ptr(), su.data_ptr(), Bo, Bs, We, ori.data_ptr(), dist.data_ptr(), _p(score),
                                       ws.data_ptr(), _stream()), 'witw_match_fwd')
@@ -539,8 +554,7 @@ def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=Fa
         _lib.check(lib.witw_match_fwd_masked(ov.data_ptr(), su.data_ptr(), Bo, Bs, We, ori.data_ptr(), dist.data_ptr(), _p(score),
                                              ws.data_ptr(), shift_mask.data_ptr(), _stream()), 'witw_match_fwd_masked')
     if prof is not None:      # the launch = two small norm kernels + the match kernel
-        e1.record()
-        prof.append((('match', We), 2.0 * 64 * (64 * We) * Bo * Bs, e0, e1))
+        _prof_end(prof, ('match', We), 2.0 * 64 * (64 * We) * Bo * Bs)
     if want_workspace:
         return ori, dist, score, ws
     return (ori, dist, score) if want_score else (ori, dist)
@@ -633,10 +647,7 @@ def match_fwd_dft(overhead_embed, surface_embed, spec_ov=None, spec_su=None, wan
     dist = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device)
     score = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device) if want_score else None
     ws = torch.empty(lib.witw_match_dft_workspace_floats(Bo, Bs), dtype=torch.float32, device=ov.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     gap = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device) if want_gap else None
     if want_gap:
         _lib.check(lib.witw_match_fwd_dft_gap(ov.data_ptr(), su.data_ptr(), spec_ov.data_ptr(), spec_su.data_ptr(), Bo, Bs, We,
@@ -646,8 +657,7 @@ def match_fwd_dft(overhead_embed, surface_embed, spec_ov=None, spec_su=None, wan
         _lib.check(lib.witw_match_fwd_dft(ov.data_ptr(), su.data_ptr(), spec_ov.data_ptr(), spec_su.data_ptr(), Bo, Bs, We,
                                           _p(ori), dist.data_ptr(), _p(score), ws.data_ptr(), _stream()), 'witw_match_fwd_dft')
     if prof is not None:      # FLOP of this form per pair: 33 frequencies x (2 rows x K=128 x 2 + 32 shifts x K=2 x 2) = 21,120 (algorithmic; the kernel runs 32 slots)
-        e1.record()
-        prof.append((('match_dft', We), 33.0 * (2 * 128 * 2 + 32 * 2 * 2) * Bo * Bs, e0, e1))
+        _prof_end(prof, ('match_dft', We), 33.0 * (2 * 128 * 2 + 32 * 2 * 2) * Bo * Bs)
     if want_gap:            # best - runner-up score per pair (how far the chosen shift is from a tie), then the workspace
         return ori, dist, gap, ws
     if want_workspace:      # window norms [Bo,64] then surface norms [Bs]: what match_pairs needs to re-score pairs of this pass
@@ -1358,25 +1368,17 @@ def bf16_wres(enable=None):
     return bool(_lib.load().witw_conv3x3_bf16_wres(-1 if enable is None else int(bool(enable))))
 
 
-class PackedConvBf16:
-    """bf16 filter packing of one 3x3 conv for the bf16 MFMA kernel + fp32 bias padded to the channel tile."""
+class PackedConvBf16(_Packed):
+    """bf16 filter packing of one 3x3 conv for the bf16 MFMA kernel + fp32 bias padded to the channel tile.
+    transpose_flip: the dgrad filter, built by the pack kernel itself."""
+    CPAD, DTYPE = 16, torch.bfloat16
 
     def __init__(self, weight, bias, transpose_flip=False, reuse=None):
         lib = _lib.load()
-        w = _dev_f32(weight.detach(), 'weight')
-        # transpose_flip: the dgrad filter w_t[ci][co][kh][kw] = w[co][ci][2-kh][2-kw], built by the pack kernel itself
-        self.cout, self.cin = (w.shape[1], w.shape[0]) if transpose_flip else (w.shape[0], w.shape[1])
-        self.cin_pad = (self.cin + 15) // 16 * 16
-        n_pk = lib.witw_conv3x3_bf16_packed_elems(self.cout, self.cin)
-        if reuse is not None and not (reuse.wpk.numel() == n_pk and reuse.wpk.device == w.device and reuse.cout == self.cout):
-            reuse = None
-        self.wpk = reuse.wpk if reuse is not None else torch.empty(n_pk, dtype=torch.bfloat16, device=w.device)
+        w, reuse = self._filter_buffer(weight, transpose_flip, reuse, lib.witw_conv3x3_bf16_packed_elems)
         _lib.check(lib.witw_conv3x3_bf16_pack_weights_ex(w.data_ptr(), self.wpk.data_ptr(), self.cout, self.cin,
                                                          int(bool(transpose_flip)), _stream()), 'witw_conv3x3_bf16_pack_weights_ex')
-        self.bias = reuse.bias if reuse is not None else \
-            torch.zeros(lib.witw_conv3x3_bias_floats(self.cout), dtype=torch.float32, device=w.device)
-        if bias is not None:
-            self.bias[:self.cout].copy_(bias.detach())
+        self._bias_buffer(reuse, bias)
 
     @classmethod
     def batch(cls, items):
@@ -1387,16 +1389,9 @@ class PackedConvBf16:
         lib = _lib.load()
         out, tab = [], []
         for weight, bias, transpose_flip, reuse in items:
-            w = _dev_f32(weight.detach(), 'weight')
             pk = cls.__new__(cls)
-            pk.cout, pk.cin = (w.shape[1], w.shape[0]) if transpose_flip else (w.shape[0], w.shape[1])
-            pk.cin_pad = (pk.cin + 15) // 16 * 16
-            n_pk = lib.witw_conv3x3_bf16_packed_elems(pk.cout, pk.cin)
-            if reuse is not None and not (reuse.wpk.numel() == n_pk and reuse.wpk.device == w.device and reuse.cout == pk.cout):
-                reuse = None
-            pk.wpk = reuse.wpk if reuse is not None else torch.empty(n_pk, dtype=torch.bfloat16, device=w.device)
-            pk.bias = reuse.bias if reuse is not None else \
-                torch.zeros(lib.witw_conv3x3_bias_floats(pk.cout), dtype=torch.float32, device=w.device)
+            w, reuse = pk._filter_buffer(weight, transpose_flip, reuse, lib.witw_conv3x3_bf16_packed_elems)
+            pk._bias_buffer(reuse)      # the launch below copies the biases too
             b = None if bias is None else _dev_f32(bias.detach(), 'bias')
             if b is not None and b.numel() != pk.cout:
                 raise _lib.WitwError('PackedConvBf16.batch: bias of %d elements for %d output channels' % (b.numel(), pk.cout))
@@ -1431,45 +1426,20 @@ def conv3x3_bf16_fwd(x_nhwc, packed, stride_h=1, circular=False, relu=True, pool
     lib = _lib.load()
     if not (x_nhwc.is_cuda and x_nhwc.dtype == torch.bfloat16 and x_nhwc.is_contiguous()):
         raise _lib.WitwError('conv3x3_bf16_fwd: x must be a contiguous bfloat16 GPU tensor')
-    B, H, W, C = x_nhwc.shape
-    if C != packed.cin_pad:
-        raise _lib.WitwError('conv3x3_bf16_fwd: input has %d channels, packed weights expect %d' % (C, packed.cin_pad))
-    if dilate_h:
-        if out_h is None or (out_h - 1) // 2 + 1 != H:
-            raise _lib.WitwError('conv3x3_bf16_fwd: dilate_h needs out_h with (out_h-1)//2+1 == %d physical rows' % H)
-        h_phys, H = H, out_h          # logical (zero-interleaved) height
-    Ho = (H + 2 - 3) // stride_h + 1
-    Hy, Wy = (Ho // 2, W // 2) if pool else (Ho, W)
-    if out_nchw_f32:
-        y = torch.empty((B, packed.cout, Hy, Wy), dtype=torch.float32, device=x_nhwc.device)
-    else:
-        if packed.cout % 16:
-            raise _lib.WitwError('conv3x3_bf16_fwd: a bf16 NHWC output needs Cout %% 16 == 0 (next layer\'s K chunk)')
-        y = torch.empty((B, Hy, Wy, packed.cout), dtype=torch.bfloat16, device=x_nhwc.device)
-    if drop_scale is not None:
-        drop_scale = _dev_f32(drop_scale, 'drop_scale')
-        if tuple(drop_scale.shape) != (B, packed.cout):
-            raise _lib.WitwError('drop_scale must be [B,Cout]')
-    if gate is not None:
-        if not (gate.is_cuda and gate.dtype == torch.bfloat16 and gate.is_contiguous() and tuple(gate.shape) == tuple(y.shape)):
-            raise _lib.WitwError('gate must be a contiguous bfloat16 GPU tensor with the output shape %s' % (tuple(y.shape),))
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    code = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if (pool and want_pool_code) else None
+    B, _h, W, C = x_nhwc.shape
+    H, flop_rows, y, drop_scale = _conv_fwd_setup('conv3x3_bf16_fwd', x_nhwc, C, packed, stride_h, pool, out_nchw_f32, dilate_h, out_h,
+                                                  drop_scale, gate)
+    code = torch.empty(y.shape, dtype=torch.uint8, device=y.device) if (pool and want_pool_code) else None
+    prof = _prof_begin()
     _lib.check(lib.witw_conv3x3_bf16_fwd_ex(x_nhwc.data_ptr(), packed.wpk.data_ptr(), packed.bias.data_ptr(), _p(drop_scale),
                                             _p(gate), y.data_ptr(), _p(code), B, H, W, C, packed.cout, stride_h, int(circular),
                                             int(relu), int(pool), int(out_nchw_f32), int(bool(dilate_h)), _stream()),
                'witw_conv3x3_bf16_fwd_ex')
     if prof is not None:
-        e1.record()
         # the 64-input-channel layer runs on its own kernel (csrc/conv3x3_bf16_wres.hip): its own launch class
-        kind = 'bf16_wres' if last_kernel_variant().startswith('conv3x3_bf16_wres_kernel') else 'bf16'
-        prof.append(((kind, lib.witw_conv3x3_tile_n(packed.cout), stride_h, bool(pool)) + (('dil',) if dilate_h else ()),
-                     2.0 * packed.cin * packed.cout * 9 * (h_phys if dilate_h else Ho) * W * B, e0, e1))      # dilated: see conv3x3_fwd
-        if PROFILE_BY_KERNEL is not None:
-            PROFILE_BY_KERNEL.setdefault(last_kernel_variant(), []).append((prof[-1][1], e0, e1))
+        _prof_end(prof, lambda: ('bf16_wres' if last_kernel_variant().startswith('conv3x3_bf16_wres_kernel') else 'bf16',
+                                 lib.witw_conv3x3_tile_n(packed.cout), stride_h, bool(pool)) + (('dil',) if dilate_h else ()),
+                  2.0 * packed.cin * packed.cout * 9 * flop_rows * W * B, kernel=True)
     if want_pool_code:
         return y, code
     return y
@@ -1519,10 +1489,7 @@ def conv3x3_wgrad_bf16(x_nhwc, dz_nhwc, cin_real, stride_h=1, circular=False, wa
     if tuple(dz_nhwc.shape[:3]) != (B, Ho, W):
         raise _lib.WitwError('conv3x3_wgrad_bf16: dz %s does not match x %s (stride %d)' % (tuple(dz_nhwc.shape),
                                                                                           tuple(x_nhwc.shape), stride_h))
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     if out is not None:
         dw, db = out
         if not (dw.is_contiguous() and tuple(dw.shape) == (Cout, cin_real, 3, 3) and dw.dtype == torch.float32 and dw.is_cuda
@@ -1547,31 +1514,22 @@ def conv3x3_wgrad_bf16(x_nhwc, dz_nhwc, cin_real, stride_h=1, circular=False, wa
                                                ws.data_ptr(), B, H, W, Cin, cin_real, Cout, stride_h, int(circular), 0, _stream()),
                    'witw_conv3x3_wgrad_bf16')
     if prof is not None:
-        e1.record()
-        prof.append((('wgrad_bf16', stride_h), 2.0 * cin_real * Cout * 9 * Ho * W * B, e0, e1))
+        _prof_end(prof, ('wgrad_bf16', stride_h), 2.0 * cin_real * Cout * 9 * Ho * W * B)
     return dw, db
 
 
 # ----------------------------------------------------------------------------- fp16x3: fp32-grade inference on the fp16 MFMA
-class PackedConvF16x3:
+class PackedConvF16x3(_Packed):
     """fp16 hi / lo filter packing of one 3x3 conv for the fp16x3 kernel (19 slots per 8-channel chunk) + fp32 bias.
     transpose_flip packs the dgrad filter; reuse = a previous packing of the same layer whose buffers are overwritten."""
+    DTYPE = torch.float16
 
     def __init__(self, weight, bias, transpose_flip=False, reuse=None):
         lib = _lib.load()
-        w = _dev_f32(weight.detach(), 'weight')
-        self.cout, self.cin = (w.shape[1], w.shape[0]) if transpose_flip else (w.shape[0], w.shape[1])
-        self.cin_pad = (self.cin + 7) // 8 * 8
-        n_pk = lib.witw_conv3x3_f16x3_packed_elems(self.cout, self.cin)
-        if reuse is not None and not (reuse.wpk.numel() == n_pk and reuse.wpk.device == w.device and reuse.cout == self.cout):
-            reuse = None
-        self.wpk = reuse.wpk if reuse is not None else torch.empty(n_pk, dtype=torch.float16, device=w.device)
+        w, reuse = self._filter_buffer(weight, transpose_flip, reuse, lib.witw_conv3x3_f16x3_packed_elems)
         _lib.check(lib.witw_conv3x3_f16x3_pack_weights_ex(w.data_ptr(), self.wpk.data_ptr(), self.cout, self.cin,
                                                           int(bool(transpose_flip)), _stream()), 'witw_conv3x3_f16x3_pack_weights_ex')
-        self.bias = reuse.bias if reuse is not None else \
-            torch.zeros(lib.witw_conv3x3_bias_floats(self.cout), dtype=torch.float32, device=w.device)
-        if bias is not None:
-            self.bias[:self.cout].copy_(bias.detach())
+        self._bias_buffer(reuse, bias)
 
 
 def nchw_to_split_f16(x, cpad=8):
@@ -1629,40 +1587,19 @@ def conv3x3_f16x3_fwd(x_split, packed, stride_h=1, circular=False, relu=True, po
         raise _lib.WitwError('conv3x3_f16x3_fwd: x must be a contiguous float16 GPU tensor shaped [B,H,W,C/8,2,8]')
     B, H, W, C8 = x_split.shape[:4]
     C = C8 * 8
-    if C != packed.cin_pad:
-        raise _lib.WitwError('conv3x3_f16x3_fwd: input has %d channels, packed weights expect %d' % (C, packed.cin_pad))
-    if dilate_h:
-        if out_h is None or (out_h - 1) // 2 + 1 != H:
-            raise _lib.WitwError('conv3x3_f16x3_fwd: dilate_h needs out_h with (out_h-1)//2+1 == %d physical rows' % H)
-        h_phys, H = H, out_h
-    Ho = (H + 2 - 3) // stride_h + 1
-    Hy, Wy = (Ho // 2, W // 2) if pool else (Ho, W)
-    if out_nchw_f32:
-        y = torch.empty((B, packed.cout, Hy, Wy), dtype=torch.float32, device=x_split.device)
-    else:
-        if packed.cout % 8:
-            raise _lib.WitwError('conv3x3_f16x3_fwd: a split-fp16 output needs Cout %% 8 == 0')
-        y = torch.empty((B, Hy, Wy, packed.cout // 8, 2, 8), dtype=torch.float16, device=x_split.device)
-    if drop_scale is not None:
-        drop_scale = _dev_f32(drop_scale, 'drop_scale')
-        if tuple(drop_scale.shape) != (B, packed.cout):
-            raise _lib.WitwError('drop_scale must be [B,Cout]')
-    if gate is not None and not (_is_split(gate) and tuple(gate.shape) == tuple(y.shape)):
-        raise _lib.WitwError('gate must be a split-fp16 GPU tensor with the output shape %s' % (tuple(y.shape),))
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    H, flop_rows, y, drop_scale = _conv_fwd_setup('conv3x3_f16x3_fwd', x_split, C, packed, stride_h, pool, out_nchw_f32, dilate_h, out_h,
+                                                  drop_scale, gate)
+    Hy, Wy = y.shape[2:] if out_nchw_f32 else y.shape[1:3]
     code = torch.empty((B, Hy, Wy, packed.cout), dtype=torch.uint8, device=y.device) if (pool and want_pool_code) else None
+    prof = _prof_begin()
     _lib.check(lib.witw_conv3x3_f16x3_fwd_ex(x_split.data_ptr(), packed.wpk.data_ptr(), packed.bias.data_ptr(), _p(drop_scale),
                                              _p(gate), y.data_ptr(), _p(code), _f16x3_flag(x_split.device).data_ptr(), B, H, W, C,
                                              packed.cout, stride_h, int(circular), int(relu), int(pool), int(out_nchw_f32),
                                              int(bool(dilate_h)), _stream()),
                'witw_conv3x3_f16x3_fwd_ex')
     if prof is not None:
-        e1.record()
-        prof.append((('f16x3', lib.witw_conv3x3_tile_n(packed.cout), stride_h, bool(pool)) + (('dil',) if dilate_h else ()),
-                     2.0 * packed.cin * packed.cout * 9 * (h_phys if dilate_h else Ho) * W * B, e0, e1))      # dilated: see conv3x3_fwd
+        _prof_end(prof, lambda: ('f16x3', lib.witw_conv3x3_tile_n(packed.cout), stride_h, bool(pool)) + (('dil',) if dilate_h else ()),
+                  2.0 * packed.cin * packed.cout * 9 * flop_rows * W * B)
     if want_pool_code:
         return y, code
     return y
@@ -1704,10 +1641,7 @@ def conv3x3_wgrad_f16x3(x_split, dz_split, cin_real, stride_h=1, circular=False,
     if tuple(dz_split.shape[:3]) != (B, Ho, W):
         raise _lib.WitwError('conv3x3_wgrad_f16x3: dz %s does not match x %s (stride %d)' % (tuple(dz_split.shape),
                                                                                            tuple(x_split.shape), stride_h))
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    prof = _prof_begin()
     x_oct, dz_oct = split_f16_to_octet(x_split), split_f16_to_octet(dz_split)
     dw = torch.empty((Cout, cin_real, 3, 3), dtype=torch.float32, device=x_split.device)
     db = torch.empty((Cout,), dtype=torch.float32, device=x_split.device) if want_bias else None
@@ -1717,8 +1651,7 @@ def conv3x3_wgrad_f16x3(x_split, dz_split, cin_real, stride_h=1, circular=False,
                                             ws.data_ptr(), B, H, W, Cin, cin_real, Cout, stride_h, int(circular), 0, _stream()),
                'witw_conv3x3_wgrad_f16x3')
     if prof is not None:
-        e1.record()
-        prof.append((('wgrad_f16x3', stride_h), 2.0 * cin_real * Cout * 9 * Ho * W * B, e0, e1))
+        _prof_end(prof, ('wgrad_f16x3', stride_h), 2.0 * cin_real * Cout * 9 * Ho * W * B)
     return dw, db
 
 
