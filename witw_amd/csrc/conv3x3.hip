@@ -140,26 +140,21 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
     }
     const unsigned gwoff = (unsigned)tid * 16u;
     f32x4 rin[NIN], rw[NWT];
-    auto load_stage = [&](int kc) {
-#pragma unroll
-        for (int i = 0; i < NIN; ++i)
-            rin[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rs, gin[i], (unsigned)kc * 32u, 0));
-        const unsigned wbase = (unsigned)kc * W_F4 * 16u;
-#pragma unroll
-        for (int i = 0; i < NWT; ++i)
-            rw[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rs, gwoff, wbase + (unsigned)i * (NTHREADS * 16u), 0));
+    // staging of a K chunk, one instruction at a time (i < NIN: input tile, then the filter slab): global -> registers -> LDS
+    auto load_one = [&](int kc, int i) {
+        if (i < NIN) rin[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rs, gin[i], (unsigned)kc * 32u, 0));
+        else rw[i - NIN] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                 w_rs, gwoff, (unsigned)kc * W_F4 * 16u + (unsigned)(i - NIN) * (NTHREADS * 16u), 0));
     };
-    auto store_stage = [&](int buf) {
+    auto store_one = [&](int buf, int i) {
         f32x4* in_s = smem + buf * STAGE_F4;
-        f32x4* w_s = in_s + IN_F4;
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) {
+        if (i < NIN) {
             const int s = tid + i * NTHREADS;
             f32x4* dst = (NIN * NTHREADS == IN_F4 || s < IN_F4) ? in_s + (s & 1) * (IH * IW) + (s >> 1) : smem + 2 * STAGE_F4;
             *dst = rin[i];
+        } else {
+            in_s[IN_F4 + tid + (i - NIN) * NTHREADS] = rw[i - NIN];
         }
-#pragma unroll
-        for (int i = 0; i < NWT; ++i) w_s[tid + i * NTHREADS] = rw[i];
     };
 
     // wave -> (row pair wm, channel half wn); step s = (kw = s >> 1, column half ct = s & 1), 6 steps per K chunk
@@ -176,99 +171,102 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
 
     // fa: input rows d0..d3 of a step, transformed in place into V0..V3 late in the step before; fb: filter slices U0..U3 of a kw
     f32x4 fa[2][4], fb[2][4];
-    auto read_a = [&](int set, const f32x4* in_s, int s) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa[set][i] = in_s[abase + i * IW + 32 * (s & 1) + (s >> 1)];
-    };
-    auto read_b = [&](int set, const f32x4* w_s, int kw) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) fb[set][t] = w_s[(kw * 4 + t) * 2 * WTN + wbase];
-    };
-    auto transform = [&](int set) {      // 16 single v_add_f32 / v_sub_f32 (packed f32 VALU beside MFMAs costs more)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float d0 = fa[set][0][j], d1 = fa[set][1][j], d2 = fa[set][2][j], d3 = fa[set][3][j];
+    auto read_a = [&](int set, const f32x4* in_s, int s, int i) { fa[set][i] = in_s[abase + i * IW + 32 * (s & 1) + (s >> 1)]; };
+    auto read_b = [&](int set, const f32x4* w_s, int kw, int t) { fb[set][t] = w_s[(kw * 4 + t) * 2 * WTN + wbase]; };
+    // the transform in 8 pairs of single v_add_f32 / v_sub_f32 (packed f32 VALU beside MFMAs costs more): pair k = channel k >> 1,
+    // (V0, V3) then (V1, V2)
+    auto transform2 = [&](int set, int k) {
+        const int j = k >> 1;
+        const float d0 = fa[set][0][j], d1 = fa[set][1][j], d2 = fa[set][2][j], d3 = fa[set][3][j];
+        if ((k & 1) == 0) {
             fa[set][0][j] = d0 - d2;
+            fa[set][3][j] = d1 - d3;
+        } else {
             fa[set][1][j] = d1 + d2;
             fa[set][2][j] = d2 - d1;
-            fa[set][3][j] = d1 - d3;
         }
     };
-    auto mfma_step = [&](int set, int bset, int ct) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                acc[t][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][t][j], fb[bset][t][j], acc[t][ct], 0, 0, 0);
+    auto mfma_one = [&](int set, int bset, int ct, int i) {      // MFMA i of a step: channel i >> 2, product t = i & 3
+        const int j = i >> 2, t = i & 3;
+        acc[t][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][t][j], fb[bset][t][j], acc[t][ct], 0, 0, 0);
     };
 
-    load_stage(0);
-    store_stage(0);
+#pragma unroll
+    for (int i = 0; i < NIN + NWT; ++i) load_one(0, i);
+#pragma unroll
+    for (int i = 0; i < NIN + NWT; ++i) store_one(0, i);
     __syncthreads();
-    read_a(0, smem, 0);
-    read_b(0, smem + IN_F4, 0);
-    transform(0);
+    // filter slices before input rows, pinned: the transform's wait for the rows then leaves no read in flight at the loop's head,
+    // where a read still pending from here would turn the first MFMA's counted wait into a full drain on every trip
+#pragma unroll
+    for (int i = 0; i < 4; ++i) read_b(0, smem + IN_F4, 0, i);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) read_a(0, smem, 0, i);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) transform2(0, k);
 
-    // Issue order per step (16 MFMAs): each LDS / global instruction alone behind an MFMA, the next step's fragment reads
-    // first; the transform of those fragments follows the step's MFMAs in program order.
-#define SG_STEP(NR, MASK, NX)                                           \
-    do {                                                                \
-        _Pragma("unroll") for (int i_ = 0; i_ < (NR); ++i_) {           \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          \
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);          \
-        }                                                               \
-        _Pragma("unroll") for (int i_ = 0; i_ < (NX); ++i_) {           \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          \
-            __builtin_amdgcn_sched_group_barrier(MASK, 1, 0);           \
-        }                                                               \
-        _Pragma("unroll") for (int i_ = 0; i_ < 16 - (NR) - (NX); ++i_) \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          \
-    } while (0)
-    static_assert(16 - 4 - (NIN + NWT) >= 0, "step too short to hide the staging instructions");
+    // A step is 16 MFMAs on fragment set `set` and filter set `bset`. Behind MFMA i stands what mem(i) issues -- the next step's
+    // fragment reads first, input rows 0..3 before filter slices, then a staging instruction where due, one instruction each --
+    // and, from MFMA 8 on, one pair of the transform of those rows into set ^ 1: at least 4 MFMAs behind the last of their reads,
+    // a whole step ahead of the MFMAs that take them. The order is pinned gap by gap (sched_barrier): left to itself the scheduler
+    // sinks every v_add / v_sub to the MFMA it feeds and drags the raw rows' reads and full LDS drains there with it; named as
+    // sched_group_barrier groups the greedy solver scatters reads and transforms over the step.
+    auto step = [&](int set, int bset, int ct, auto&& mem, bool barrier_mid) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            mfma_one(set, bset, ct, i);
+            mem(i);
+            if (i >= 8) transform2(set ^ 1, i - 8);
+            __builtin_amdgcn_sched_barrier(0);
+            if (barrier_mid && i == 7) {
+                __syncthreads();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    static_assert(16 - 6 - (NIN + NWT) >= 0, "step too short to hide the staging instructions");
 
     // B slices: kw 0 and 2 in set 0, kw 1 in set 1 (kw 2 read in step 2, behind the last use of kw 0); the next chunk's kw 0
     // arrives in set 1 during step 5, behind the chunk's single barrier, and is moved to set 0. Next chunk: loads under step 0,
-    // LDS writes under step 3.
+    // LDS writes under step 3. A transform waits for its four rows only, and in every step a younger LDS instruction follows the
+    // row reads (filter slices in steps 0, 1, 2 and 5 -- hence kw 1 in two halves --, the staging writes in step 3), so the wait
+    // is a counted one. Step 4 has none to offer: there the chunk's barrier, whose drain is the loop's only full one, stands
+    // between the reads (MFMAs 0..3) and the transform (MFMAs 8..15). It still separates the last read of this stage (step 4)
+    // from its next overwrite (step 3 of the next chunk), and the writes of the next stage (step 3) from their first read (step 5).
     for (int kc = 0; kc < nkc; ++kc) {
         const int cur = kc & 1;
         const int kn = (kc + 1 < nkc) ? kc + 1 : kc;   // last chunk restages itself (never read)
         const f32x4* in_s = smem + cur * STAGE_F4;
         const f32x4* w_s = in_s + IN_F4;
         const f32x4* in_n = smem + (cur ^ 1) * STAGE_F4;
-        read_a(1, in_s, 1);
-        load_stage(kn);
-        mfma_step(0, 0, 0);
-        transform(1);
-        SG_STEP(4, 0x020, NIN + NWT);
-        read_a(0, in_s, 2);
-        read_b(1, w_s, 1);
-        mfma_step(1, 0, 1);
-        transform(0);
-        SG_STEP(8, 0x020, 0);
-        read_a(1, in_s, 3);
-        read_b(0, w_s, 2);
-        mfma_step(0, 1, 0);
-        transform(1);
-        SG_STEP(8, 0x020, 0);
-        read_a(0, in_s, 4);
-        store_stage(cur ^ 1);
-        mfma_step(1, 1, 1);
-        transform(0);
-        SG_STEP(4, 0x200, NIN + NWT);
-        read_a(1, in_s, 5);
-        mfma_step(0, 0, 0);
-        transform(1);
-        SG_STEP(4, 0x020, 0);
-        __syncthreads();
-        read_a(0, in_n, 0);
-        read_b(1, in_n + IN_F4, 0);
-        mfma_step(1, 0, 1);
-        transform(0);
-        SG_STEP(8, 0x020, 0);
+        step(0, 0, 0, [&](int i) {
+            if (i < 4) read_a(1, in_s, 1, i);
+            else if (i < 6) read_b(1, w_s, 1, i - 4);
+            else if (i < 6 + NIN + NWT) load_one(kn, i - 6);
+        }, false);
+        step(1, 0, 1, [&](int i) {
+            if (i < 4) read_a(0, in_s, 2, i);
+            else if (i < 6) read_b(1, w_s, 1, i - 2);
+        }, false);
+        step(0, 1, 0, [&](int i) {
+            if (i < 4) read_a(1, in_s, 3, i);
+            else if (i < 8) read_b(0, w_s, 2, i - 4);
+        }, false);
+        step(1, 1, 1, [&](int i) {
+            if (i < 4) read_a(0, in_s, 4, i);
+            else if (i < 4 + NIN + NWT) store_one(cur ^ 1, i - 4);
+        }, false);
+        step(0, 0, 0, [&](int i) {
+            if (i < 4) read_a(1, in_s, 5, i);
+        }, true);
+        step(1, 0, 1, [&](int i) {
+            if (i < 4) read_a(0, in_n, 0, i);
+            else if (i < 8) read_b(1, in_n + IN_F4, 0, i - 4);
+        }, false);
 #pragma unroll
         for (int t = 0; t < 4; ++t) fb[0][t] = fb[1][t];
     }
-#undef SG_STEP
 
     // ---- epilogue: output transform, bias, dropout scale, ReLU, optional 2x2 max pool (the wave's own row pair), 16-byte stores
     // through a wave-private 4 KB LDS slab (32 pixels x 32 channels; the staging buffers are dead behind the loop's last barrier)
