@@ -172,6 +172,13 @@ int witw_match_fwd_dft(const float* ov, const float* su, const float* spec_ov, c
 /* the same, also writing gap [Bo,Bs] = best score - runner-up score over the 64 shifts (distance of the arg-max from a tie) */
 int witw_match_fwd_dft_gap(const float* ov, const float* su, const float* spec_ov, const float* spec_su, int Bo, int Bs, int We,
                            long long* orientation, float* distance, float* score, float* gap, float* workspace, void* stream);
+/* witw_match_fwd_dft / _gap under the orientation prior of witw_match_fwd_masked (model/cvig_fov.py:297-315 restricted per query;
+ * retrieval loop :547-552): shift_mask [Bs] (device, NOT NULL here) holds one 64-bit word per surface embedding, bit k set = shift k
+ * may be chosen, 0 = no prior = all 64 bits. orientation = the first maximum over the allowed shifts, distance / score at that
+ * shift. gap may be NULL; otherwise gap = best score - second best ALLOWED score, +inf where the word allows a single shift. */
+int witw_match_fwd_dft_masked(const float* ov, const float* su, const float* spec_ov, const float* spec_su, int Bo, int Bs, int We,
+                              long long* orientation, float* distance, float* score, float* gap /* may be NULL */, float* workspace,
+                              const unsigned long long* shift_mask, void* stream);
 /* backward of witw_match_fwd (orientation is a constant of the graph): grad_distance [Bo,Bs] ->
  * grad_ov [Bo,16,4,64] and/or grad_su [Bs,16,4,We]; orientation/score/workspace as left by the forward. scratch: NULL,
  * or witw_match_bwd_scratch_floats(Bo,Bs,We) floats that let the surface gradient split the overheads over several
@@ -216,6 +223,15 @@ int witw_rank_count_band(const float* distance, const float* threshold, float ep
  * adds 1 to counts[pair_s[i]] for every pair with exact distance <= threshold[pair_s[i]]. */
 int witw_match_pairs_count(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o, const int* pair_s,
                            const int* n_pairs_dev, int capacity, int Bo, int Bs, int We, const float* threshold, int* counts, void* stream);
+/* witw_match_pairs / witw_match_pairs_count under shift masks (model/cvig_fov.py:547-552 with the orientation prior): shift_mask
+ * [Bs] (device, NOT NULL here) is indexed by pair_s[i]; orientation / distance / score are bit-identical to the entries
+ * witw_match_fwd_masked writes for those pairs. */
+int witw_match_pairs_masked(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o, const int* pair_s,
+                            int n_pairs, int Bo, int Bs, int We, long long* orientation, float* distance, float* score,
+                            const unsigned long long* shift_mask, void* stream);
+int witw_match_pairs_count_masked(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o,
+                                  const int* pair_s, const int* n_pairs_dev, int capacity, int Bo, int Bs, int We,
+                                  const float* threshold, int* counts, const unsigned long long* shift_mask, void* stream);
 /* which kernel witw_match_pairs runs: 1 = v_fma_f32 chain on the vector pipe, one lane per shift (default, round 6); 0 = the
  * v_mfma_f32_32x32x2_f32 chain of rounds 4-5. Same bits (the f32 MFMA accumulates as a fused-multiply-add chain in k order).
  * impl < 0 only queries; returns the previous setting. */

@@ -26,7 +26,7 @@ def nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous()
 
 
-N_KINDS = 20
+N_KINDS = 21
 
 
 def run(budget=120.0, seed=0, rounds=None, kinds=None):
@@ -59,9 +59,51 @@ def run(budget=120.0, seed=0, rounds=None, kinds=None):
             while time.time() - t0 < budget:
                 yield int(rng.choice(kinds))
 
+    def masked_spectral(case):
+        # kind 20: the spectral match under random shift masks (witw_match_fwd_dft_masked) against the fp64 sum: every orientation
+        # allowed; equal to the fp64 arg-max over the allowed shifts wherever its two best allowed scores are further apart than
+        # 4e-6 |ov||su| (the fp32 rounding of a score, twice over); distance there to 2e-5 as the kinds above. Its shapes and words
+        # come from a generator of its own, so that the cases of the other kinds are the ones they were before this kind existed.
+        g = np.random.Generator(np.random.Philox(key=[seed, case]))
+        tg = torch.Generator().manual_seed(int(g.integers(0, 2 ** 31)))
+        bo, bs, we = int(g.integers(1, 80)), int(g.integers(1, 150)), int(g.integers(1, 65))
+        ov, su = torch.randn(bo, 16, 4, 64, generator=tg), torch.randn(bs, 16, 4, we, generator=tg)
+        words = g.integers(-2 ** 63, 2 ** 63, size=bs, dtype=np.int64)
+        words[g.random(bs) < 0.2] = 0                                            # no prior
+        narrow = g.random(bs) < 0.3                                              # a single allowed shift
+        words[narrow] = (np.uint64(1) << g.integers(0, 64, size=int(narrow.sum()), dtype=np.uint64)).view(np.int64)
+        mask = torch.from_numpy(words)
+        bits = ((words.view(np.uint64)[:, None] >> np.arange(64, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+        bits[words == 0] = True
+        sc = O.correlation_scores(ov.double(), su.double()).masked_fill(~torch.from_numpy(bits)[None], float('-inf'))
+        top2 = sc.topk(2, -1)
+        scale = ov.double().reshape(bo, -1).norm(dim=1)[:, None] * su.double().reshape(bs, -1).norm(dim=1)[None, :]
+        clear = (top2.values[..., 0] - top2.values[..., 1]) > 4e-6 * scale
+        ori_r = top2.indices[..., 0]
+        col = (ov.double() ** 2).sum(dim=(1, 2))
+        col2 = torch.cat((col, col[:, :we - 1]), dim=1) if we > 1 else col
+        wn = torch.gather(col2.unfold(1, we, 1)[:, :64].sum(-1), 1, ori_r).sqrt()
+        d_r = 2 * (1 - top2.values[..., 0] / (wn * su.double().reshape(bs, -1).norm(dim=1)[None, :]))
+        ori, d = ops.match_fwd_dft(ov.to(dev), su.to(dev), shift_mask=mask.to(dev))[:2]
+        ori = ori.cpu()
+        if not bool(torch.from_numpy(bits)[None].expand(bo, -1, -1).gather(2, ori[..., None]).all()):
+            fails.append(('masked_dft_forbidden_shift', (bo, bs, we), 0, 0))
+            print('FAIL masked spectral match: a forbidden shift', (bo, bs, we), flush=True)
+        if not torch.equal(ori[clear], ori_r[clear]):
+            fails.append(('masked_dft_ori', (bo, bs, we), 0, 0))
+            print('FAIL masked spectral match orientation', (bo, bs, we), flush=True)
+        check('masked_dft_dist', (bo, bs, we), d.cpu().double()[clear], d_r[clear], 2e-5)
+
     for kind in draw_kinds():
         n += 1
         ran[kind] += 1
+        if kind == 20:
+            try:
+                masked_spectral(n)
+            except Exception as e:
+                fails.append(('exception', 'masked_spectral', str(e)[:200], kind))
+                print('EXC kind %d: %s' % (kind, str(e)[:300]), flush=True)
+            continue
         B = int(rng.integers(1, 5))
         H = int(rng.integers(1, 40))
         W = int(rng.integers(1, 140))

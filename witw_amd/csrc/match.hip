@@ -991,11 +991,15 @@ __global__ __launch_bounds__(256) void rank_count_thresh_kernel(const float* __r
 // surface (31/32 of the matrix work is redundant: the price of bit-identity; the callers re-score a few pairs per million).
 // Used by the index-exact spectral retrieval (cvig_fov.retrieve(method='dft')) for the pairs whose spectral distance sits
 // within fp32 rounding of a decision boundary.
+// MASKED (witw_match_pairs_masked): the arg-max of the masked all-pairs kernels -- a lane whose shift the word mask[pair_s[i]]
+// forbids enters with -inf and its index + 64, the winner is taken & 63 -- bit-identical to witw_match_fwd_masked's entries.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void match_pairs_kernel(const float* __restrict__ ov, const float* __restrict__ su,
                                                           const float* __restrict__ wn, const float* __restrict__ sn,
                                                           const int* __restrict__ pair_o, const int* __restrict__ pair_s,
                                                           int n_pairs, int We, long long* __restrict__ orientation,
-                                                          float* __restrict__ distance, float* __restrict__ score) {
+                                                          float* __restrict__ distance, float* __restrict__ score,
+                                                          const unsigned long long* __restrict__ mask) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pr = blockIdx.x * 4 + wave;
     if (pr >= n_pairs) return;                       // wave-uniform; the kernel has no barrier
@@ -1019,14 +1023,21 @@ __global__ __launch_bounds__(256) void match_pairs_kernel(const float* __restric
     }
     float v = acc0[0];
     int idx = l31;
-    const float v1 = acc1[0];
-    if (v1 > v) { v = v1; idx = 32 + l31; }
+    float v1 = acc1[0];
+    int i1 = 32 + l31;
+    if (MASKED) {
+        const unsigned long long m = load_shift_mask(mask, s, s + 1);
+        mask_shift(m, v, idx);
+        mask_shift(m, v1, i1);
+    }
+    if (v1 > v || (MASKED && v1 == v && i1 < idx)) { v = v1; idx = i1; }
 #pragma unroll
     for (int d = 1; d < 32; d <<= 1) {
         const float vo = __shfl_xor(v, d, 64);
         const int io = __shfl_xor(idx, d, 64);
         if (vo > v || (vo == v && io < idx)) { v = vo; idx = io; }
     }
+    if (MASKED) idx &= 63;
     if (lane == 0) {
         if (orientation) orientation[pr] = idx;
         if (score) score[pr] = v;
@@ -1042,14 +1053,15 @@ __global__ __launch_bounds__(256) void match_pairs_kernel(const float* __restric
 // ~43 k pairs: 11 ms of its 233). The overhead row is written twice over into a wave-private LDS strip (128 floats, double
 // buffered by row parity; a wave's LDS operations execute in order, so no barrier) and lane j reads strip[k + j] -- consecutive
 // lanes, consecutive banks; the multiplier is wave-uniform (scalar loads). Arg-max and distance: the MFMA kernel's own code.
-template <int WE>      // WE > 0: the embedding width as a constant (64: retrieval at fov 360); 0: any width
+// MASKED: as in match_pairs_kernel.
+template <int WE, bool MASKED>      // WE > 0: the embedding width as a constant (64: retrieval at fov 360); 0: any width
 __global__ __launch_bounds__(256) void match_pairs_valu_kernel(const float* __restrict__ ov, const float* __restrict__ su,
                                                                const float* __restrict__ wn, const float* __restrict__ sn,
                                                                const int* __restrict__ pair_o, const int* __restrict__ pair_s,
                                                                int n_pairs, int We_rt, long long* __restrict__ orientation,
                                                                float* __restrict__ distance, float* __restrict__ score,
                                                                const int* __restrict__ n_dev, const float* __restrict__ thr,
-                                                               int* __restrict__ counts) {
+                                                               int* __restrict__ counts, const unsigned long long* __restrict__ mask) {
     __shared__ float strip[4][2][128];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int pr = blockIdx.x * 4 + wave;
@@ -1086,14 +1098,21 @@ __global__ __launch_bounds__(256) void match_pairs_valu_kernel(const float* __re
     const int l31 = lane & 31;
     float v = acc;
     int idx = l31;
-    const float v1 = __shfl_xor(acc, 32, 64);
-    if (v1 > v) { v = v1; idx = 32 + l31; }
+    float v1 = __shfl_xor(acc, 32, 64);
+    int i1 = 32 + l31;
+    if (MASKED) {
+        const unsigned long long m = load_shift_mask(mask, s, s + 1);
+        mask_shift(m, v, idx);
+        mask_shift(m, v1, i1);
+    }
+    if (v1 > v || (MASKED && v1 == v && i1 < idx)) { v = v1; idx = i1; }
 #pragma unroll
     for (int d = 1; d < 32; d <<= 1) {
         const float vo = __shfl_xor(v, d, 64);
         const int io = __shfl_xor(idx, d, 64);
         if (vo > v || (vo == v && io < idx)) { v = vo; idx = io; }
     }
+    if (MASKED) idx &= 63;
     if (lane == 0) {
         const float d = 2.f * (1.f - v / (wn[(size_t)o * 64 + idx] * sn[s]));
         if (orientation) orientation[pr] = idx;
@@ -1194,6 +1213,51 @@ static int match_fwd_launch(const float* ov, const float* su, int Bo, int Bs, in
         hipLaunchKernelGGL((match_kernel<1, 1, MASKED>), dim3(cdiv(Bs, 64), cdiv(Bo, 2)), dim3(NT), 0, st, a);
     }
     WITW_CHECK_LAUNCH("match_fwd");
+    return WITW_OK;
+}
+
+// n_pairs (overhead row, surface row) pairs -> orientation / distance / score [n_pairs] (any may be null), bit-identical to
+// the entries witw_match_fwd writes for those pairs. wn [Bo,64] / sn [Bs]: the norms of a witw_match_fwd or
+// witw_match_fwd_dft workspace over the same ov / su (window norms first, surface norms behind them).
+// MASKED = a shift mask was given: the same choice among the kernels, in their masked instantiations
+template <bool MASKED>
+static int match_pairs_launch(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o, const int* pair_s,
+                              int n_pairs, int Bo, int Bs, int We, long long* orientation, float* distance, float* score,
+                              const unsigned long long* shift_mask, void* stream) {
+    WITW_CHECK_ARG(ov && su && wn && sn && pair_o && pair_s, "match_pairs: null pointer");
+    WITW_CHECK_ARG(n_pairs > 0 && Bo > 0 && Bs > 0, "match_pairs: empty list n=%d Bo=%d Bs=%d", n_pairs, Bo, Bs);
+    WITW_CHECK_ARG(We >= 1 && We <= 64, "match_pairs: surface embedding width %d outside [1,64]", We);
+    if (g_match_pairs_impl == 0)
+        hipLaunchKernelGGL((match_pairs_kernel<MASKED>), dim3(cdiv(n_pairs, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o, pair_s,
+                           n_pairs, We, orientation, distance, score, shift_mask);
+    else if (We == 64)
+        hipLaunchKernelGGL((match_pairs_valu_kernel<64, MASKED>), dim3(cdiv(n_pairs, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o,
+                           pair_s, n_pairs, We, orientation, distance, score, (const int*)nullptr, (const float*)nullptr, (int*)nullptr, shift_mask);
+    else
+        hipLaunchKernelGGL((match_pairs_valu_kernel<0, MASKED>), dim3(cdiv(n_pairs, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o,
+                           pair_s, n_pairs, We, orientation, distance, score, (const int*)nullptr, (const float*)nullptr, (int*)nullptr, shift_mask);
+    WITW_CHECK_LAUNCH("match_pairs");
+    return WITW_OK;
+}
+
+// The band of witw_rank_count_band resolved WITHOUT a host round trip: the first min(*n_pairs_dev, capacity) pairs of the list are
+// re-scored exactly (as witw_match_pairs) and counts[pair_s[i]] is incremented for every pair whose exact distance is <=
+// threshold[pair_s[i]] -- after it counts[q] = #{o : D_exact[o][q] <= threshold[q]} provided the list did not overflow (the caller
+// checks *n_pairs_dev <= capacity once, at the end of its pass). Launches capacity / 4 workgroups; those beyond the list exit.
+template <bool MASKED>
+static int match_pairs_count_launch(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o, const int* pair_s,
+                                    const int* n_pairs_dev, int capacity, int Bo, int Bs, int We, const float* threshold, int* counts,
+                                    const unsigned long long* shift_mask, void* stream) {
+    WITW_CHECK_ARG(ov && su && wn && sn && pair_o && pair_s && n_pairs_dev && threshold && counts, "match_pairs_count: null pointer");
+    WITW_CHECK_ARG(capacity > 0 && Bo > 0 && Bs > 0, "match_pairs_count: bad arguments capacity=%d Bo=%d Bs=%d", capacity, Bo, Bs);
+    WITW_CHECK_ARG(We >= 1 && We <= 64, "match_pairs_count: surface embedding width %d outside [1,64]", We);
+    if (We == 64)
+        hipLaunchKernelGGL((match_pairs_valu_kernel<64, MASKED>), dim3(cdiv(capacity, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o,
+                           pair_s, capacity, We, (long long*)nullptr, (float*)nullptr, (float*)nullptr, n_pairs_dev, threshold, counts, shift_mask);
+    else
+        hipLaunchKernelGGL((match_pairs_valu_kernel<0, MASKED>), dim3(cdiv(capacity, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o,
+                           pair_s, capacity, We, (long long*)nullptr, (float*)nullptr, (float*)nullptr, n_pairs_dev, threshold, counts, shift_mask);
+    WITW_CHECK_LAUNCH("match_pairs_count");
     return WITW_OK;
 }
 
@@ -1302,44 +1366,31 @@ int witw_rank_count_thresh(const float* distance, const float* threshold, int* r
     return WITW_OK;
 }
 
-// n_pairs (overhead row, surface row) pairs -> orientation / distance / score [n_pairs] (any may be null), bit-identical to
-// the entries witw_match_fwd writes for those pairs. wn [Bo,64] / sn [Bs]: the norms of a witw_match_fwd or
-// witw_match_fwd_dft workspace over the same ov / su (window norms first, surface norms behind them).
 int witw_match_pairs(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o, const int* pair_s,
                      int n_pairs, int Bo, int Bs, int We, long long* orientation, float* distance, float* score, void* stream) {
-    WITW_CHECK_ARG(ov && su && wn && sn && pair_o && pair_s, "match_pairs: null pointer");
-    WITW_CHECK_ARG(n_pairs > 0 && Bo > 0 && Bs > 0, "match_pairs: empty list n=%d Bo=%d Bs=%d", n_pairs, Bo, Bs);
-    WITW_CHECK_ARG(We >= 1 && We <= 64, "match_pairs: surface embedding width %d outside [1,64]", We);
-    if (g_match_pairs_impl == 0)
-        hipLaunchKernelGGL(match_pairs_kernel, dim3(cdiv(n_pairs, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o, pair_s,
-                           n_pairs, We, orientation, distance, score);
-    else if (We == 64)
-        hipLaunchKernelGGL((match_pairs_valu_kernel<64>), dim3(cdiv(n_pairs, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o,
-                           pair_s, n_pairs, We, orientation, distance, score, (const int*)nullptr, (const float*)nullptr, (int*)nullptr);
-    else
-        hipLaunchKernelGGL((match_pairs_valu_kernel<0>), dim3(cdiv(n_pairs, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o,
-                           pair_s, n_pairs, We, orientation, distance, score, (const int*)nullptr, (const float*)nullptr, (int*)nullptr);
-    WITW_CHECK_LAUNCH("match_pairs");
-    return WITW_OK;
+    return match_pairs_launch<false>(ov, su, wn, sn, pair_o, pair_s, n_pairs, Bo, Bs, We, orientation, distance, score, nullptr, stream);
 }
 
-// The band of witw_rank_count_band resolved WITHOUT a host round trip: the first min(*n_pairs_dev, capacity) pairs of the list are
-// re-scored exactly (as witw_match_pairs) and counts[pair_s[i]] is incremented for every pair whose exact distance is <=
-// threshold[pair_s[i]] -- after it counts[q] = #{o : D_exact[o][q] <= threshold[q]} provided the list did not overflow (the caller
-// checks *n_pairs_dev <= capacity once, at the end of its pass). Launches capacity / 4 workgroups; those beyond the list exit.
+// witw_match_pairs under the shift masks of witw_match_fwd_masked (shift_mask [Bs], indexed by pair_s[i]): bit-identical to the
+// entries witw_match_fwd_masked writes for those pairs.
+int witw_match_pairs_masked(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o, const int* pair_s,
+                            int n_pairs, int Bo, int Bs, int We, long long* orientation, float* distance, float* score,
+                            const unsigned long long* shift_mask, void* stream) {
+    WITW_CHECK_ARG(shift_mask, "match_pairs_masked: null shift_mask pointer");
+    return match_pairs_launch<true>(ov, su, wn, sn, pair_o, pair_s, n_pairs, Bo, Bs, We, orientation, distance, score, shift_mask, stream);
+}
+
 int witw_match_pairs_count(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o, const int* pair_s,
                            const int* n_pairs_dev, int capacity, int Bo, int Bs, int We, const float* threshold, int* counts, void* stream) {
-    WITW_CHECK_ARG(ov && su && wn && sn && pair_o && pair_s && n_pairs_dev && threshold && counts, "match_pairs_count: null pointer");
-    WITW_CHECK_ARG(capacity > 0 && Bo > 0 && Bs > 0, "match_pairs_count: bad arguments capacity=%d Bo=%d Bs=%d", capacity, Bo, Bs);
-    WITW_CHECK_ARG(We >= 1 && We <= 64, "match_pairs_count: surface embedding width %d outside [1,64]", We);
-    if (We == 64)
-        hipLaunchKernelGGL((match_pairs_valu_kernel<64>), dim3(cdiv(capacity, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o,
-                           pair_s, capacity, We, (long long*)nullptr, (float*)nullptr, (float*)nullptr, n_pairs_dev, threshold, counts);
-    else
-        hipLaunchKernelGGL((match_pairs_valu_kernel<0>), dim3(cdiv(capacity, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn, pair_o,
-                           pair_s, capacity, We, (long long*)nullptr, (float*)nullptr, (float*)nullptr, n_pairs_dev, threshold, counts);
-    WITW_CHECK_LAUNCH("match_pairs_count");
-    return WITW_OK;
+    return match_pairs_count_launch<false>(ov, su, wn, sn, pair_o, pair_s, n_pairs_dev, capacity, Bo, Bs, We, threshold, counts, nullptr, stream);
+}
+
+// witw_match_pairs_count with the pairs re-scored as witw_match_pairs_masked does.
+int witw_match_pairs_count_masked(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o, const int* pair_s,
+                                  const int* n_pairs_dev, int capacity, int Bo, int Bs, int We, const float* threshold, int* counts,
+                                  const unsigned long long* shift_mask, void* stream) {
+    WITW_CHECK_ARG(shift_mask, "match_pairs_count_masked: null shift_mask pointer");
+    return match_pairs_count_launch<true>(ov, su, wn, sn, pair_o, pair_s, n_pairs_dev, capacity, Bo, Bs, We, threshold, counts, shift_mask, stream);
 }
 
 // Which kernel witw_match_pairs runs: 1 = the v_fma_f32 chain on the vector pipe (default), 0 = the v_mfma_f32_32x32x2_f32 chain of

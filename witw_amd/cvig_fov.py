@@ -48,7 +48,8 @@ class Globals:
     device_jpeg = True
     pinned_ring = True
     # not in the reference: how test() ranks the queries against the gallery. 'direct' = the reference's sum on every pair,
-    # 'dft' = the spectral pass with exact re-scoring (same ranks), 'auto' = 'dft' from cvig_fov.SPECTRAL_FROM pairs on.
+    # 'dft' = the spectral pass with exact re-scoring (same ranks), 'auto' = 'dft' from cvig_fov.SPECTRAL_FROM pairs on;
+    # 'dft_masked' = 'dft' that also takes an orientation prior (test(orientation_window=): the masked spectral pass).
     match_method = 'auto'
     # not in the reference: the training objective of train() (`--loss`). 'soft_margin' = the reference's all-pairs soft-margin
     # triplet loss (triplet_loss); 'batch_hard' = the soft-margin loss on each anchor's hardest negative in the global batch
@@ -755,20 +756,23 @@ def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, meth
     17x faster at retrieval sizes; 'auto' = 'dft' from SPECTRAL_FROM pairs on. 8,884 CVUSA test pairs: 0.55 s direct, 10^5 pairs:
     36 s direct / 2 s spectral.
     shift_mask: int64, one word per query of the WHOLE evaluation set (all ranks' rows, in order), see orientation_mask. The
-    spectral pass has no masked form: 'auto' then means 'direct', an explicit 'dft' is an error."""
+    masked spectral pass is method 'dft_masked' (retrieve(): the same ranks as 'direct' under the same mask; without a mask it is
+    'dft'); with a mask 'auto' still means 'direct' and an explicit 'dft' is an error."""
     from . import parallel
-    if method not in ('auto', 'direct', 'dft'):
-        raise _lib.WitwError("match_method must be 'auto', 'direct' or 'dft', got %r" % (method,))
+    if method not in ('auto', 'direct', 'dft', 'dft_masked'):
+        raise _lib.WitwError("match_method must be 'auto', 'direct', 'dft' or 'dft_masked', got %r" % (method,))
     if shift_mask is not None:
         if method == 'dft':
             raise _lib.WitwError("evaluation_ranks: shift_mask is not supported by the spectral pass (method='dft'); use "
-                                 "'direct' or 'auto'")
-        method = 'direct'
+                                 "'dft_masked', 'direct' or 'auto'")
+        if method == 'auto':
+            method = 'direct'
     surface_all = parallel.all_gather_ragged(surface_embed) if world > 1 else surface_embed
     if method == 'auto':
         method = 'dft' if surface_all.shape[0] >= SPECTRAL_FROM else 'direct'
-    if method == 'dft':
-        return retrieve(overhead_embed, surface_all, k=1, shard_begin=shard_begin, method='dft')[0]
+    if method in ('dft', 'dft_masked'):
+        masked = {} if shift_mask is None else {'shift_mask': shift_mask}
+        return retrieve(overhead_embed, surface_all, k=1, shard_begin=shard_begin, method=method, **masked)[0]
     if world > 1:
         return sharded_ranks(overhead_embed, surface_all, shard_begin, shift_mask=shift_mask)
     return ranks(overhead_embed, surface_embed, shift_mask)
@@ -845,26 +849,31 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     spectral distances leave within fp32 rounding -- a row within DISTANCE_EPS of a query's true-match distance, neighbours
     in a top-k list closer than 2 DISTANCE_EPS -- is re-made on distances from ops.match_pairs, which are bit-identical to the
     direct kernel's: ranks and top-k INDICES equal method='direct' exactly (the listed distances agree to DISTANCE_EPS).
-    shift_mask (int64 [N], one word per query, see orientation_mask): every query chunk is matched under its own slice of it;
-    method 'direct' (or 'auto', which a mask resolves to 'direct') only -- the spectral pass has no masked form."""
+    shift_mask (int64 [N], one word per query, see orientation_mask): every query chunk is matched under its own slice of it.
+    method='dft_masked' is the spectral pass under a mask (witw_match_fwd_dft_masked, every re-scoring through
+    witw_match_pairs_masked): ranks and top-k indices equal method='direct' with the same mask; without a mask it is 'dft'.
+    'dft' itself keeps refusing a mask and 'auto' with a mask keeps meaning 'direct'."""
     from . import parallel
     kn = _kernels or ops
     if shift_mask is not None:
         if method == 'dft':
-            raise _lib.WitwError("retrieve: shift_mask is not supported by the spectral pass (method='dft'); use 'direct'")
+            raise _lib.WitwError("retrieve: shift_mask is not supported by the spectral pass (method='dft'); use 'dft_masked' or "
+                                 "'direct'")
         if method == 'auto':
             method = 'direct'
         shift_mask = _query_mask(shift_mask, surface_all)
-    if method == 'dft' and k + DFT_MARGIN > 32:      # no room for the candidate margin in a 32-wide list: the top-k comes from the
+    spectral = method in ('dft', 'dft_masked')
+    masked = {} if shift_mask is None else {'shift_mask': shift_mask}
+    if spectral and k + DFT_MARGIN > 32:             # no room for the candidate margin in a 32-wide list: the top-k comes from the
         ranks_dft = None                              # direct pass, the rank counts (no list involved) still from the spectral one
         if _want_ranks:
-            ranks_dft = _retrieve_dft(overhead_shard, surface_all, 1, shard_begin, query_chunk, kn, True)[0]
-        _r, v, i = retrieve(overhead_shard, surface_all, k, shard_begin, query_chunk, 'direct', _kernels, _want_ranks=False)
+            ranks_dft = _retrieve_dft(overhead_shard, surface_all, 1, shard_begin, query_chunk, kn, True, method=method, **masked)[0]
+        _r, v, i = retrieve(overhead_shard, surface_all, k, shard_begin, query_chunk, 'direct', _kernels, _want_ranks=False, **masked)
         return ranks_dft, v, i
-    if method == 'dft':
-        return _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, _want_ranks)
+    if spectral:
+        return _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, _want_ranks, method=method, **masked)
     if method != 'direct':
-        raise ValueError("retrieve: method must be 'direct' or 'dft'")
+        raise ValueError("retrieve: method must be 'direct', 'dft' or 'dft_masked'")
     n_q, n_g = surface_all.shape[0], overhead_shard.shape[0]
     counts = torch.zeros((n_q,), dtype=torch.int32, device=surface_all.device)
     vals, idxs = [], []
@@ -923,10 +932,15 @@ def last_retrieve_stats():
 DFT_MARGIN = 6      # candidates kept beyond place k by the spectral top-k (place k+1 must exist to decide place k)
 
 
-def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, want_ranks):
+def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, want_ranks, method='dft', shift_mask=None):
     """retrieve() on the spectral pass, index-exact (see retrieve). eps = ops.DISTANCE_EPS bounds |d_dft - d_direct| at full
     width; narrower surfaces (We < 64: the window norm, hence the distance, depends on the chosen shift) first have every pair
-    whose two best spectral scores are within rounding re-scored, so that the same bound holds for what is left."""
+    whose two best spectral scores are within rounding re-scored, so that the same bound holds for what is left.
+    shift_mask (int64 [N], already on the queries' device): every op of the pass gets the slice of the queries it sees -- the
+    keyword is passed only when a mask was given. eps is derived as without a mask: at full width the distance depends on the
+    largest ALLOWED score only, which both kernels know to SCORE_ROUNDING; below full width the gap that decides a re-scoring
+    is taken over the allowed shifts, so what is left has its shift settled among them; and the gallery's worst window bounds
+    |ov| / |window| whatever shifts a mask leaves."""
     from . import parallel
     eps = float(getattr(kn, 'DISTANCE_EPS', ops.DISTANCE_EPS))
     dev = surface_all.device
@@ -939,18 +953,20 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
     vals, idxs, sns = [], [], []
     band_checks = []
     wn = None
-    stats = {'method': 'dft', 'pairs': float(n_g) * n_q, 'rescored_rank': 0, 'rescored_topk': 0, 'rescored_true': 0,
-             'rescored_orientation': 0, 'fallback_queries': 0}
+    stats = {'method': method, 'masked': shift_mask is not None, 'pairs': float(n_g) * n_q, 'rescored_rank': 0, 'rescored_topk': 0,
+             'rescored_true': 0, 'rescored_orientation': 0, 'fallback_queries': 0}
+    whole = {} if shift_mask is None else {'shift_mask': shift_mask}
     for q0 in range(0, n_q, query_chunk):
         q1 = min(n_q, q0 + query_chunk)
         nq = q1 - q0
         su = surface_all[q0:q1].contiguous()
+        masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
         if n_g:
             if we < 64:
-                dist, ws, n_fix = _dft_pass_narrow(kn, gallery, su, spec_g)
+                dist, ws, n_fix = _dft_pass_narrow(kn, gallery, su, spec_g, **masked)
                 stats['rescored_orientation'] += n_fix
             else:
-                _, dist, ws = kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False, want_workspace=True)
+                _, dist, ws = kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False, want_workspace=True, **masked)
             wn, sn = ws[:n_g * 64], ws[n_g * 64:n_g * 64 + nq]
         else:
             dist = torch.empty((0, nq), dtype=torch.float32, device=dev)
@@ -976,7 +992,7 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
             if n_g and hi > lo:                          # the owner's EXACT distance of every true pair
                 po = torch.arange(lo - shard_begin, hi - shard_begin, dtype=torch.int32, device=dev)
                 ps = torch.arange(lo - q0, hi - q0, dtype=torch.int32, device=dev)
-                d_true[lo - q0:hi - q0] = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False)[1]
+                d_true[lo - q0:hi - q0] = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **masked)[1]
                 stats['rescored_true'] += hi - lo
             parallel.all_reduce_sum_(d_true)
             if n_g:
@@ -984,12 +1000,12 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
                 if hasattr(kn, 'rank_count_resolved'):
                     # band list, exact re-scoring and the count update in one stream sequence; the list's length stays on the device
                     # and is looked at once, behind the last chunk (band_checks)
-                    c, n_band, cap = kn.rank_count_resolved(dist, d_true, eps, gallery, su, wn, sn)
+                    c, n_band, cap = kn.rank_count_resolved(dist, d_true, eps, gallery, su, wn, sn, **masked)
                     band_checks.append((n_band, cap, q0, q1, dist if len(range(0, n_q, query_chunk)) == 1 else None, su, d_true, sn))
                 else:
                     c, po, ps = kn.rank_count_band(dist, d_true, eps)
                     if po.numel():
-                        d_x = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False)[1]
+                        d_x = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **masked)[1]
                         c.index_add_(0, ps.long(), (d_x <= d_true[ps.long()]).to(torch.int32))
                         stats['rescored_rank'] += int(po.numel())
                 counts[q0:q1] = c
@@ -1007,12 +1023,13 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
         for got, (_n, cap, q0, q1, dist_kept, su, d_true, sn) in zip(n_host, band_checks):
             stats['rescored_rank'] += min(int(got), cap)
             if got > cap:
+                masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
                 dist_c = dist_kept
                 if dist_c is None:
-                    dist_c = (_dft_pass_narrow(kn, gallery, su, spec_g)[0] if we < 64 else
-                              kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False)[1])
+                    dist_c = (_dft_pass_narrow(kn, gallery, su, spec_g, **masked)[0] if we < 64 else
+                              kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False, **masked)[1])
                 c, po, ps = kn.rank_count_band(dist_c, d_true, eps)
-                d_x = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False)[1]
+                d_x = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **masked)[1]
                 c.index_add_(0, ps.long(), (d_x <= d_true[ps.long()]).to(torch.int32))
                 counts[q0:q1] = c
         band_checks = []
@@ -1045,7 +1062,7 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
         if n_g and bool(mine.any()):
             po = (ci - shard_begin)[mine].to(torch.int32).contiguous()
             ps = rows[:, None].expand(-1, m)[mine].to(torch.int32).contiguous()
-            exact[mine] = kn.match_pairs(gallery, surface_all.contiguous(), wn, sn_all, po, ps, want_orientation=False)[1]
+            exact[mine] = kn.match_pairs(gallery, surface_all.contiguous(), wn, sn_all, po, ps, want_orientation=False, **whole)[1]
             stats['rescored_topk'] += int(po.numel())
         parallel.all_reduce_sum_(exact)
         exact = torch.where(ci < 0, torch.full_like(exact, float('inf')), exact)
@@ -1058,8 +1075,9 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
         fallback = rows[~safe]
     if fallback.numel():     # more near-ties than candidates kept (not seen on real data): those queries take the direct pass
         stats['fallback_queries'] = int(fallback.numel())
+        masked = {} if shift_mask is None else {'shift_mask': shift_mask[fallback].contiguous()}
         _r, fv, fi = retrieve(overhead_shard, surface_all[fallback].contiguous(), k, shard_begin, query_chunk, 'direct',
-                              None if kn is ops else kn, _want_ranks=False)
+                              None if kn is ops else kn, _want_ranks=False, **masked)
         v[fallback, :k], i[fallback, :k] = fv, fi
     stats['eps'] = eps
     retrieve.last_stats = stats
@@ -1067,13 +1085,17 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
     return (counts.cpu().numpy().astype('int64') if want_ranks else None), v[:, :k].contiguous(), i[:, :k].contiguous()
 
 
-def _dft_pass_narrow(kn, gallery, su, spec_g):
+def _dft_pass_narrow(kn, gallery, su, spec_g, shift_mask=None):
     """The spectral pass for surfaces narrower than the overhead embedding (We < 64): the window norm depends on the shift, so
     a pair whose two best scores are within rounding could take the other shift in the direct kernel and land on a different
     distance. Those pairs (top-2 score gap <= 4 SCORE_ROUNDING |ov| |su|) are re-scored exactly and patched into the matrix.
+    shift_mask (int64 [nq], this chunk's words): the gap is then the one between the two best ALLOWED scores (+inf where a word
+    allows one shift: nothing to re-score) and the re-scoring runs under the mask.
     -> (distance [n_g, nq], workspace, pairs re-scored)."""
     n_g, nq = gallery.shape[0], su.shape[0]
-    _, dist, gap, ws = kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False, want_workspace=True, want_gap=True)
+    masked = {} if shift_mask is None else {'shift_mask': shift_mask}
+    _, dist, gap, ws = kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False, want_workspace=True, want_gap=True,
+                                        **masked)
     wn, sn = ws[:n_g * 64], ws[n_g * 64:n_g * 64 + nq]
     ov_norm = gallery.reshape(n_g, -1).norm(dim=1)
     rounding = float(getattr(kn, 'SCORE_ROUNDING', ops.SCORE_ROUNDING))
@@ -1081,7 +1103,7 @@ def _dft_pass_narrow(kn, gallery, su, spec_g):
     pairs = torch.nonzero(close)
     if pairs.numel():
         po, ps = pairs[:, 0].to(torch.int32).contiguous(), pairs[:, 1].to(torch.int32).contiguous()
-        dist[pairs[:, 0], pairs[:, 1]] = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False)[1]
+        dist[pairs[:, 0], pairs[:, 1]] = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **masked)[1]
     return dist, ws, int(pairs.shape[0])
 
 
@@ -2076,8 +2098,14 @@ def main(argv=None):
                         help='test mode (not in the reference): restrict every query\'s orientation search to the shifts within '
                              'HALFWIDTH degrees of CENTER (degrees of the heat-map CSV: shift k = k*360/64 - 180). '
                              '[Default = all 64 shifts]')
+    parser.add_argument('--match-method', default='auto', choices=['auto', 'direct', 'dft', 'dft_masked'],
+                        help='test mode (not in the reference): how the queries are ranked against the gallery. direct = the '
+                             'correlation sum on every pair, dft = the spectral pass with exact re-scoring (same ranks), dft_masked '
+                             '= the spectral pass that also takes --orientation-window, auto = dft on large sets without a window, '
+                             'direct otherwise. [Default = auto]')
     args = parser.parse_args(argv)
     print(args)
+    Globals.match_method = args.match_method
     Globals.precision = args.precision
     Globals.vgg16_weights = args.vgg16
     Globals.loss = args.loss

@@ -521,6 +521,14 @@ def match_bwd(overhead_embed, surface_embed, orientation, score, workspace, grad
     return gov, gsu
 
 
+def _check_shift_mask(name, shift_mask, Bs, device):
+    if not (isinstance(shift_mask, torch.Tensor) and shift_mask.dtype == torch.int64 and shift_mask.device == device
+            and tuple(shift_mask.shape) == (Bs,) and shift_mask.is_contiguous()):
+        raise _lib.WitwError('%s: shift_mask must be a contiguous int64 [%d] tensor on %s, got %s'
+                             % (name, Bs, device, (tuple(shift_mask.shape), shift_mask.dtype, shift_mask.device)
+                                if isinstance(shift_mask, torch.Tensor) else type(shift_mask)))
+
+
 def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=False, shift_mask=None):
     """Fused correlation -> argmax -> window norm -> chord distance (no crop tensor).
     overhead_embed [Bo,16,4,64], surface_embed [Bs,16,4,We] -> (orientation int64 [Bo,Bs],
@@ -616,10 +624,12 @@ def match_spectrum(embed, overhead):
 
 
 def match_fwd_dft(overhead_embed, surface_embed, spec_ov=None, spec_su=None, want_score=False, want_orientation=True,
-                  want_workspace=False, want_gap=False):
+                  want_workspace=False, want_gap=False, shift_mask=None):
     """match_fwd through the row spectra (21k FLOP per pair instead of 524k): same outputs; scores agree with the direct sum to
     fp32 rounding, so an orientation can differ only between shifts whose scores tie to ~1e-6. spec_ov / spec_su: cached
-    match_spectrum of the two sides (the gallery's is computed once per retrieval)."""
+    match_spectrum of the two sides (the gallery's is computed once per retrieval).
+    shift_mask: None, or int64 [Bs] as match_fwd takes it (witw_match_fwd_dft_masked): the first maximum over the allowed shifts;
+    the gap is then taken over the allowed shifts, +inf where a word allows one shift."""
     lib = _lib.load()
     ov = _dev_f32(overhead_embed, 'overhead_embed')
     su = _dev_f32(surface_embed, 'surface_embed')
@@ -628,6 +638,8 @@ def match_fwd_dft(overhead_embed, surface_embed, spec_ov=None, spec_su=None, wan
     if su.shape[1] != ov.shape[1] or su.shape[2] != ov.shape[2]:
         raise _lib.WitwError('match_fwd_dft: surface embedding %s does not match overhead %s' % (tuple(su.shape), tuple(ov.shape)))
     Bo, Bs, We = ov.shape[0], su.shape[0], su.shape[3]
+    if shift_mask is not None:
+        _check_shift_mask('match_fwd_dft', shift_mask, Bs, ov.device)
     spec_ov = match_spectrum(ov, overhead=True) if spec_ov is None else spec_ov
     spec_su = match_spectrum(su, overhead=False) if spec_su is None else spec_su
     for name, sp, n, side in (('spec_ov', spec_ov, Bo, True), ('spec_su', spec_su, Bs, False)):
@@ -649,7 +661,11 @@ def match_fwd_dft(overhead_embed, surface_embed, spec_ov=None, spec_su=None, wan
     ws = torch.empty(lib.witw_match_dft_workspace_floats(Bo, Bs), dtype=torch.float32, device=ov.device)
     prof = _prof_begin()
     gap = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device) if want_gap else None
-    if want_gap:
+    if shift_mask is not None:
+        _lib.check(lib.witw_match_fwd_dft_masked(ov.data_ptr(), su.data_ptr(), spec_ov.data_ptr(), spec_su.data_ptr(), Bo, Bs, We,
+                                                 _p(ori), dist.data_ptr(), _p(score), _p(gap), ws.data_ptr(), shift_mask.data_ptr(),
+                                                 _stream()), 'witw_match_fwd_dft_masked')
+    elif want_gap:
         _lib.check(lib.witw_match_fwd_dft_gap(ov.data_ptr(), su.data_ptr(), spec_ov.data_ptr(), spec_su.data_ptr(), Bo, Bs, We,
                                               _p(ori), dist.data_ptr(), _p(score), gap.data_ptr(), ws.data_ptr(), _stream()),
                    'witw_match_fwd_dft_gap')
@@ -672,9 +688,10 @@ SCORE_ROUNDING = 2e-6
 DISTANCE_EPS = 1e-5
 
 
-def match_pairs(overhead_embed, surface_embed, wn, sn, pair_o, pair_s, want_orientation=True):
+def match_pairs(overhead_embed, surface_embed, wn, sn, pair_o, pair_s, want_orientation=True, shift_mask=None):
     """(overhead row pair_o[i], surface row pair_s[i]) -> (orientation int64 [n] or None, distance f32 [n]) with the bits
-    match_fwd gives those pairs. wn / sn: the norm blocks of a match_fwd / match_fwd_dft workspace over the same tensors."""
+    match_fwd gives those pairs. wn / sn: the norm blocks of a match_fwd / match_fwd_dft workspace over the same tensors.
+    shift_mask: None, or int64 [Bs] (indexed by pair_s): the bits of match_fwd(..., shift_mask=) (witw_match_pairs_masked)."""
     lib = _lib.load()
     ov = _dev_f32(overhead_embed, 'overhead_embed')
     su = _dev_f32(surface_embed, 'surface_embed')
@@ -685,9 +702,15 @@ def match_pairs(overhead_embed, surface_embed, wn, sn, pair_o, pair_s, want_orie
             raise _lib.WitwError('match_pairs: %s must be a contiguous int32 GPU tensor of %d entries' % (name, n))
     if wn.numel() != Bo * 64 or sn.numel() != Bs:
         raise _lib.WitwError('match_pairs: wn / sn must hold [Bo,64] / [Bs] norms')
+    if shift_mask is not None:
+        _check_shift_mask('match_pairs', shift_mask, Bs, ov.device)
     ori = torch.empty((n,), dtype=torch.int64, device=ov.device) if want_orientation else None
     dist = torch.empty((n,), dtype=torch.float32, device=ov.device)
-    if n:
+    if n and shift_mask is not None:
+        _lib.check(lib.witw_match_pairs_masked(ov.data_ptr(), su.data_ptr(), _dev_f32(wn, 'wn').data_ptr(), _dev_f32(sn, 'sn').data_ptr(),
+                                               pair_o.data_ptr(), pair_s.data_ptr(), n, Bo, Bs, We, _p(ori), dist.data_ptr(), None,
+                                               shift_mask.data_ptr(), _stream()), 'witw_match_pairs_masked')
+    elif n:
         _lib.check(lib.witw_match_pairs(ov.data_ptr(), su.data_ptr(), _dev_f32(wn, 'wn').data_ptr(), _dev_f32(sn, 'sn').data_ptr(),
                                         pair_o.data_ptr(), pair_s.data_ptr(), n, Bo, Bs, We, _p(ori), dist.data_ptr(), None,
                                         _stream()), 'witw_match_pairs')
@@ -717,11 +740,12 @@ def rank_count_band(distance, threshold, eps):
         cap = got            # rare: more pairs in the band than the list holds -> once more with room for all
 
 
-def rank_count_resolved(distance, threshold, eps, overhead_embed, surface_embed, wn, sn):
+def rank_count_resolved(distance, threshold, eps, overhead_embed, surface_embed, wn, sn, shift_mask=None):
     """rank_count_band + the exact re-scoring of its band in ONE stream sequence without a host round trip: -> (counts int32 [Bs] =
     #{o : exact distance[o][q] <= threshold[q]}, n int32 [1] on the device = pairs in the band, capacity). The result is complete iff
     n <= capacity, which the caller checks once at the end of its pass (retrieve(method='dft')); beyond it the list overflowed and the
-    chunk has to be redone through rank_count_band."""
+    chunk has to be redone through rank_count_band. shift_mask: None, or int64 [Bs]: the band is re-scored as
+    match_pairs(..., shift_mask=) does (witw_match_pairs_count_masked)."""
     lib = _lib.load()
     d = _dev_f32(distance, 'distance')
     t = _dev_f32(threshold, 'threshold')
@@ -732,6 +756,8 @@ def rank_count_resolved(distance, threshold, eps, overhead_embed, surface_embed,
         raise _lib.WitwError('rank_count_resolved: distance [Bo,Bs], threshold [Bs] and the two embedding batches must agree')
     if wn.numel() != Bo * 64 or sn.numel() != Bs:
         raise _lib.WitwError('rank_count_resolved: wn / sn must hold [Bo,64] / [Bs] norms')
+    if shift_mask is not None:
+        _check_shift_mask('rank_count_resolved', shift_mask, Bs, d.device)
     counts = torch.empty((Bs,), dtype=torch.int32, device=d.device)
     n = torch.empty((1,), dtype=torch.int32, device=d.device)
     cap = max(1 << 16, (Bo * Bs) // 4096)
@@ -739,6 +765,12 @@ def rank_count_resolved(distance, threshold, eps, overhead_embed, surface_embed,
     ps = torch.empty((cap,), dtype=torch.int32, device=d.device)
     _lib.check(lib.witw_rank_count_band(d.data_ptr(), t.data_ptr(), float(eps), counts.data_ptr(), po.data_ptr(), ps.data_ptr(),
                                         n.data_ptr(), cap, Bo, Bs, _stream()), 'witw_rank_count_band')
+    if shift_mask is not None:
+        _lib.check(lib.witw_match_pairs_count_masked(ov.data_ptr(), su.data_ptr(), _dev_f32(wn, 'wn').data_ptr(),
+                                                     _dev_f32(sn, 'sn').data_ptr(), po.data_ptr(), ps.data_ptr(), n.data_ptr(), cap, Bo, Bs,
+                                                     su.shape[3], t.data_ptr(), counts.data_ptr(), shift_mask.data_ptr(), _stream()),
+                   'witw_match_pairs_count_masked')
+        return counts, n, cap
     _lib.check(lib.witw_match_pairs_count(ov.data_ptr(), su.data_ptr(), _dev_f32(wn, 'wn').data_ptr(), _dev_f32(sn, 'sn').data_ptr(),
                                           po.data_ptr(), ps.data_ptr(), n.data_ptr(), cap, Bo, Bs, su.shape[3], t.data_ptr(),
                                           counts.data_ptr(), _stream()), 'witw_match_pairs_count')
