@@ -153,6 +153,16 @@ int witw_match_fwd(const float* ov, const float* su, int Bo, int Bs, int We, lon
  * backward of this entry as it is. */
 int witw_match_fwd_masked(const float* ov, const float* su, int Bo, int Bs, int We, long long* orientation, float* distance,
                           float* score, float* workspace, const unsigned long long* shift_mask, void* stream);
+/* The match at a KNOWN orientation (an aligned protocol, a trusted heading): shift [Bs] (device int64) gives every surface embedding
+ * its one shift, used as shift[s] & 63, and score[o][s] = sum_{ch,k<We} ov[o][ch][(k+shift[s])%64] * su[s][ch][k] is one
+ * Bo x Bs x 64*We contraction -- 1/64 of the products of witw_match_fwd_masked under one-bit words. orientation[o][s] = shift[s] & 63;
+ * distance and score are taken there and are BIT-IDENTICAL to witw_match_fwd_masked with shift_mask[s] = 1 << (shift[s] & 63) (the
+ * same fp32 MFMA chain per pair, row outer, k inner). Any output may be NULL. workspace: witw_match_fixed_workspace_floats(Bo,Bs)
+ * floats; it begins with the window norms [Bo,64] and surface norms [Bs] of a witw_match_fwd workspace, so witw_match_bwd,
+ * witw_match_bwd_pairs and witw_match_pairs* take it as they take that one; the grouping of the surfaces by shift follows. */
+long long witw_match_fixed_workspace_floats(int Bo, int Bs);
+int witw_match_fwd_fixed(const float* ov, const float* su, int Bo, int Bs, int We, const long long* shift /* [Bs], device */,
+                         long long* orientation, float* distance, float* score, float* workspace, void* stream);
 /* The same match through the row spectra (retrieval, BASELINE config 5: every gallery row against every query). The orientation
  * search is a circular cross-correlation along the 64 columns: with the 64-point DFT of every (channel,row) line of both sides it
  * costs 21k FLOP per pair instead of 524k. witw_match_spectrum: emb [B,64 lines,W] (overhead: W = 64; surface: W = We, zero-

@@ -1158,6 +1158,211 @@ __global__ __launch_bounds__(256) void rank_band_kernel(const float* __restrict_
     if (c) atomicAdd(&counts[q], c);
 }
 
+// ---- known orientation (witw_match_fwd_fixed): every surface s is matched at ONE given shift, shift[s] & 63, so
+//   score[o,s] = sum_{ch,k<We} ov[o,ch,(k+shift_s)%64] * su[s,ch,k]
+// is a Bo x Bs x 64*We contraction: 1/64 of the products of the kernels above, which form all 64 shift scores and let a one-bit mask
+// discard 63 of them. An MFMA tile needs one shift for all its A rows (the B operand is the overhead row read AT that shift), so the
+// surfaces are first grouped by shift: fixed_group_kernel, a stable counting sort over 64 bins in the workspace, cuts every group
+// into "supertiles" of up to 32*SM surfaces. A workgroup takes one supertile (1-4 M-tiles of 32 surfaces of ONE shift) x 128
+// overheads: wave w owns overheads [32w, 32w+32) and all the supertile's M-tiles. The overhead rows are staged into LDS already
+// rotated (column (k+shift)&63 lands at k), so both operands are K-contiguous rows of stride 65. The SUMMATION order is untouched:
+// per pair the same v_mfma_f32_32x32x2_f32 chain over (row ch outer, k inner) from a zero accumulator as in match_kernel -- lanes
+// beyond We multiply exact zeros, as the padded columns of match_kernel_rows do -- so distance and score carry the bits
+// witw_match_fwd_masked writes under shift_mask[s] = 1 << (shift[s] & 63). One LDS stage is 64 columns = R = 64/WP embedding rows
+// of WP >= We columns (32 unrolled k-steps), single-buffered behind a register prefetch of the next stage (66.5 KB: two
+// workgroups per CU). The accumulators leave through LDS transposed, so a wave writes consecutive surfaces of one overhead row.
+constexpr int FX_TN = 128;                    // overheads per workgroup
+constexpr int FX_LDS_F = 256 * SUS;           // floats of the stage: 128 surface rows + 128 overhead rows (>= the 128 x 129 epilogue tile)
+constexpr int FX_TS = 129;                    // row stride of the transposed epilogue tile
+
+struct FixedArgs {
+    const float* ov;     // [Bo,64,64]
+    const float* su;     // [Bs,64,We]
+    const float* wn;     // [Bo,64]
+    const float* sn;     // [Bs]
+    const int* tab;      // [0]: number of supertiles; [1+2t]: first position in perm; [2+2t]: surfaces << 8 | shift
+    const int* perm;     // [Bs] surface indices ordered by (shift, index)
+    long long* orientation;
+    float* distance;
+    float* score;
+    int Bo, Bs, We;
+};
+
+// upper bound of the number of supertiles of `rows` surfaces each that Bs surfaces in at most 64 groups can make
+static inline int fixed_max_tiles(int Bs, int rows) {
+    const int groups = Bs < 64 ? Bs : 64;
+    return (int)(((long long)Bs + (long long)groups * (rows - 1)) / rows);
+}
+
+// One workgroup: histogram of shift & 63 (LDS integer atomics: the counts do not depend on their order), the supertile table, then
+// the stable placement -- per chunk of 256 surfaces a lane's rank among the lanes of its wave with the same shift (six ballots),
+// the waves' counts through LDS, a running base per bin.
+__global__ __launch_bounds__(256) void fixed_group_kernel(const long long* __restrict__ shift, int Bs, int rows_per_tile,
+                                                          int* __restrict__ tab, int* __restrict__ perm) {
+    __shared__ int cnt[64];
+    __shared__ int base[64];
+    __shared__ int wcnt[4][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 64) cnt[tid] = 0;
+    __syncthreads();
+    for (int s = tid; s < Bs; s += 256) atomicAdd(&cnt[(int)(shift[s] & 63)], 1);
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0, nt = 0;
+        for (int g = 0; g < 64; ++g) {
+            const int c = cnt[g];
+            base[g] = run;
+            for (int t = 0; t < c; t += rows_per_tile) {
+                tab[1 + 2 * nt] = run + t;
+                tab[2 + 2 * nt] = (min(rows_per_tile, c - t) << 8) | g;
+                ++nt;
+            }
+            run += c;
+        }
+        tab[0] = nt;
+    }
+    for (int c0 = 0; c0 < Bs; c0 += 256) {
+        const int s = c0 + tid;
+        const bool valid = s < Bs;
+        const int b = valid ? (int)(shift[s] & 63) : 0;
+        unsigned long long same = __builtin_amdgcn_ballot_w64(valid);
+#pragma unroll
+        for (int bit = 0; bit < 6; ++bit) {
+            const unsigned long long bb = __builtin_amdgcn_ballot_w64((b >> bit) & 1);
+            same &= ((b >> bit) & 1) ? bb : ~bb;
+        }
+        const int before = __builtin_popcountll(same & ((1ull << lane) - 1ull));
+        wcnt[wave][lane] = 0;
+        __syncthreads();               // also: base[] of the table pass / the previous chunk is in place
+        if (valid && before == 0) wcnt[wave][b] = __builtin_popcountll(same);
+        __syncthreads();
+        if (valid) {
+            int pos = base[b] + before;
+            for (int w = 0; w < wave; ++w) pos += wcnt[w][b];
+            perm[pos] = s;
+        }
+        __syncthreads();
+        if (tid < 64) base[tid] += (wcnt[0][tid] + wcnt[1][tid]) + (wcnt[2][tid] + wcnt[3][tid]);
+        __syncthreads();
+    }
+}
+
+template <int WP, int MT>      // WP: columns per embedding row in a stage (16, 32, 64; >= We); MT: 32-surface M-tiles of this supertile
+__device__ __forceinline__ void fixed_tile(const FixedArgs& p, float* smem, int first, int rows, int shift, int o0) {
+    constexpr int R = 64 / WP, NS = 64 / R, KS = 32;
+    constexpr unsigned OOR = 0x80000000u;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int l31 = lane & 31, hk = lane >> 5;
+    const int We = p.We;
+
+    // staging: lane <-> (row rr = lane / WP of the stage, column k = lane % WP), (wave + 4*i) <-> surface / overhead of the tile.
+    // Buffer loads: a lane beyond We, a surface beyond the supertile and an overhead beyond Bo carry an out-of-range offset and read
+    // 0. The surface buffer spans all of su (the rows are gathered through perm; the launcher keeps it below 2 GB so that OOR is out
+    // of range), the overhead buffer this workgroup's rows.
+    __amdgpu_buffer_rsrc_t su_rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.su, 0, (unsigned)p.Bs * 64u * We * 4u, 0x00020000);
+    const int ov_here = min(FX_TN, p.Bo - o0);
+    __amdgpu_buffer_rsrc_t ov_rs =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(p.ov + (size_t)o0 * 4096), 0, (unsigned)ov_here * 4096u * 4u, 0x00020000);
+    const int lrr = lane / WP, lk = lane % WP;
+    const bool kin = lk < We;
+    unsigned suoff[8 * MT];
+#pragma unroll
+    for (int i = 0; i < 8 * MT; ++i) {
+        const int m = wave + 4 * i;
+        const int s = (m < rows) ? __builtin_amdgcn_readfirstlane(p.perm[first + m]) : 0;
+        suoff[i] = (kin && m < rows) ? ((unsigned)s * 64u * We + lrr * We + lk) * 4u : OOR;
+    }
+    const unsigned ovoff = kin ? ((unsigned)wave * 4096u + lrr * 64 + ((lk + shift) & 63)) * 4u : OOR;   // + 4*i overheads: no wrap below 2^32
+
+    float rsu[8 * MT], rov[32];
+    auto load_stage = [&](int st) {
+        const unsigned srow = (unsigned)st * R * We * 4u;
+#pragma unroll
+        for (int i = 0; i < 8 * MT; ++i) rsu[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(su_rs, suoff[i], srow, 0));
+        const unsigned orow = (unsigned)st * R * 256u;
+#pragma unroll
+        for (int i = 0; i < 32; ++i)
+            rov[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ov_rs, ovoff + (unsigned)i * 4u * 4096u * 4u, orow, 0));
+    };
+    auto store_stage = [&]() {
+#pragma unroll
+        for (int i = 0; i < 8 * MT; ++i) smem[(wave + 4 * i) * SUS + lane] = rsu[i];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) smem[(128 + wave + 4 * i) * SUS + lane] = rov[i];
+    };
+
+    f32x16 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+
+    const int arow = l31 * SUS + hk;
+    const int brow = (128 + 32 * wave + l31) * SUS + hk;
+    load_stage(0);
+    for (int st = 0; st < NS; ++st) {
+        __syncthreads();                 // the previous stage has been read by every wave
+        store_stage();
+        __syncthreads();
+        if (st + 1 < NS) load_stage(st + 1);
+#pragma unroll
+        for (int k = 0; k < KS; ++k) {
+            const float b = smem[brow + 2 * k];
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(smem[arow + 32 * m * SUS + 2 * k], b, acc[m], 0, 0, 0);
+        }
+    }
+
+    // ---- epilogue: [overhead][surface] through LDS, then lanes <-> consecutive surfaces of the supertile
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            smem[(32 * wave + l31) * FX_TS + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * hk] = acc[m][r];
+    __syncthreads();
+    constexpr int HALVES = MT > 2 ? 2 : 1;
+    int sg[HALVES];
+    float snv[HALVES];
+#pragma unroll
+    for (int h = 0; h < HALVES; ++h) {
+        const int c = lane + 64 * h;
+        sg[h] = (c < rows) ? p.perm[first + c] : -1;
+        snv[h] = (sg[h] >= 0) ? p.sn[sg[h]] : 1.f;
+    }
+    for (int j = 0; j < 32; ++j) {
+        const int ol = wave + 4 * j, og = o0 + ol;
+        if (og >= p.Bo) break;           // wave-uniform; no barrier follows
+        const float wnv = p.wn[(size_t)og * 64 + shift];
+#pragma unroll
+        for (int h = 0; h < HALVES; ++h) {
+            if (sg[h] < 0) continue;
+            const float v = smem[ol * FX_TS + lane + 64 * h];
+            const size_t off = (size_t)og * p.Bs + sg[h];
+            if (p.orientation) p.orientation[off] = shift;
+            if (p.score) p.score[off] = v;
+            if (p.distance) p.distance[off] = 2.f * (1.f - v / (wnv * snv[h]));
+        }
+    }
+}
+
+template <int WP>
+__global__ __launch_bounds__(NT, 2) void match_fixed_kernel(FixedArgs p) {
+    extern __shared__ float smem[];      // FX_LDS_F floats
+    const int t = blockIdx.x;
+    if (t >= p.tab[0]) return;           // the grid is sized for the worst split into groups; uniform per workgroup
+    const int first = p.tab[1 + 2 * t], info = p.tab[2 + 2 * t];
+    const int rows = info >> 8, shift = info & 63;
+    const int o0 = blockIdx.y * FX_TN;
+    switch ((rows + 31) >> 5) {
+        case 1: fixed_tile<WP, 1>(p, smem, first, rows, shift, o0); break;
+        case 2: fixed_tile<WP, 2>(p, smem, first, rows, shift, o0); break;
+        case 3: fixed_tile<WP, 3>(p, smem, first, rows, shift, o0); break;
+        default: fixed_tile<WP, 4>(p, smem, first, rows, shift, o0); break;
+    }
+}
+
 }  // namespace
 
 static int g_match_pairs_impl = 1;      // witw_match_pairs_impl
@@ -1276,6 +1481,57 @@ int witw_match_fwd_masked(const float* ov, const float* su, int Bo, int Bs, int 
                           float* score, float* workspace, const unsigned long long* shift_mask, void* stream) {
     if (!shift_mask) return match_fwd_launch<false>(ov, su, Bo, Bs, We, orientation, distance, score, workspace, nullptr, stream);
     return match_fwd_launch<true>(ov, su, Bo, Bs, We, orientation, distance, score, workspace, shift_mask, stream);
+}
+
+// ---- witw_match_fwd_fixed: the match at ONE known shift per surface (shift[s] & 63; [Bs] int64 on the device), 1/64 of the products
+// of witw_match_fwd_masked under one-bit words and the same bits in distance / score. The workspace starts with the norms of a
+// witw_match_fwd workspace (wn [Bo,64], sn [Bs]: witw_match_bwd* / witw_match_pairs* read it unchanged); the supertile table and the
+// permutation of fixed_group_kernel follow.
+static int fixed_tab_ints(int Bs) { return 1 + 2 * fixed_max_tiles(Bs, 32); }
+
+long long witw_match_fixed_workspace_floats(int Bo, int Bs) {
+    if (Bo <= 0 || Bs <= 0) return -1;
+    return (long long)Bo * 64 + Bs + fixed_tab_ints(Bs) + Bs;
+}
+
+int witw_match_fwd_fixed(const float* ov, const float* su, int Bo, int Bs, int We, const long long* shift, long long* orientation,
+                         float* distance, float* score, float* workspace, void* stream) {
+    WITW_CHECK_ARG(ov && su && workspace && shift, "match_fwd_fixed: null pointer");
+    WITW_CHECK_ARG(Bo > 0 && Bs > 0, "match_fwd_fixed: empty batch Bo=%d Bs=%d", Bo, Bs);
+    WITW_CHECK_ARG(We >= 1 && We <= 64, "match_fwd_fixed: surface embedding width %d outside [1,64]", We);
+    WITW_CHECK_ARG((long long)Bs * 64 * We * 4 <= 0x40000000LL, "match_fwd_fixed: %d surfaces of width %d exceed 1 GiB; match them in chunks", Bs, We);
+    WITW_CHECK_ARG(cdiv(Bo, FX_TN) <= 65535, "match_fwd_fixed: too many overhead rows Bo=%d", Bo);
+    hipStream_t st = (hipStream_t)stream;
+    float* wn = workspace;
+    float* sn = workspace + (size_t)Bo * 64;
+    int* tab = reinterpret_cast<int*>(sn + Bs);
+    int* perm = tab + fixed_tab_ints(Bs);
+    hipLaunchKernelGGL(window_norm_kernel, dim3(Bo), dim3(256), 0, st, ov, wn, We);
+    hipLaunchKernelGGL(row_norm_kernel, dim3(Bs), dim3(256), 0, st, su, sn, 64 * We);
+    // surfaces per supertile: 128 when that still makes two workgroups per CU, else fewer (a minibatch: 32, every wave one tile)
+    int sm = 4;
+    while (sm > 1 && (long long)cdiv(Bs, 32 * sm) * cdiv(Bo, FX_TN) < 2LL * witw_cu_count()) sm >>= 1;
+    hipLaunchKernelGGL(fixed_group_kernel, dim3(1), dim3(256), 0, st, shift, Bs, 32 * sm, tab, perm);
+    FixedArgs a;
+    a.ov = ov; a.su = su; a.wn = wn; a.sn = sn; a.tab = tab; a.perm = perm;
+    a.orientation = orientation; a.distance = distance; a.score = score;
+    a.Bo = Bo; a.Bs = Bs; a.We = We;
+    const dim3 grid(fixed_max_tiles(Bs, 32 * sm), cdiv(Bo, FX_TN));
+    constexpr size_t lds = FX_LDS_F * sizeof(float);
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_fixed_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_fixed_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_fixed_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_set = true;
+    }
+    const int wp = We <= 16 ? 16 : We <= 32 ? 32 : 64;
+    if (wp == 16) hipLaunchKernelGGL((match_fixed_kernel<16>), grid, dim3(NT), lds, st, a);
+    else if (wp == 32) hipLaunchKernelGGL((match_fixed_kernel<32>), grid, dim3(NT), lds, st, a);
+    else hipLaunchKernelGGL((match_fixed_kernel<64>), grid, dim3(NT), lds, st, a);
+    witw_note_variant("match_fixed_kernel<%d>", wp);
+    WITW_CHECK_LAUNCH("match_fwd_fixed");
+    return WITW_OK;
 }
 
 // grad_distance [Bo,Bs] -> grad_ov [Bo,16,4,64], grad_su [Bs,16,4,We]. orientation / score / workspace are

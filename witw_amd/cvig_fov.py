@@ -605,11 +605,62 @@ def _query_mask(shift_mask, surface_embed):
     return shift_mask.to(surface_embed.device).contiguous()
 
 
-def correlation(overhead_embed, surface_embed, shift_mask=None):
+def orientation_shift(center_deg, output_width_max=64):
+    """A KNOWN orientation as the `known_shift=` of the matching functions: int64 [Bs] ([1] for a scalar), the shift nearest to
+    center_deg in the degrees of orientation_mask (deg(k) = k * 360 / output_width_max - 180), the lower one of two equally near:
+    1 << orientation_shift(c) is the word orientation_mask(c, 0) (read as uint64) for every c. A CPU tensor, computed in fp64."""
+    import numpy as np
+    W = int(output_width_max)
+    if not 1 <= W <= 64:
+        raise _lib.WitwError('orientation_shift: output_width_max must lie in [1, 64], got %r' % (output_width_max,))
+    c = np.atleast_1d(np.asarray(center_deg.detach().cpu().numpy() if isinstance(center_deg, torch.Tensor) else center_deg,
+                                 dtype=np.float64))
+    if c.ndim != 1 or not np.isfinite(c).all():
+        raise _lib.WitwError('orientation_shift: center_deg must be a finite scalar or [Bs], got shape %s' % (c.shape,))
+    deg = np.arange(W, dtype=np.float64) * 360. / W - 180.
+    dist = np.abs((deg[None, :] - c[:, None] + 180.) % 360. - 180.)          # the circular distance orientation_mask measures
+    return torch.from_numpy(dist.argmin(axis=1).astype(np.int64))
+
+
+def _query_shift(known_shift, shift_mask, surface_embed):
+    """`known_shift` of a matching function as ops.match_fwd_fixed wants it: int64 [Bs], contiguous, on the queries' device."""
+    if known_shift is None:
+        return None
+    if shift_mask is not None:
+        raise _lib.WitwError('known_shift and shift_mask are mutually exclusive: a known orientation is one shift per query, '
+                             'a mask a set of them')
+    if not (isinstance(known_shift, torch.Tensor) and known_shift.dtype == torch.int64 and known_shift.dim() == 1
+            and known_shift.shape[0] == surface_embed.shape[0]):
+        raise _lib.WitwError('known_shift must be an int64 tensor with one shift per query ([%d]), got %s' % (
+            surface_embed.shape[0], (tuple(known_shift.shape), known_shift.dtype) if isinstance(known_shift, torch.Tensor)
+            else type(known_shift)))
+    return known_shift.to(surface_embed.device).contiguous()
+
+
+def _match_fwd(kn, ov, su, shift_mask=None, known_shift=None, **kw):
+    """kn.match_fwd, under a mask when one is given, or kn.match_fwd_fixed at known shifts (the keywords are passed only when set:
+    injected op sets of the CPU tests need not know them)."""
+    if known_shift is not None:
+        return kn.match_fwd_fixed(ov, su, known_shift, **kw)
+    if shift_mask is not None:
+        kw['shift_mask'] = shift_mask
+    return kn.match_fwd(ov, su, **kw)
+
+
+def _prior(shift_mask, known_shift, q0=None, q1=None):
+    """the keywords of _match_fwd for the queries [q0, q1) (all of them without bounds)"""
+    cut = (lambda t: t) if q0 is None else (lambda t: t[q0:q1].contiguous())
+    if known_shift is not None:
+        return {'known_shift': cut(known_shift)}
+    return {} if shift_mask is None else {'shift_mask': cut(shift_mask)}
+
+
+def correlation(overhead_embed, surface_embed, shift_mask=None, known_shift=None):
     """model/cvig_fov.py:297-315 -> int64 [Bo,Bs]. shift_mask (int64 [Bs], see orientation_mask): the arg-max runs over the
-    shifts the query's word allows."""
-    return ops.match_fwd(overhead_embed.contiguous(), surface_embed.contiguous(),
-                         shift_mask=_query_mask(shift_mask, surface_embed))[0]
+    shifts the query's word allows. known_shift (int64 [Bs], see orientation_shift): the orientation is given."""
+    known_shift = _query_shift(known_shift, shift_mask, surface_embed)
+    return _match_fwd(ops, overhead_embed.contiguous(), surface_embed.contiguous(), _query_mask(shift_mask, surface_embed),
+                      known_shift)[0]
 
 
 def crop_overhead(overhead_embed, orientation, surface_width):
@@ -624,9 +675,9 @@ def l2_distance(overhead_cropped, surface_embed):
 
 class _MatchFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, overhead_embed, surface_embed, shift_mask=None):
+    def forward(ctx, overhead_embed, surface_embed, shift_mask=None, known_shift=None):
         ov, su = overhead_embed.contiguous(), surface_embed.contiguous()
-        ori, dist, score, ws = ops.match_fwd(ov, su, want_score=True, want_workspace=True, shift_mask=shift_mask)
+        ori, dist, score, ws = _match_fwd(ops, ov, su, shift_mask, known_shift, want_score=True, want_workspace=True)
         ctx.save_for_backward(ov, su, ori, score, ws)
         ctx.mark_non_differentiable(ori)
         return ori, dist
@@ -636,18 +687,22 @@ class _MatchFn(torch.autograd.Function):
         ov, su, ori, score, ws = ctx.saved_tensors
         gov, gsu = ops.match_bwd(ov, su, ori, score, ws, g_dist.contiguous(), ctx.needs_input_grad[0],
                                  ctx.needs_input_grad[1])
-        return gov, gsu, None
+        return gov, gsu, None, None
 
 
-def match(overhead_embed, surface_embed, shift_mask=None):
+def match(overhead_embed, surface_embed, shift_mask=None, known_shift=None):
     """correlation -> crop_overhead -> l2_distance fused (no crop tensor): (orientation, distance).
     Differentiable w.r.t. both embeddings (the arg-max orientation is a constant, as in the reference).
     shift_mask (int64 [Bs], see orientation_mask): the orientation is the first maximum over the shifts the query's word allows,
-    the distance is taken there; the backward consumes that orientation as it does the unrestricted one."""
+    the distance is taken there; the backward consumes that orientation as it does the unrestricted one.
+    known_shift (int64 [Bs], see orientation_shift; excludes shift_mask): every query is matched at its one given shift
+    (ops.match_fwd_fixed: 1/64 of the products) -- orientation, distance and both gradients carry the bits of
+    shift_mask = 1 << known_shift; the backward is the same ops.match_bwd on what the fixed forward left."""
+    known_shift = _query_shift(known_shift, shift_mask, surface_embed)
     shift_mask = _query_mask(shift_mask, surface_embed)
     if torch.is_grad_enabled() and (overhead_embed.requires_grad or surface_embed.requires_grad):
-        return _MatchFn.apply(overhead_embed, surface_embed, shift_mask)
-    return ops.match_fwd(overhead_embed.contiguous(), surface_embed.contiguous(), shift_mask=shift_mask)
+        return _MatchFn.apply(overhead_embed, surface_embed, shift_mask, known_shift)
+    return _match_fwd(ops, overhead_embed.contiguous(), surface_embed.contiguous(), shift_mask, known_shift)
 
 
 class Adam(object):
@@ -738,17 +793,17 @@ def batch_hard_triplet_loss(distances, alpha=10.):
     return _BatchHardTripletLoss.apply(distances, float(alpha))
 
 
-def ranks(overhead_embed, surface_embed, shift_mask=None):
+def ranks(overhead_embed, surface_embed, shift_mask=None, known_shift=None):
     """Ranking loop of test() (model/cvig_fov.py:543-552) for all queries at once: int64 [N] on
-    the host, rank = #{gallery : d <= d_true} with gallery index == query index. shift_mask: see match()."""
-    _, dist = match(overhead_embed, surface_embed, shift_mask)
+    the host, rank = #{gallery : d <= d_true} with gallery index == query index. shift_mask / known_shift: see match()."""
+    _, dist = match(overhead_embed, surface_embed, shift_mask, known_shift)
     return ops.rank_count(dist, 0).cpu().numpy().astype('int64')
 
 
 SPECTRAL_FROM = 8192      # evaluation sets from this many pairs on rank through the spectral pass under match_method 'auto'
 
 
-def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, method='auto', shift_mask=None):
+def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, method='auto', shift_mask=None, known_shift=None):
     """The ranks test() tabulates (model/cvig_fov.py:543-552), int64 [N] on the host, identical on every rank. `overhead_embed` /
     `surface_embed` are THIS rank's rows (world > 1: queries are replicated, gallery rows stay sharded). method:
     'direct' = the fused correlation kernel on every (gallery, query) pair (2*64*E FLOP each); 'dft' = the spectral pass
@@ -757,10 +812,23 @@ def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, meth
     36 s direct / 2 s spectral.
     shift_mask: int64, one word per query of the WHOLE evaluation set (all ranks' rows, in order), see orientation_mask. The
     masked spectral pass is method 'dft_masked' (retrieve(): the same ranks as 'direct' under the same mask; without a mask it is
-    'dft'); with a mask 'auto' still means 'direct' and an explicit 'dft' is an error."""
+    'dft'); with a mask 'auto' still means 'direct' and an explicit 'dft' is an error.
+    known_shift: int64, one shift per query of the WHOLE evaluation set (orientation_shift; excludes shift_mask): the ranks of
+    shift_mask = 1 << known_shift at 1/64 of the products. method 'fixed' (requires it) is retrieve()'s chunked pass on the fixed
+    kernel; 'direct' / 'auto' match through it too; the spectral methods refuse it."""
     from . import parallel
-    if method not in ('auto', 'direct', 'dft', 'dft_masked'):
-        raise _lib.WitwError("match_method must be 'auto', 'direct', 'dft' or 'dft_masked', got %r" % (method,))
+    if method not in ('auto', 'direct', 'dft', 'dft_masked', 'fixed'):
+        raise _lib.WitwError("match_method must be 'auto', 'direct', 'dft', 'dft_masked' or 'fixed', got %r" % (method,))
+    if known_shift is not None and shift_mask is not None:
+        raise _lib.WitwError('evaluation_ranks: known_shift and shift_mask are mutually exclusive')
+    if method == 'fixed' and known_shift is None:
+        raise _lib.WitwError("evaluation_ranks: method='fixed' requires known_shift")
+    if known_shift is not None:
+        if method in ('dft', 'dft_masked'):
+            raise _lib.WitwError("evaluation_ranks: known_shift is not supported by the spectral pass (method=%r); use 'fixed'"
+                                 % (method,))
+        if method == 'auto':
+            method = 'direct'
     if shift_mask is not None:
         if method == 'dft':
             raise _lib.WitwError("evaluation_ranks: shift_mask is not supported by the spectral pass (method='dft'); use "
@@ -773,19 +841,26 @@ def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, meth
     if method in ('dft', 'dft_masked'):
         masked = {} if shift_mask is None else {'shift_mask': shift_mask}
         return retrieve(overhead_embed, surface_all, k=1, shard_begin=shard_begin, method=method, **masked)[0]
+    if method == 'fixed':
+        return retrieve(overhead_embed, surface_all, k=1, shard_begin=shard_begin, method='fixed', known_shift=known_shift)[0]
     if world > 1:
-        return sharded_ranks(overhead_embed, surface_all, shard_begin, shift_mask=shift_mask)
-    return ranks(overhead_embed, surface_embed, shift_mask)
+        return sharded_ranks(overhead_embed, surface_all, shard_begin, **_prior(shift_mask, known_shift))
+    return ranks(overhead_embed, surface_embed, shift_mask, known_shift)
 
 
-def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _match=None, _count=None, shift_mask=None):
+def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _match=None, _count=None, shift_mask=None,
+                  known_shift=None):
     """Ranking with the GALLERY sharded by rows across ranks: this rank holds
     overhead_shard = gallery rows [shard_begin, shard_begin+n); queries (replicated) match gallery row
     == query index. The owner of each true row publishes its distance (all-reduce of a vector that is
     zero elsewhere), every rank counts d <= d_true over its shard, counts are summed. Returns int64 [N]
     on the host, identical on every rank and identical to ranks() on one GPU. shift_mask (int64 [N], one word per query, see
-    orientation_mask): every query chunk is matched under its own slice of it."""
+    orientation_mask): every query chunk is matched under its own slice of it. known_shift (int64 [N], excludes shift_mask):
+    every chunk runs on ops.match_fwd_fixed at its slice of the shifts (an injected _match is called with known_shift=)."""
     from . import parallel
+    known_shift = _query_shift(known_shift, shift_mask, surface_all)
+    if known_shift is not None and _match is None:
+        _match = lambda ov, su, known_shift: ops.match_fwd_fixed(ov, su, known_shift)
     _match = _match or ops.match_fwd                 # injectable so the collective algebra is testable on CPU/gloo
     _count = _count or ops.rank_count_thresh
     shift_mask = _query_mask(shift_mask, surface_all)
@@ -797,7 +872,7 @@ def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _m
         if n_g == 0:         # a rank without gallery rows still takes part in the exchanges
             parallel.all_reduce_sum_(torch.zeros((q1 - q0,), dtype=torch.float32, device=surface_all.device))
             continue
-        masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
+        masked = _prior(shift_mask, known_shift, q0, q1)
         _, dist = _match(overhead_shard.contiguous(), surface_all[q0:q1].contiguous(), **masked)   # [n_g, q]
         qi = torch.arange(q0, q1, device=dist.device)
         own = (qi >= shard_begin) & (qi < shard_begin + n_g)
@@ -810,13 +885,14 @@ def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _m
 
 
 def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='direct', _kernels=None,
-                  shift_mask=None):
+                  shift_mask=None, known_shift=None):
     """Top-k retrieval (BASELINE config C5): for every query the k nearest gallery rows by the fused
     orientation-search chord distance, ordered by (distance, gallery index). With the gallery sharded over
     ranks each rank ranks its shard, the [N,k] candidate lists are all-gathered and merged by the same kernel.
-    -> (distances f32 [N,k], gallery indices int64 [N,k]) on the device, identical on every rank. shift_mask: see retrieve()."""
+    -> (distances f32 [N,k], gallery indices int64 [N,k]) on the device, identical on every rank. shift_mask / known_shift: see
+    retrieve()."""
     return retrieve(overhead_shard, surface_all, k, shard_begin, query_chunk, method, _kernels, _want_ranks=False,
-                    shift_mask=shift_mask)[1:]
+                    shift_mask=shift_mask, known_shift=known_shift)[1:]
 
 
 def _merge_topk(v, i, k, _kernels=None):
@@ -840,7 +916,7 @@ def _merge_topk(v, i, k, _kernels=None):
 
 
 def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='direct', _kernels=None,
-             _want_ranks=True, shift_mask=None):
+             _want_ranks=True, shift_mask=None, known_shift=None):
     """sharded_ranks + retrieve_topk from ONE matching pass per query chunk (config C5: the pass is
     2*64*E FLOP per (gallery row, query) and dominates). -> (ranks int64 [N] on the host, distances f32 [N,k],
     gallery indices int64 [N,k] on the device), identical on every rank. The gallery may be sharded raggedly (any
@@ -852,9 +928,21 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     shift_mask (int64 [N], one word per query, see orientation_mask): every query chunk is matched under its own slice of it.
     method='dft_masked' is the spectral pass under a mask (witw_match_fwd_dft_masked, every re-scoring through
     witw_match_pairs_masked): ranks and top-k indices equal method='direct' with the same mask; without a mask it is 'dft'.
-    'dft' itself keeps refusing a mask and 'auto' with a mask keeps meaning 'direct'."""
+    'dft' itself keeps refusing a mask and 'auto' with a mask keeps meaning 'direct'.
+    known_shift (int64 [N], one shift per query, see orientation_shift; excludes shift_mask): method='fixed' (which requires it)
+    is this chunked pass with ops.match_fwd_fixed -- 2*E FLOP per pair, no spectra, no band, no re-scoring -- feeding the same
+    rank-count and top-k kernels: ranks, distances and indices equal method='direct' under shift_mask = 1 << known_shift exactly.
+    'direct' / 'auto' with known_shift run the same pass; 'dft' / 'dft_masked' refuse it."""
     from . import parallel
     kn = _kernels or ops
+    if method == 'fixed' and known_shift is None:
+        raise _lib.WitwError("retrieve: method='fixed' requires known_shift")
+    if known_shift is not None:
+        if method in ('dft', 'dft_masked'):
+            raise _lib.WitwError("retrieve: known_shift is not supported by the spectral pass (method=%r); use 'fixed'" % (method,))
+        known_shift = _query_shift(known_shift, shift_mask, surface_all)
+        if method in ('auto', 'fixed'):
+            method = 'direct'
     if shift_mask is not None:
         if method == 'dft':
             raise _lib.WitwError("retrieve: shift_mask is not supported by the spectral pass (method='dft'); use 'dft_masked' or "
@@ -873,7 +961,7 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     if spectral:
         return _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, _want_ranks, method=method, **masked)
     if method != 'direct':
-        raise ValueError("retrieve: method must be 'direct', 'dft' or 'dft_masked'")
+        raise ValueError("retrieve: method must be 'direct', 'dft', 'dft_masked' or 'fixed'")
     n_q, n_g = surface_all.shape[0], overhead_shard.shape[0]
     counts = torch.zeros((n_q,), dtype=torch.int32, device=surface_all.device)
     vals, idxs = [], []
@@ -884,8 +972,12 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
         if n_g == 0:        # a rank without gallery rows (more ranks than rows): nothing to match, empty candidate lists
             dist = torch.empty((0, nq), dtype=torch.float32, device=surface_all.device)
         else:
-            masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
-            _, dist = kn.match_fwd(gallery, surface_all[q0:q1].contiguous(), **masked)            # [n_g, q]
+            if known_shift is not None:      # no orientation matrix: it is known_shift broadcast, 8 bytes per pair
+                dist = kn.match_fwd_fixed(gallery, surface_all[q0:q1].contiguous(), known_shift[q0:q1].contiguous(),
+                                          want_orientation=False)[1]
+            else:
+                masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
+                _, dist = kn.match_fwd(gallery, surface_all[q0:q1].contiguous(), **masked)            # [n_g, q]
         if _want_ranks:
             qi = torch.arange(q0, q1, device=dist.device)
             own = (qi >= shard_begin) & (qi < shard_begin + n_g)
@@ -1116,7 +1208,7 @@ class _ShardedMatchLossFn(torch.autograd.Function):
     are complete locally. Same value and gradients as match + triplet_loss on the gathered batch."""
 
     @staticmethod
-    def forward(ctx, overhead_local, surface_local, alpha, k):
+    def forward(ctx, overhead_local, surface_local, alpha, k, known_shift=None):
         from . import parallel
         b = surface_local.shape[0]
         col0 = parallel.rank() * b
@@ -1124,7 +1216,7 @@ class _ShardedMatchLossFn(torch.autograd.Function):
             ov_all = parallel._all_gather_cat(overhead_local.contiguous())
         su = surface_local.contiguous()
         with parallel.phase('slab_match'):
-            ori, dist, score, ws = k.match_fwd(ov_all, su, want_score=True, want_workspace=True)
+            ori, dist, score, ws = _match_fwd(k, ov_all, su, None, known_shift, want_score=True, want_workspace=True)
         B = ov_all.shape[0]
         with parallel.phase('diagonal_all_gather'):
             diag = parallel._all_gather_cat(dist[col0:col0 + b].diagonal().contiguous())
@@ -1149,7 +1241,7 @@ class _ShardedMatchLossFn(torch.autograd.Function):
             gov_all, gsu = k.match_bwd(ov_all, su, ori, score, ws, g_dist, True, True)
         with parallel.phase('overhead_grad_reduce_scatter'):
             gov = parallel.reduce_scatter_rows(gov_all, b)
-        return gov, gsu, None, None
+        return gov, gsu, None, None, None
 
 
 class _BatchHardMatchLossFn(torch.autograd.Function):
@@ -1164,7 +1256,7 @@ class _BatchHardMatchLossFn(torch.autograd.Function):
     rank's surface anchors (global indices)."""
 
     @staticmethod
-    def forward(ctx, overhead_local, surface_local, alpha, k):
+    def forward(ctx, overhead_local, surface_local, alpha, k, known_shift=None):
         from . import parallel
         world = parallel.world()
         b = surface_local.shape[0]
@@ -1176,7 +1268,7 @@ class _BatchHardMatchLossFn(torch.autograd.Function):
         else:
             ov_all = overhead_local.contiguous()
         with parallel.phase('slab_match'):
-            ori, dist, score, ws = k.match_fwd(ov_all, su, want_score=True, want_workspace=True)
+            ori, dist, score, ws = _match_fwd(k, ov_all, su, None, known_shift, want_score=True, want_workspace=True)
         B = ov_all.shape[0]
         if world > 1:
             with parallel.phase('diagonal_all_gather'):
@@ -1202,7 +1294,7 @@ class _BatchHardMatchLossFn(torch.autograd.Function):
     def backward(ctx, g_loss, *_g):
         from . import parallel
         if g_loss is None:
-            return None, None, None, None
+            return None, None, None, None, None
         ov_all, su, ori, score, ws, diag, rv, ri, cv, ci = ctx.saved_tensors
         col0, b, world, alpha, k = ctx.cfg
         with parallel.phase('slab_match_backward'):
@@ -1211,25 +1303,28 @@ class _BatchHardMatchLossFn(torch.autograd.Function):
         if world > 1:
             with parallel.phase('overhead_grad_reduce_scatter'):
                 gov_all = parallel.reduce_scatter_rows(gov_all, b)
-        return gov_all, gsu, None, None
+        return gov_all, gsu, None, None, None
 
 
-def sharded_match_loss(overhead_local, surface_local, alpha=10., _kernels=None, loss='soft_margin', mined=False):
+def sharded_match_loss(overhead_local, surface_local, alpha=10., _kernels=None, loss='soft_margin', mined=False, known_shift=None):
     """(loss, orientation [B,b], distance [B,b]) of the GLOBAL batch from this rank's b pairs; every rank must call it
     with the same b. On one rank it is match + triplet_loss. `_kernels` swaps the op set (CPU tests of the
     collective algebra). loss='batch_hard': the batch-hard soft-margin loss (batch_hard_triplet_loss) over the global batch,
     through _BatchHardMatchLossFn (no dense loss gradient on any rank); mined=True appends the mined
-    (rv [B], ri [B], cv [b], ci [b]) of the global rows and this rank's columns."""
+    (rv [B], ri [B], cv [b], ci [b]) of the global rows and this rank's columns.
+    known_shift (int64 [b], see orientation_shift): the known orientations of THIS rank's b surface columns -- the slab is matched
+    by match_fwd_fixed instead of match_fwd (aligned training); everything behind that call is what it is without it."""
     from . import parallel
+    known_shift = _query_shift(known_shift, None, surface_local)
     if loss == 'batch_hard':
-        out = _BatchHardMatchLossFn.apply(overhead_local, surface_local, float(alpha), _kernels or ops)
+        out = _BatchHardMatchLossFn.apply(overhead_local, surface_local, float(alpha), _kernels or ops, known_shift)
         return out if mined else out[:3]
     if loss != 'soft_margin':
         raise _lib.WitwError("sharded_match_loss: loss must be 'soft_margin' or 'batch_hard', got %r" % (loss,))
     if parallel.world() == 1 and _kernels is None:
-        ori, dist = match(overhead_local, surface_local)
+        ori, dist = match(overhead_local, surface_local, known_shift=known_shift)
         return triplet_loss(dist, alpha), ori, dist.detach()
-    return _ShardedMatchLossFn.apply(overhead_local, surface_local, float(alpha), _kernels or ops)
+    return _ShardedMatchLossFn.apply(overhead_local, surface_local, float(alpha), _kernels or ops, known_shift)
 
 
 class PairEmbedder(object):
@@ -1872,9 +1967,11 @@ def load_vgg16_state_dict(encoder, state):
 
 
 def train(dataset='cvusa', fov=360, val_quantity=1000, batch_size=64, num_workers=12, num_epochs=999999, csv_path=None,
-          seed=0, _mod=None):
+          seed=0, _mod=None, known_orientation=None):
     """model/cvig_fov.py:385-487 on the HIP kernels (same flow, checkpoint names and prints). `_mod` is the
-    module whose Globals / FOV_DSM / ImagePairDataset / GpuPreprocess are used (cvig_semantic passes itself)."""
+    module whose Globals / FOV_DSM / ImagePairDataset / GpuPreprocess are used (cvig_semantic passes itself).
+    known_orientation (not in the reference): degrees of orientation_shift -- the training and the validation loss match every
+    query at that one shift (sharded_match_loss(known_shift=)): the aligned protocol. None: the unrestricted search."""
     import pathlib
     import sys
     import time
@@ -1946,8 +2043,10 @@ def train(dataset='cvusa', fov=360, val_quantity=1000, batch_size=64, num_worker
                     # validation: PairEmbedder (small batches on two streams, bf16 as one hipGraph); training: the plain calls
                     surface_embed, overhead_embed = embed(surface, overhead)
                     # correlation -> crop_overhead -> l2_distance -> triplet_loss (:450-454) over the GLOBAL batch
+                    known = {} if known_orientation is None else {
+                        'known_shift': orientation_shift(known_orientation).expand(surface_embed.size(0)).contiguous()}
                     loss, orientation_estimate, distance = sharded_match_loss(overhead_embed, surface_embed,
-                                                                              loss=getattr(Globals, 'loss', 'soft_margin'))
+                                                                              loss=getattr(Globals, 'loss', 'soft_margin'), **known)
                     if phase == 'train':
                         optimizer.zero_grad()
                         loss.backward()          # per-encoder gradient all-reduce overlapped with the other encoder's backward
@@ -1981,14 +2080,20 @@ def train(dataset='cvusa', fov=360, val_quantity=1000, batch_size=64, num_worker
     return best_loss
 
 
-def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, _mod=None, orientation_window=None):
+def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, _mod=None, orientation_window=None,
+         known_orientation=None):
     """model/cvig_fov.py:490-575: embed the test set, rank every query against the whole gallery (all
     queries at once on the GPU instead of the O(N) Python loop), print the recall table.
     orientation_window (not in the reference): (center_deg, half_width_deg) of orientation_mask, applied to every query --
     the "orientation known" protocol, e.g. north-aligned panoramas cropped with Globals.test_random_orientation = False.
-    None: the unrestricted search over all 64 shifts."""
+    None: the unrestricted search over all 64 shifts.
+    known_orientation (not in the reference; excludes orientation_window): degrees of orientation_shift -- every query is ranked
+    at that one shift (evaluation_ranks(known_shift=)): the ranks of orientation_window=(DEG, 0) at 1/64 of the products;
+    Globals.match_method may then be 'fixed'."""
     import sys
     from datetime import datetime
+    if known_orientation is not None and orientation_window is not None:
+        raise _lib.WitwError('test: known_orientation and orientation_window are mutually exclusive')
     m = _mod or sys.modules[__name__]
     Globals, FOV_DSM, ImagePairDataset, GpuPreprocess, device = m.Globals, m.FOV_DSM, m.ImagePairDataset, m.GpuPreprocess, m.device
     from . import parallel
@@ -2039,8 +2144,11 @@ def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, 
     shift_mask = None
     if orientation_window is not None:
         shift_mask = orientation_mask(orientation_window[0], orientation_window[1]).expand(len(test_set)).contiguous()
+    known_shift = None
+    if known_orientation is not None:
+        known_shift = orientation_shift(known_orientation).expand(len(test_set)).contiguous()
     rk = evaluation_ranks(overhead_embed, surface_embed, shard_begin, world, getattr(Globals, 'match_method', 'auto'),
-                          shift_mask=shift_mask)
+                          shift_mask=shift_mask, known_shift=known_shift)
     t = recall_table(rk)
     count = len(rk)
     if rank != 0:
@@ -2054,11 +2162,11 @@ def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, 
     return t
 
 
-def sweep_scores(overhead_embed, surface_embed, output_width_max=64, shift_mask=None):
+def sweep_scores(overhead_embed, surface_embed, output_width_max=64, shift_mask=None, known_shift=None):
     """The scoring block of tools/heatmap/heatmap.py:172-178 (one photo against N satellite tiles):
-    -> (orientation in degrees, dissimilarity, score = exp(10*(1-d))), each [N] (or [N,Bs]). shift_mask: see match(); the
-    degrees returned here are the ones orientation_mask takes."""
-    ori, dist = match(overhead_embed, surface_embed, shift_mask)
+    -> (orientation in degrees, dissimilarity, score = exp(10*(1-d))), each [N] (or [N,Bs]). shift_mask / known_shift: see match(); the
+    degrees returned here are the ones orientation_mask / orientation_shift take."""
+    ori, dist = match(overhead_embed, surface_embed, shift_mask, known_shift)
     orientations = torch.squeeze(ori) * 360 / output_width_max - 180
     distances = torch.squeeze(dist)
     return orientations, distances, torch.exp(10. * (1. - distances))
@@ -2098,12 +2206,22 @@ def main(argv=None):
                         help='test mode (not in the reference): restrict every query\'s orientation search to the shifts within '
                              'HALFWIDTH degrees of CENTER (degrees of the heat-map CSV: shift k = k*360/64 - 180). '
                              '[Default = all 64 shifts]')
-    parser.add_argument('--match-method', default='auto', choices=['auto', 'direct', 'dft', 'dft_masked'],
+    parser.add_argument('--known-orientation', default=None, type=float, metavar='DEG',
+                        help='(not in the reference) the orientation of every query is KNOWN to be DEG degrees (north-aligned '
+                             'panoramas, a compass heading): test mode ranks every query at that one shift, train mode runs the '
+                             'training and the validation loss under it -- 1/64 of the matching products. Excludes '
+                             '--orientation-window. [Default = search all 64 shifts]')
+    parser.add_argument('--match-method', default='auto', choices=['auto', 'direct', 'dft', 'dft_masked', 'fixed'],
                         help='test mode (not in the reference): how the queries are ranked against the gallery. direct = the '
                              'correlation sum on every pair, dft = the spectral pass with exact re-scoring (same ranks), dft_masked '
                              '= the spectral pass that also takes --orientation-window, auto = dft on large sets without a window, '
-                             'direct otherwise. [Default = auto]')
+                             'direct otherwise, fixed = the one-shift pass of --known-orientation (which it requires). '
+                             '[Default = auto]')
     args = parser.parse_args(argv)
+    if args.known_orientation is not None and args.orientation_window is not None:
+        parser.error('--known-orientation and --orientation-window are mutually exclusive')
+    if args.match_method == 'fixed' and args.known_orientation is None:
+        parser.error('--match-method fixed requires --known-orientation')
     print(args)
     Globals.match_method = args.match_method
     Globals.precision = args.precision
@@ -2111,9 +2229,10 @@ def main(argv=None):
     Globals.loss = args.loss
     init_distributed()
     if args.mode == 'train':
-        train(dataset=args.dataset, fov=args.fov)
+        train(dataset=args.dataset, fov=args.fov, known_orientation=args.known_orientation)
     elif args.mode == 'test':
-        test(dataset=args.dataset, fov=args.fov, orientation_window=args.orientation_window)
+        test(dataset=args.dataset, fov=args.fov, orientation_window=args.orientation_window,
+             known_orientation=args.known_orientation)
 
 
 def init_distributed(backend='nccl'):

@@ -240,8 +240,11 @@ def sweep(aoi, bounds, edge, offset, fov, sat_dir, photo_path, csv_path, tile_so
         photo = cvig.ImagePairDataset._read(photo_path)
     surface_embed = embed_photo(surface_encoder, photo, fov)
     overhead_embed = embed_tiles(overhead_encoder, tile_source, windows, batch_size)
-    shift_mask = None if window is None else cvig.orientation_mask(window[0], window[1])     # one photo: one word
-    orientations, distances, scores = cvig.sweep_scores(overhead_embed, surface_embed, shift_mask=shift_mask)
+    if window is not None and window[1] == 0:      # a trusted heading: one shift, the fixed match (the bits of the one-bit word)
+        prior = {'known_shift': cvig.orientation_shift(window[0])}
+    else:
+        prior = {'shift_mask': None if window is None else cvig.orientation_mask(window[0], window[1])}     # one photo: one word
+    orientations, distances, scores = cvig.sweep_scores(overhead_embed, surface_embed, **prior)
     df = pd.DataFrame({'x': center_eastings, 'y': center_northings, 'orientation': orientations.cpu().numpy().reshape(-1),
                        'dissimilarity': distances.cpu().numpy().reshape(-1), 'score': scores.cpu().numpy().reshape(-1)})
     df.to_csv(csv_path, index=False)

@@ -568,6 +568,39 @@ def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=Fa
     return (ori, dist, score) if want_score else (ori, dist)
 
 
+def match_fwd_fixed(overhead_embed, surface_embed, shift, want_score=False, want_workspace=False, want_orientation=True):
+    """match_fwd at a KNOWN orientation (witw_match_fwd_fixed): shift int64 [Bs] on the embeddings' device gives every surface
+    embedding its one shift (used as shift & 63), so a pair costs 2*64*We FLOP instead of 64 times that. Returns what match_fwd
+    returns -- orientation ([Bo,Bs], = shift & 63 broadcast; None with want_orientation=False, which spares its 8 bytes per pair),
+    distance[, score][, workspace] -- with distance and score bit-identical to match_fwd(..., shift_mask=1 << (shift & 63)). The
+    workspace begins with the norms match_bwd / match_pairs read."""
+    lib = _lib.load()
+    ov = _dev_f32(overhead_embed, 'overhead_embed')
+    su = _dev_f32(surface_embed, 'surface_embed')
+    if ov.dim() != 4 or su.dim() != 4 or ov.shape[1] * ov.shape[2] != 64 or ov.shape[3] != 64:
+        raise _lib.WitwError('match_fwd_fixed: overhead embedding must be [Bo,16,4,64], got %s' % (tuple(ov.shape),))
+    if su.shape[1] != ov.shape[1] or su.shape[2] != ov.shape[2]:
+        raise _lib.WitwError('match_fwd_fixed: surface embedding %s does not match overhead %s' % (tuple(su.shape), tuple(ov.shape)))
+    Bo, Bs, We = ov.shape[0], su.shape[0], su.shape[3]
+    if not (isinstance(shift, torch.Tensor) and shift.dtype == torch.int64 and shift.device == ov.device
+            and tuple(shift.shape) == (Bs,) and shift.is_contiguous()):
+        raise _lib.WitwError('match_fwd_fixed: shift must be a contiguous int64 [%d] tensor on %s, got %s'
+                             % (Bs, ov.device, (tuple(shift.shape), shift.dtype, shift.device)
+                                if isinstance(shift, torch.Tensor) else type(shift)))
+    ori = torch.empty((Bo, Bs), dtype=torch.int64, device=ov.device) if want_orientation else None
+    dist = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device)
+    score = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device) if want_score else None
+    ws = torch.empty(lib.witw_match_fixed_workspace_floats(Bo, Bs), dtype=torch.float32, device=ov.device)
+    prof = _prof_begin()
+    _lib.check(lib.witw_match_fwd_fixed(ov.data_ptr(), su.data_ptr(), Bo, Bs, We, shift.data_ptr(), _p(ori), dist.data_ptr(),
+                                        _p(score), ws.data_ptr(), _stream()), 'witw_match_fwd_fixed')
+    if prof is not None:
+        _prof_end(prof, ('match_fixed', We), 2.0 * (64 * We) * Bo * Bs)
+    if want_workspace:
+        return ori, dist, score, ws
+    return (ori, dist, score) if want_score else (ori, dist)
+
+
 SPECTRA_ALIGN = 32      # an overhead row's stored chunk order depends on bit 4 of its index (csrc/match_dft.hip:331)
 
 
