@@ -7,6 +7,7 @@ hand-written HIP kernels (witw_amd/csrc) behind the C ABI of include/witw_hip.h.
 CPU path: tensors must live on the gfx950 device.
 """
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -593,18 +594,6 @@ def orientation_mask(center_deg, half_width_deg, output_width_max=64):
     return torch.from_numpy(words.view(np.int64).copy())
 
 
-def _query_mask(shift_mask, surface_embed):
-    """`shift_mask` of a matching function as ops.match_fwd wants it: int64 [Bs], contiguous, on the queries' device."""
-    if shift_mask is None:
-        return None
-    if not (isinstance(shift_mask, torch.Tensor) and shift_mask.dtype == torch.int64 and shift_mask.dim() == 1
-            and shift_mask.shape[0] == surface_embed.shape[0]):
-        raise _lib.WitwError('shift_mask must be an int64 tensor with one word per query ([%d]), got %s' % (
-            surface_embed.shape[0], (tuple(shift_mask.shape), shift_mask.dtype) if isinstance(shift_mask, torch.Tensor)
-            else type(shift_mask)))
-    return shift_mask.to(surface_embed.device).contiguous()
-
-
 def orientation_shift(center_deg, output_width_max=64):
     """A KNOWN orientation as the `known_shift=` of the matching functions: int64 [Bs] ([1] for a scalar), the shift nearest to
     center_deg in the degrees of orientation_mask (deg(k) = k * 360 / output_width_max - 180), the lower one of two equally near:
@@ -622,45 +611,69 @@ def orientation_shift(center_deg, output_width_max=64):
     return torch.from_numpy(dist.argmin(axis=1).astype(np.int64))
 
 
-def _query_shift(known_shift, shift_mask, surface_embed):
-    """`known_shift` of a matching function as ops.match_fwd_fixed wants it: int64 [Bs], contiguous, on the queries' device."""
-    if known_shift is None:
-        return None
-    if shift_mask is not None:
-        raise _lib.WitwError('known_shift and shift_mask are mutually exclusive: a known orientation is one shift per query, '
-                             'a mask a set of them')
-    if not (isinstance(known_shift, torch.Tensor) and known_shift.dtype == torch.int64 and known_shift.dim() == 1
-            and known_shift.shape[0] == surface_embed.shape[0]):
-        raise _lib.WitwError('known_shift must be an int64 tensor with one shift per query ([%d]), got %s' % (
-            surface_embed.shape[0], (tuple(known_shift.shape), known_shift.dtype) if isinstance(known_shift, torch.Tensor)
-            else type(known_shift)))
-    return known_shift.to(surface_embed.device).contiguous()
+class _Prior(object):
+    """What is known about each query's orientation: nothing, a set of shifts per query (`mask`: int64 [Bs], orientation_mask) or
+    the one shift (`shift`: int64 [Bs], orientation_shift) -- at most one of the two, validated, contiguous and on the queries'
+    device. The public matching functions build it at their entry (_Prior.of) and everything below them passes this one object;
+    a further kind of prior is added here."""
+    __slots__ = ('mask', 'shift')
+
+    def __init__(self, mask=None, shift=None):
+        self.mask, self.shift = mask, shift
+
+    @staticmethod
+    def of(shift_mask, known_shift, surface_embed=None):
+        """the prior of a matching function's `shift_mask=` / `known_shift=` over the queries surface_embed (None: the queries
+        are not at hand yet -- only the kind of prior is settled, the entry that sees them checks the rest)"""
+        if shift_mask is None and known_shift is None:
+            return _NO_PRIOR                     # shared: the training step pays no allocation and no tensor op for it
+        if shift_mask is not None and known_shift is not None:
+            raise _lib.WitwError('known_shift and shift_mask are mutually exclusive: a known orientation is one shift per query, '
+                                 'a mask a set of them')
+        name, one, t = ('shift_mask', 'word', shift_mask) if known_shift is None else ('known_shift', 'shift', known_shift)
+        if surface_embed is not None:
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == surface_embed.shape[0]):
+                raise _lib.WitwError('%s must be an int64 tensor with one %s per query ([%d]), got %s' % (
+                    name, one, surface_embed.shape[0], (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t)))
+            t = t.to(surface_embed.device).contiguous()
+        return _Prior(mask=t) if known_shift is None else _Prior(shift=t)
+
+    def _each(self, cut):
+        if self.shift is not None:
+            return _Prior(shift=cut(self.shift).contiguous())
+        return self if self.mask is None else _Prior(mask=cut(self.mask).contiguous())
+
+    def rows(self, q0, q1):
+        """the prior of the queries [q0, q1)"""
+        return self._each(lambda t: t[q0:q1])
+
+    def take(self, index):
+        """the prior of the queries gathered by `index`"""
+        return self._each(lambda t: t[index])
+
+    def kw(self):
+        """the keyword an op set (or a public matching function) takes it as -- none without a prior: injected op sets of the
+        CPU tests need not know the keywords"""
+        if self.shift is not None:
+            return {'known_shift': self.shift}
+        return {} if self.mask is None else {'shift_mask': self.mask}
+
+    def match_fwd(self, kn, ov, su, want_orientation=True, **kw):
+        """kn.match_fwd, under the mask when there is one, or kn.match_fwd_fixed at the known shifts (which alone can spare the
+        orientation matrix: there it is the shift broadcast, 8 bytes per pair)"""
+        if self.shift is not None:
+            return kn.match_fwd_fixed(ov, su, self.shift, want_orientation=want_orientation, **kw)
+        return kn.match_fwd(ov, su, **self.kw(), **kw)
 
 
-def _match_fwd(kn, ov, su, shift_mask=None, known_shift=None, **kw):
-    """kn.match_fwd, under a mask when one is given, or kn.match_fwd_fixed at known shifts (the keywords are passed only when set:
-    injected op sets of the CPU tests need not know them)."""
-    if known_shift is not None:
-        return kn.match_fwd_fixed(ov, su, known_shift, **kw)
-    if shift_mask is not None:
-        kw['shift_mask'] = shift_mask
-    return kn.match_fwd(ov, su, **kw)
-
-
-def _prior(shift_mask, known_shift, q0=None, q1=None):
-    """the keywords of _match_fwd for the queries [q0, q1) (all of them without bounds)"""
-    cut = (lambda t: t) if q0 is None else (lambda t: t[q0:q1].contiguous())
-    if known_shift is not None:
-        return {'known_shift': cut(known_shift)}
-    return {} if shift_mask is None else {'shift_mask': cut(shift_mask)}
+_NO_PRIOR = _Prior()
 
 
 def correlation(overhead_embed, surface_embed, shift_mask=None, known_shift=None):
     """model/cvig_fov.py:297-315 -> int64 [Bo,Bs]. shift_mask (int64 [Bs], see orientation_mask): the arg-max runs over the
     shifts the query's word allows. known_shift (int64 [Bs], see orientation_shift): the orientation is given."""
-    known_shift = _query_shift(known_shift, shift_mask, surface_embed)
-    return _match_fwd(ops, overhead_embed.contiguous(), surface_embed.contiguous(), _query_mask(shift_mask, surface_embed),
-                      known_shift)[0]
+    prior = _Prior.of(shift_mask, known_shift, surface_embed)
+    return prior.match_fwd(ops, overhead_embed.contiguous(), surface_embed.contiguous())[0]
 
 
 def crop_overhead(overhead_embed, orientation, surface_width):
@@ -675,9 +688,9 @@ def l2_distance(overhead_cropped, surface_embed):
 
 class _MatchFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, overhead_embed, surface_embed, shift_mask=None, known_shift=None):
+    def forward(ctx, overhead_embed, surface_embed, prior):
         ov, su = overhead_embed.contiguous(), surface_embed.contiguous()
-        ori, dist, score, ws = _match_fwd(ops, ov, su, shift_mask, known_shift, want_score=True, want_workspace=True)
+        ori, dist, score, ws = prior.match_fwd(ops, ov, su, want_score=True, want_workspace=True)
         ctx.save_for_backward(ov, su, ori, score, ws)
         ctx.mark_non_differentiable(ori)
         return ori, dist
@@ -687,7 +700,7 @@ class _MatchFn(torch.autograd.Function):
         ov, su, ori, score, ws = ctx.saved_tensors
         gov, gsu = ops.match_bwd(ov, su, ori, score, ws, g_dist.contiguous(), ctx.needs_input_grad[0],
                                  ctx.needs_input_grad[1])
-        return gov, gsu, None, None
+        return gov, gsu, None
 
 
 def match(overhead_embed, surface_embed, shift_mask=None, known_shift=None):
@@ -698,11 +711,10 @@ def match(overhead_embed, surface_embed, shift_mask=None, known_shift=None):
     known_shift (int64 [Bs], see orientation_shift; excludes shift_mask): every query is matched at its one given shift
     (ops.match_fwd_fixed: 1/64 of the products) -- orientation, distance and both gradients carry the bits of
     shift_mask = 1 << known_shift; the backward is the same ops.match_bwd on what the fixed forward left."""
-    known_shift = _query_shift(known_shift, shift_mask, surface_embed)
-    shift_mask = _query_mask(shift_mask, surface_embed)
+    prior = _Prior.of(shift_mask, known_shift, surface_embed)
     if torch.is_grad_enabled() and (overhead_embed.requires_grad or surface_embed.requires_grad):
-        return _MatchFn.apply(overhead_embed, surface_embed, shift_mask, known_shift)
-    return _match_fwd(ops, overhead_embed.contiguous(), surface_embed.contiguous(), shift_mask, known_shift)
+        return _MatchFn.apply(overhead_embed, surface_embed, prior)
+    return prior.match_fwd(ops, overhead_embed.contiguous(), surface_embed.contiguous())
 
 
 class Adam(object):
@@ -803,6 +815,30 @@ def ranks(overhead_embed, surface_embed, shift_mask=None, known_shift=None):
 SPECTRAL_FROM = 8192      # evaluation sets from this many pairs on rank through the spectral pass under match_method 'auto'
 
 
+def _resolve_method(who, method, prior, n_queries=None):
+    """The one table of `method` against the orientation prior -> the pass that runs: 'direct' (the chunked pass on the fused or,
+    at known shifts, the fixed kernel), 'dft' or 'dft_masked' (the spectral pass without / under a mask). 'auto' with a prior is
+    'direct'; without one it is decided by the size of the evaluation set, 'dft' from SPECTRAL_FROM queries on, where the caller
+    has one (n_queries: evaluation_ranks). Raises before anything is launched or exchanged. A further method is added here."""
+    known = prior.mask is not None or prior.shift is not None
+    if method == 'auto' and (known or n_queries is not None):
+        return 'dft' if not known and n_queries >= SPECTRAL_FROM else 'direct'
+    if method == 'auto':
+        raise _lib.WitwError("%s: method='auto' without a prior is decided by the size of the evaluation set (evaluation_ranks)" % who)
+    if method not in ('direct', 'dft', 'dft_masked', 'fixed'):
+        raise _lib.WitwError("%s: method must be 'auto', 'direct', 'dft', 'dft_masked' or 'fixed', got %r" % (who, method))
+    if method == 'fixed' and prior.shift is None:
+        raise _lib.WitwError("%s: method='fixed' requires known_shift" % who)
+    if method in ('dft', 'dft_masked'):
+        if prior.shift is not None:
+            raise _lib.WitwError("%s: known_shift is not supported by the spectral pass (method=%r); use 'fixed'" % (who, method))
+        if method == 'dft' and prior.mask is not None:
+            raise _lib.WitwError("%s: shift_mask is not supported by the spectral pass (method='dft'); use 'dft_masked', 'direct' "
+                                 "or 'auto'" % who)
+        return 'dft' if prior.mask is None else 'dft_masked'
+    return 'direct'
+
+
 def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, method='auto', shift_mask=None, known_shift=None):
     """The ranks test() tabulates (model/cvig_fov.py:543-552), int64 [N] on the host, identical on every rank. `overhead_embed` /
     `surface_embed` are THIS rank's rows (world > 1: queries are replicated, gallery rows stay sharded). method:
@@ -817,35 +853,62 @@ def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, meth
     shift_mask = 1 << known_shift at 1/64 of the products. method 'fixed' (requires it) is retrieve()'s chunked pass on the fixed
     kernel; 'direct' / 'auto' match through it too; the spectral methods refuse it."""
     from . import parallel
-    if method not in ('auto', 'direct', 'dft', 'dft_masked', 'fixed'):
-        raise _lib.WitwError("match_method must be 'auto', 'direct', 'dft', 'dft_masked' or 'fixed', got %r" % (method,))
-    if known_shift is not None and shift_mask is not None:
-        raise _lib.WitwError('evaluation_ranks: known_shift and shift_mask are mutually exclusive')
-    if method == 'fixed' and known_shift is None:
-        raise _lib.WitwError("evaluation_ranks: method='fixed' requires known_shift")
-    if known_shift is not None:
-        if method in ('dft', 'dft_masked'):
-            raise _lib.WitwError("evaluation_ranks: known_shift is not supported by the spectral pass (method=%r); use 'fixed'"
-                                 % (method,))
-        if method == 'auto':
-            method = 'direct'
-    if shift_mask is not None:
-        if method == 'dft':
-            raise _lib.WitwError("evaluation_ranks: shift_mask is not supported by the spectral pass (method='dft'); use "
-                                 "'dft_masked', 'direct' or 'auto'")
-        if method == 'auto':
-            method = 'direct'
+    prior = _Prior.of(shift_mask, known_shift)       # its kind; the entries below check it against the gathered queries
+    _resolve_method('evaluation_ranks', method, prior, 0)      # every refusal comes before the gather, the size behind it
     surface_all = parallel.all_gather_ragged(surface_embed) if world > 1 else surface_embed
-    if method == 'auto':
-        method = 'dft' if surface_all.shape[0] >= SPECTRAL_FROM else 'direct'
-    if method in ('dft', 'dft_masked'):
-        masked = {} if shift_mask is None else {'shift_mask': shift_mask}
-        return retrieve(overhead_embed, surface_all, k=1, shard_begin=shard_begin, method=method, **masked)[0]
-    if method == 'fixed':
-        return retrieve(overhead_embed, surface_all, k=1, shard_begin=shard_begin, method='fixed', known_shift=known_shift)[0]
+    resolved = _resolve_method('evaluation_ranks', method, prior, surface_all.shape[0])
+    if resolved != 'direct' or method == 'fixed':    # retrieve()'s chunked pass, under the name it was asked for
+        return retrieve(overhead_embed, surface_all, k=1, shard_begin=shard_begin, method=resolved if method == 'auto' else method,
+                        **prior.kw())[0]
     if world > 1:
-        return sharded_ranks(overhead_embed, surface_all, shard_begin, **_prior(shift_mask, known_shift))
-    return ranks(overhead_embed, surface_embed, shift_mask, known_shift)
+        return sharded_ranks(overhead_embed, surface_all, shard_begin, **prior.kw())
+    return ranks(overhead_embed, surface_embed, **prior.kw())
+
+
+def _empty_topk(nq, k, device):
+    """the candidate lists of a rank without gallery rows (more ranks than rows): k places at +inf, index -1"""
+    return (torch.full((nq, k), float('inf'), dtype=torch.float32, device=device),
+            torch.full((nq, k), -1, dtype=torch.int64, device=device))
+
+
+def _direct_pass(kn, gallery, surface_all, prior, shard_begin, query_chunk, k, want_ranks):
+    """The chunked pass of sharded_ranks / retrieve(method='direct' / 'fixed') over this rank's gallery rows [shard_begin,
+    shard_begin + n): one match per query chunk under the chunk's rows of the prior; want_ranks: the owner of each true row
+    publishes its distance (all-reduce of a vector that is zero elsewhere), every rank counts d <= d_true over its shard and the
+    counts are summed behind the last chunk; k (None: no lists): the k nearest rows per query, merged over the ranks. A rank
+    without gallery rows still takes part in every exchange. -> (counts int32 [N] on the device, values [N,k], indices [N,k])."""
+    from . import parallel
+    dev = surface_all.device
+    n_q, n_g = surface_all.shape[0], gallery.shape[0]
+    counts = torch.zeros((n_q,), dtype=torch.int32, device=dev)
+    vals, idxs = [], []
+    for q0 in range(0, n_q, query_chunk):
+        q1 = min(n_q, q0 + query_chunk)
+        if n_g:
+            dist = prior.rows(q0, q1).match_fwd(kn, gallery, surface_all[q0:q1].contiguous(), want_orientation=False)[1]   # [n_g, q]
+        if want_ranks:
+            if n_g:
+                qi = torch.arange(q0, q1, device=dist.device)
+                own = (qi >= shard_begin) & (qi < shard_begin + n_g)
+                row = (qi - shard_begin).clamp(0, n_g - 1)
+                d_true = torch.where(own, dist[row, qi - q0], torch.zeros_like(dist[0]))
+            else:
+                d_true = torch.zeros((q1 - q0,), dtype=torch.float32, device=dev)
+            parallel.all_reduce_sum_(d_true)
+            if n_g:
+                counts[q0:q1] = kn.rank_count_thresh(dist, d_true.contiguous())
+        if k is not None:
+            v, i = kn.topk_smallest(dist, k, shard_begin) if n_g else _empty_topk(q1 - q0, k, dev)
+            vals.append(v)
+            idxs.append(i)
+    if want_ranks:
+        parallel.all_reduce_sum_(counts)
+    if k is None:
+        return counts, None, None
+    v, i = torch.cat(vals), torch.cat(idxs)
+    if parallel.world() > 1:
+        v, i = _merge_topk(v, i, k, kn)
+    return counts, v, i
 
 
 def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _match=None, _count=None, shift_mask=None,
@@ -853,35 +916,16 @@ def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _m
     """Ranking with the GALLERY sharded by rows across ranks: this rank holds
     overhead_shard = gallery rows [shard_begin, shard_begin+n); queries (replicated) match gallery row
     == query index. The owner of each true row publishes its distance (all-reduce of a vector that is
-    zero elsewhere), every rank counts d <= d_true over its shard, counts are summed. Returns int64 [N]
+    zero elsewhere), every rank counts d <= d_true over its shard, counts are summed (_direct_pass). Returns int64 [N]
     on the host, identical on every rank and identical to ranks() on one GPU. shift_mask (int64 [N], one word per query, see
     orientation_mask): every query chunk is matched under its own slice of it. known_shift (int64 [N], excludes shift_mask):
-    every chunk runs on ops.match_fwd_fixed at its slice of the shifts (an injected _match is called with known_shift=)."""
-    from . import parallel
-    known_shift = _query_shift(known_shift, shift_mask, surface_all)
-    if known_shift is not None and _match is None:
-        _match = lambda ov, su, known_shift: ops.match_fwd_fixed(ov, su, known_shift)
-    _match = _match or ops.match_fwd                 # injectable so the collective algebra is testable on CPU/gloo
-    _count = _count or ops.rank_count_thresh
-    shift_mask = _query_mask(shift_mask, surface_all)
-    n_q = surface_all.shape[0]
-    n_g = overhead_shard.shape[0]
-    out = torch.zeros((n_q,), dtype=torch.int32, device=surface_all.device)
-    for q0 in range(0, n_q, query_chunk):
-        q1 = min(n_q, q0 + query_chunk)
-        if n_g == 0:         # a rank without gallery rows still takes part in the exchanges
-            parallel.all_reduce_sum_(torch.zeros((q1 - q0,), dtype=torch.float32, device=surface_all.device))
-            continue
-        masked = _prior(shift_mask, known_shift, q0, q1)
-        _, dist = _match(overhead_shard.contiguous(), surface_all[q0:q1].contiguous(), **masked)   # [n_g, q]
-        qi = torch.arange(q0, q1, device=dist.device)
-        own = (qi >= shard_begin) & (qi < shard_begin + n_g)
-        row = (qi - shard_begin).clamp(0, n_g - 1)
-        d_true = torch.where(own, dist[row, qi - q0], torch.zeros_like(dist[0]))
-        parallel.all_reduce_sum_(d_true)
-        out[q0:q1] = _count(dist, d_true.contiguous())
-    parallel.all_reduce_sum_(out)
-    return out.cpu().numpy().astype('int64')
+    every chunk runs on ops.match_fwd_fixed at its slice of the shifts (an injected _match is called with known_shift=).
+    _match / _count: injectable so the collective algebra is testable on CPU/gloo."""
+    prior = _Prior.of(shift_mask, known_shift, surface_all)
+    fixed = ops.match_fwd_fixed if _match is None else (lambda ov, su, shift, **_kw: _match(ov, su, known_shift=shift))
+    kn = SimpleNamespace(match_fwd=_match or ops.match_fwd, match_fwd_fixed=fixed, rank_count_thresh=_count or ops.rank_count_thresh)
+    counts = _direct_pass(kn, overhead_shard.contiguous(), surface_all, prior, shard_begin, query_chunk, None, True)[0]
+    return counts.cpu().numpy().astype('int64')
 
 
 def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='direct', _kernels=None,
@@ -933,75 +977,20 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     is this chunked pass with ops.match_fwd_fixed -- 2*E FLOP per pair, no spectra, no band, no re-scoring -- feeding the same
     rank-count and top-k kernels: ranks, distances and indices equal method='direct' under shift_mask = 1 << known_shift exactly.
     'direct' / 'auto' with known_shift run the same pass; 'dft' / 'dft_masked' refuse it."""
-    from . import parallel
     kn = _kernels or ops
-    if method == 'fixed' and known_shift is None:
-        raise _lib.WitwError("retrieve: method='fixed' requires known_shift")
-    if known_shift is not None:
-        if method in ('dft', 'dft_masked'):
-            raise _lib.WitwError("retrieve: known_shift is not supported by the spectral pass (method=%r); use 'fixed'" % (method,))
-        known_shift = _query_shift(known_shift, shift_mask, surface_all)
-        if method in ('auto', 'fixed'):
-            method = 'direct'
-    if shift_mask is not None:
-        if method == 'dft':
-            raise _lib.WitwError("retrieve: shift_mask is not supported by the spectral pass (method='dft'); use 'dft_masked' or "
-                                 "'direct'")
-        if method == 'auto':
-            method = 'direct'
-        shift_mask = _query_mask(shift_mask, surface_all)
-    spectral = method in ('dft', 'dft_masked')
-    masked = {} if shift_mask is None else {'shift_mask': shift_mask}
-    if spectral and k + DFT_MARGIN > 32:             # no room for the candidate margin in a 32-wide list: the top-k comes from the
+    prior = _Prior.of(shift_mask, known_shift, surface_all)
+    resolved = _resolve_method('retrieve', method, prior)
+    gallery = overhead_shard.contiguous()
+    if resolved == 'direct':
+        counts, v, i = _direct_pass(kn, gallery, surface_all, prior, shard_begin, query_chunk, k, _want_ranks)
+        return (counts.cpu().numpy().astype('int64') if _want_ranks else None), v, i
+    if k + DFT_MARGIN > 32:                          # no room for the candidate margin in a 32-wide list: the top-k comes from the
         ranks_dft = None                              # direct pass, the rank counts (no list involved) still from the spectral one
         if _want_ranks:
-            ranks_dft = _retrieve_dft(overhead_shard, surface_all, 1, shard_begin, query_chunk, kn, True, method=method, **masked)[0]
-        _r, v, i = retrieve(overhead_shard, surface_all, k, shard_begin, query_chunk, 'direct', _kernels, _want_ranks=False, **masked)
+            ranks_dft = _retrieve_dft(kn, gallery, surface_all, prior, 1, shard_begin, query_chunk, True, method)[0]
+        _counts, v, i = _direct_pass(kn, gallery, surface_all, prior, shard_begin, query_chunk, k, False)
         return ranks_dft, v, i
-    if spectral:
-        return _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, _want_ranks, method=method, **masked)
-    if method != 'direct':
-        raise ValueError("retrieve: method must be 'direct', 'dft', 'dft_masked' or 'fixed'")
-    n_q, n_g = surface_all.shape[0], overhead_shard.shape[0]
-    counts = torch.zeros((n_q,), dtype=torch.int32, device=surface_all.device)
-    vals, idxs = [], []
-    gallery = overhead_shard.contiguous()
-    for q0 in range(0, n_q, query_chunk):
-        q1 = min(n_q, q0 + query_chunk)
-        nq = q1 - q0
-        if n_g == 0:        # a rank without gallery rows (more ranks than rows): nothing to match, empty candidate lists
-            dist = torch.empty((0, nq), dtype=torch.float32, device=surface_all.device)
-        else:
-            if known_shift is not None:      # no orientation matrix: it is known_shift broadcast, 8 bytes per pair
-                dist = kn.match_fwd_fixed(gallery, surface_all[q0:q1].contiguous(), known_shift[q0:q1].contiguous(),
-                                          want_orientation=False)[1]
-            else:
-                masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
-                _, dist = kn.match_fwd(gallery, surface_all[q0:q1].contiguous(), **masked)            # [n_g, q]
-        if _want_ranks:
-            qi = torch.arange(q0, q1, device=dist.device)
-            own = (qi >= shard_begin) & (qi < shard_begin + n_g)
-            if n_g:
-                row = (qi - shard_begin).clamp(0, n_g - 1)
-                d_true = torch.where(own, dist[row, qi - q0], torch.zeros_like(dist[0]))
-            else:
-                d_true = torch.zeros((nq,), dtype=torch.float32, device=dist.device)
-            parallel.all_reduce_sum_(d_true)
-            if n_g:
-                counts[q0:q1] = kn.rank_count_thresh(dist, d_true.contiguous())
-        if n_g:
-            v, i = kn.topk_smallest(dist, k, shard_begin)
-        else:
-            v = torch.full((nq, k), float('inf'), dtype=torch.float32, device=dist.device)
-            i = torch.full((nq, k), -1, dtype=torch.int64, device=dist.device)
-        vals.append(v)
-        idxs.append(i)
-    if _want_ranks:
-        parallel.all_reduce_sum_(counts)
-    v, i = torch.cat(vals), torch.cat(idxs)
-    if parallel.world() > 1:
-        v, i = _merge_topk(v, i, k, _kernels)
-    return (counts.cpu().numpy().astype('int64') if _want_ranks else None), v, i
+    return _retrieve_dft(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, _want_ranks, method)
 
 
 def _sort_by_value_then_index(v, i):
@@ -1024,44 +1013,40 @@ def last_retrieve_stats():
 DFT_MARGIN = 6      # candidates kept beyond place k by the spectral top-k (place k+1 must exist to decide place k)
 
 
-def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, want_ranks, method='dft', shift_mask=None):
+def _retrieve_dft(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, want_ranks, method):
     """retrieve() on the spectral pass, index-exact (see retrieve). eps = ops.DISTANCE_EPS bounds |d_dft - d_direct| at full
     width; narrower surfaces (We < 64: the window norm, hence the distance, depends on the chosen shift) first have every pair
     whose two best spectral scores are within rounding re-scored, so that the same bound holds for what is left.
-    shift_mask (int64 [N], already on the queries' device): every op of the pass gets the slice of the queries it sees -- the
-    keyword is passed only when a mask was given. eps is derived as without a mask: at full width the distance depends on the
+    prior (no prior or a mask): every op of the pass gets the rows of the queries it sees -- the keyword is passed only when a
+    mask was given. eps is derived as without a mask: at full width the distance depends on the
     largest ALLOWED score only, which both kernels know to SCORE_ROUNDING; below full width the gap that decides a re-scoring
     is taken over the allowed shifts, so what is left has its shift settled among them; and the gallery's worst window bounds
-    |ov| / |window| whatever shifts a mask leaves."""
+    |ov| / |window| whatever shifts a mask leaves. method: the name the pass was asked for, for the statistics."""
     from . import parallel
     eps = float(getattr(kn, 'DISTANCE_EPS', ops.DISTANCE_EPS))
     dev = surface_all.device
-    n_q, n_g, we = surface_all.shape[0], overhead_shard.shape[0], surface_all.shape[3]
+    n_q, n_g, we = surface_all.shape[0], gallery.shape[0], surface_all.shape[3]
     kc = k + DFT_MARGIN                                  # local candidates per query, by spectral distance (retrieve: <= 32)
     assert kc <= 32
-    gallery = overhead_shard.contiguous()
+    single_chunk = n_q <= query_chunk                    # then an overflowed band list finds its chunk's distances kept
     spec_g = kn.match_spectrum(gallery, overhead=True) if n_g else None
     counts = torch.zeros((n_q,), dtype=torch.int32, device=dev)
     vals, idxs, sns = [], [], []
     band_checks = []
     wn = None
-    stats = {'method': method, 'masked': shift_mask is not None, 'pairs': float(n_g) * n_q, 'rescored_rank': 0, 'rescored_topk': 0,
+    stats = {'method': method, 'masked': prior.mask is not None, 'pairs': float(n_g) * n_q, 'rescored_rank': 0, 'rescored_topk': 0,
              'rescored_true': 0, 'rescored_orientation': 0, 'fallback_queries': 0}
-    whole = {} if shift_mask is None else {'shift_mask': shift_mask}
     for q0 in range(0, n_q, query_chunk):
         q1 = min(n_q, q0 + query_chunk)
         nq = q1 - q0
         su = surface_all[q0:q1].contiguous()
-        masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
+        rows = prior.rows(q0, q1)
+        masked = rows.kw()
         if n_g:
-            if we < 64:
-                dist, ws, n_fix = _dft_pass_narrow(kn, gallery, su, spec_g, **masked)
-                stats['rescored_orientation'] += n_fix
-            else:
-                _, dist, ws = kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False, want_workspace=True, **masked)
+            dist, ws, n_fix = _spectral_distances(kn, gallery, su, spec_g, rows, we)
+            stats['rescored_orientation'] += n_fix
             wn, sn = ws[:n_g * 64], ws[n_g * 64:n_g * 64 + nq]
         else:
-            dist = torch.empty((0, nq), dtype=torch.float32, device=dev)
             sn = torch.zeros((nq,), dtype=torch.float32, device=dev)
         sns.append(sn)
         if q0 == 0 and we < 64:
@@ -1093,7 +1078,7 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
                     # band list, exact re-scoring and the count update in one stream sequence; the list's length stays on the device
                     # and is looked at once, behind the last chunk (band_checks)
                     c, n_band, cap = kn.rank_count_resolved(dist, d_true, eps, gallery, su, wn, sn, **masked)
-                    band_checks.append((n_band, cap, q0, q1, dist if len(range(0, n_q, query_chunk)) == 1 else None, su, d_true, sn))
+                    band_checks.append((n_band, cap, q0, q1, dist if single_chunk else None, su, d_true, sn))
                 else:
                     c, po, ps = kn.rank_count_band(dist, d_true, eps)
                     if po.numel():
@@ -1101,34 +1086,54 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
                         c.index_add_(0, ps.long(), (d_x <= d_true[ps.long()]).to(torch.int32))
                         stats['rescored_rank'] += int(po.numel())
                 counts[q0:q1] = c
-        if n_g:
-            v, i = kn.topk_smallest(dist, kc, shard_begin)
-        else:
-            v = torch.full((nq, kc), float('inf'), dtype=torch.float32, device=dev)
-            i = torch.full((nq, kc), -1, dtype=torch.int64, device=dev)
+        v, i = kn.topk_smallest(dist, kc, shard_begin) if n_g else _empty_topk(nq, kc, dev)
         vals.append(v)
         idxs.append(i)
     if band_checks:
-        # one look at the band lists' lengths for the whole pass; a list that overflowed (more pairs within eps of a threshold than
-        # 1/4096 of the chunk: not seen on real or synthetic data) sends its chunk through the two-step form again
-        n_host = torch.cat([b[0] for b in band_checks]).tolist()
-        for got, (_n, cap, q0, q1, dist_kept, su, d_true, sn) in zip(n_host, band_checks):
-            stats['rescored_rank'] += min(int(got), cap)
-            if got > cap:
-                masked = {} if shift_mask is None else {'shift_mask': shift_mask[q0:q1].contiguous()}
-                dist_c = dist_kept
-                if dist_c is None:
-                    dist_c = (_dft_pass_narrow(kn, gallery, su, spec_g, **masked)[0] if we < 64 else
-                              kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False, **masked)[1])
-                c, po, ps = kn.rank_count_band(dist_c, d_true, eps)
-                d_x = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **masked)[1]
-                c.index_add_(0, ps.long(), (d_x <= d_true[ps.long()]).to(torch.int32))
-                counts[q0:q1] = c
-        band_checks = []
+        _redo_overflowed_bands(kn, gallery, spec_g, prior, we, eps, wn, band_checks, counts, stats)
     if want_ranks:
         parallel.all_reduce_sum_(counts)
-    v, i, sn_all = torch.cat(vals), torch.cat(idxs), torch.cat(sns)
-    # ---- candidates of all shards, ordered by (spectral distance, index)
+    v, i = _settle_topk(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, eps, torch.cat(vals), torch.cat(idxs), wn,
+                        torch.cat(sns), stats)
+    stats['eps'] = eps
+    retrieve.last_stats = stats
+    _RETRIEVE_TLS.stats = stats
+    return (counts.cpu().numpy().astype('int64') if want_ranks else None), v, i
+
+
+def _spectral_distances(kn, gallery, su, spec_g, prior, we):
+    """one spectral pass over (gallery, su) under su's rows of the prior -> (distance [n_g, nq], workspace, pairs re-scored for
+    their orientation: narrow surfaces only)"""
+    if we < 64:
+        return _dft_pass_narrow(kn, gallery, su, spec_g, prior)
+    _, dist, ws = kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False, want_workspace=True, **prior.kw())
+    return dist, ws, 0
+
+
+def _redo_overflowed_bands(kn, gallery, spec_g, prior, we, eps, wn, band_checks, counts, stats):
+    """One look at the band lists' lengths for the whole pass; a list that overflowed (more pairs within eps of a threshold than
+    1/4096 of the chunk: not seen on real or synthetic data) sends its chunk through the two-step form again."""
+    n_host = torch.cat([b[0] for b in band_checks]).tolist()
+    for got, (_n, cap, q0, q1, dist_c, su, d_true, sn) in zip(n_host, band_checks):
+        stats['rescored_rank'] += min(int(got), cap)
+        if got > cap:
+            rows = prior.rows(q0, q1)
+            if dist_c is None:
+                dist_c = _spectral_distances(kn, gallery, su, spec_g, rows, we)[0]
+            c, po, ps = kn.rank_count_band(dist_c, d_true, eps)
+            d_x = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **rows.kw())[1]
+            c.index_add_(0, ps.long(), (d_x <= d_true[ps.long()]).to(torch.int32))
+            counts[q0:q1] = c
+
+
+def _settle_topk(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, eps, v, i, wn, sn_all, stats):
+    """The shards' candidate lists (v, i: [N, k + DFT_MARGIN] by spectral distance) -> the first k places as the direct pass orders
+    them: the lists are gathered and ordered by (spectral distance, index); a query with a gap within rounding among its first
+    k + 1 places, or with place k within rounding of the best row outside the lists, has its candidates re-scored exactly; one
+    that even then cannot exclude a row outside the re-scored set takes the direct pass."""
+    from . import parallel
+    dev = surface_all.device
+    n_q, n_g, kc = surface_all.shape[0], gallery.shape[0], k + DFT_MARGIN
     w = parallel.world()
     outsider = v[:, kc - 1].clone()                      # no row outside a shard's list has a smaller spectral distance
     if w > 1:
@@ -1154,7 +1159,7 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
         if n_g and bool(mine.any()):
             po = (ci - shard_begin)[mine].to(torch.int32).contiguous()
             ps = rows[:, None].expand(-1, m)[mine].to(torch.int32).contiguous()
-            exact[mine] = kn.match_pairs(gallery, surface_all.contiguous(), wn, sn_all, po, ps, want_orientation=False, **whole)[1]
+            exact[mine] = kn.match_pairs(gallery, surface_all.contiguous(), wn, sn_all, po, ps, want_orientation=False, **prior.kw())[1]
             stats['rescored_topk'] += int(po.numel())
         parallel.all_reduce_sum_(exact)
         exact = torch.where(ci < 0, torch.full_like(exact, float('inf')), exact)
@@ -1167,25 +1172,21 @@ def _retrieve_dft(overhead_shard, surface_all, k, shard_begin, query_chunk, kn, 
         fallback = rows[~safe]
     if fallback.numel():     # more near-ties than candidates kept (not seen on real data): those queries take the direct pass
         stats['fallback_queries'] = int(fallback.numel())
-        masked = {} if shift_mask is None else {'shift_mask': shift_mask[fallback].contiguous()}
-        _r, fv, fi = retrieve(overhead_shard, surface_all[fallback].contiguous(), k, shard_begin, query_chunk, 'direct',
-                              None if kn is ops else kn, _want_ranks=False, **masked)
+        _counts, fv, fi = _direct_pass(kn, gallery, surface_all[fallback].contiguous(), prior.take(fallback), shard_begin,
+                                       query_chunk, k, False)
         v[fallback, :k], i[fallback, :k] = fv, fi
-    stats['eps'] = eps
-    retrieve.last_stats = stats
-    _RETRIEVE_TLS.stats = stats
-    return (counts.cpu().numpy().astype('int64') if want_ranks else None), v[:, :k].contiguous(), i[:, :k].contiguous()
+    return v[:, :k].contiguous(), i[:, :k].contiguous()
 
 
-def _dft_pass_narrow(kn, gallery, su, spec_g, shift_mask=None):
+def _dft_pass_narrow(kn, gallery, su, spec_g, prior):
     """The spectral pass for surfaces narrower than the overhead embedding (We < 64): the window norm depends on the shift, so
     a pair whose two best scores are within rounding could take the other shift in the direct kernel and land on a different
     distance. Those pairs (top-2 score gap <= 4 SCORE_ROUNDING |ov| |su|) are re-scored exactly and patched into the matrix.
-    shift_mask (int64 [nq], this chunk's words): the gap is then the one between the two best ALLOWED scores (+inf where a word
-    allows one shift: nothing to re-score) and the re-scoring runs under the mask.
+    prior (this chunk's rows; no prior or a mask): under a mask the gap is the one between the two best ALLOWED scores (+inf where
+    a word allows one shift: nothing to re-score) and the re-scoring runs under the mask.
     -> (distance [n_g, nq], workspace, pairs re-scored)."""
     n_g, nq = gallery.shape[0], su.shape[0]
-    masked = {} if shift_mask is None else {'shift_mask': shift_mask}
+    masked = prior.kw()
     _, dist, gap, ws = kn.match_fwd_dft(gallery, su, spec_ov=spec_g, want_orientation=False, want_workspace=True, want_gap=True,
                                         **masked)
     wn, sn = ws[:n_g * 64], ws[n_g * 64:n_g * 64 + nq]
@@ -1208,7 +1209,7 @@ class _ShardedMatchLossFn(torch.autograd.Function):
     are complete locally. Same value and gradients as match + triplet_loss on the gathered batch."""
 
     @staticmethod
-    def forward(ctx, overhead_local, surface_local, alpha, k, known_shift=None):
+    def forward(ctx, overhead_local, surface_local, alpha, k, prior=_NO_PRIOR):
         from . import parallel
         b = surface_local.shape[0]
         col0 = parallel.rank() * b
@@ -1216,7 +1217,7 @@ class _ShardedMatchLossFn(torch.autograd.Function):
             ov_all = parallel._all_gather_cat(overhead_local.contiguous())
         su = surface_local.contiguous()
         with parallel.phase('slab_match'):
-            ori, dist, score, ws = _match_fwd(k, ov_all, su, None, known_shift, want_score=True, want_workspace=True)
+            ori, dist, score, ws = prior.match_fwd(k, ov_all, su, want_score=True, want_workspace=True)
         B = ov_all.shape[0]
         with parallel.phase('diagonal_all_gather'):
             diag = parallel._all_gather_cat(dist[col0:col0 + b].diagonal().contiguous())
@@ -1256,7 +1257,7 @@ class _BatchHardMatchLossFn(torch.autograd.Function):
     rank's surface anchors (global indices)."""
 
     @staticmethod
-    def forward(ctx, overhead_local, surface_local, alpha, k, known_shift=None):
+    def forward(ctx, overhead_local, surface_local, alpha, k, prior=_NO_PRIOR):
         from . import parallel
         world = parallel.world()
         b = surface_local.shape[0]
@@ -1268,7 +1269,7 @@ class _BatchHardMatchLossFn(torch.autograd.Function):
         else:
             ov_all = overhead_local.contiguous()
         with parallel.phase('slab_match'):
-            ori, dist, score, ws = _match_fwd(k, ov_all, su, None, known_shift, want_score=True, want_workspace=True)
+            ori, dist, score, ws = prior.match_fwd(k, ov_all, su, want_score=True, want_workspace=True)
         B = ov_all.shape[0]
         if world > 1:
             with parallel.phase('diagonal_all_gather'):
@@ -1315,16 +1316,16 @@ def sharded_match_loss(overhead_local, surface_local, alpha=10., _kernels=None, 
     known_shift (int64 [b], see orientation_shift): the known orientations of THIS rank's b surface columns -- the slab is matched
     by match_fwd_fixed instead of match_fwd (aligned training); everything behind that call is what it is without it."""
     from . import parallel
-    known_shift = _query_shift(known_shift, None, surface_local)
+    prior = _Prior.of(None, known_shift, surface_local)
     if loss == 'batch_hard':
-        out = _BatchHardMatchLossFn.apply(overhead_local, surface_local, float(alpha), _kernels or ops, known_shift)
+        out = _BatchHardMatchLossFn.apply(overhead_local, surface_local, float(alpha), _kernels or ops, prior)
         return out if mined else out[:3]
     if loss != 'soft_margin':
         raise _lib.WitwError("sharded_match_loss: loss must be 'soft_margin' or 'batch_hard', got %r" % (loss,))
     if parallel.world() == 1 and _kernels is None:
-        ori, dist = match(overhead_local, surface_local, known_shift=known_shift)
+        ori, dist = match(overhead_local, surface_local, **prior.kw())
         return triplet_loss(dist, alpha), ori, dist.detach()
-    return _ShardedMatchLossFn.apply(overhead_local, surface_local, float(alpha), _kernels or ops, known_shift)
+    return _ShardedMatchLossFn.apply(overhead_local, surface_local, float(alpha), _kernels or ops, prior)
 
 
 class PairEmbedder(object):

@@ -521,12 +521,24 @@ def match_bwd(overhead_embed, surface_embed, orientation, score, workspace, grad
     return gov, gsu
 
 
-def _check_shift_mask(name, shift_mask, Bs, device):
-    if not (isinstance(shift_mask, torch.Tensor) and shift_mask.dtype == torch.int64 and shift_mask.device == device
-            and tuple(shift_mask.shape) == (Bs,) and shift_mask.is_contiguous()):
-        raise _lib.WitwError('%s: shift_mask must be a contiguous int64 [%d] tensor on %s, got %s'
-                             % (name, Bs, device, (tuple(shift_mask.shape), shift_mask.dtype, shift_mask.device)
-                                if isinstance(shift_mask, torch.Tensor) else type(shift_mask)))
+def _match_operands(name, overhead_embed, surface_embed):
+    """the two embedding batches of a match forward, checked -> (ov, su, Bo, Bs, We)"""
+    ov = _dev_f32(overhead_embed, 'overhead_embed')
+    su = _dev_f32(surface_embed, 'surface_embed')
+    if ov.dim() != 4 or su.dim() != 4 or ov.shape[1] * ov.shape[2] != 64 or ov.shape[3] != 64:
+        raise _lib.WitwError('%s: overhead embedding must be [Bo,16,4,64], got %s' % (name, tuple(ov.shape)))
+    if su.shape[1] != ov.shape[1] or su.shape[2] != ov.shape[2]:
+        raise _lib.WitwError('%s: surface embedding %s does not match overhead %s' % (name, tuple(su.shape), tuple(ov.shape)))
+    return ov, su, ov.shape[0], su.shape[0], su.shape[3]
+
+
+def _check_query_words(name, what, t, Bs, device):
+    """`what` ('shift_mask', 'shift'): one int64 word per surface embedding, as the kernels read it"""
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.device == device and tuple(t.shape) == (Bs,)
+            and t.is_contiguous()):
+        raise _lib.WitwError('%s: %s must be a contiguous int64 [%d] tensor on %s, got %s'
+                             % (name, what, Bs, device, (tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor)
+                                else type(t)))
 
 
 def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=False, shift_mask=None):
@@ -537,19 +549,9 @@ def match_fwd(overhead_embed, surface_embed, want_score=False, want_workspace=Fa
     chosen (bit 63 makes the word negative; that is fine), 0 = no prior for that query. The arg-max is then the first maximum
     over the allowed shifts (witw_match_fwd_masked); cvig_fov.orientation_mask builds the words from degrees."""
     lib = _lib.load()
-    ov = _dev_f32(overhead_embed, 'overhead_embed')
-    su = _dev_f32(surface_embed, 'surface_embed')
-    if ov.dim() != 4 or su.dim() != 4 or ov.shape[1] * ov.shape[2] != 64 or ov.shape[3] != 64:
-        raise _lib.WitwError('match_fwd: overhead embedding must be [Bo,16,4,64], got %s' % (tuple(ov.shape),))
-    if su.shape[1] != ov.shape[1] or su.shape[2] != ov.shape[2]:
-        raise _lib.WitwError('match_fwd: surface embedding %s does not match overhead %s' % (tuple(su.shape), tuple(ov.shape)))
-    Bo, Bs, We = ov.shape[0], su.shape[0], su.shape[3]
+    ov, su, Bo, Bs, We = _match_operands('match_fwd', overhead_embed, surface_embed)
     if shift_mask is not None:
-        if not (isinstance(shift_mask, torch.Tensor) and shift_mask.dtype == torch.int64 and shift_mask.device == ov.device
-                and tuple(shift_mask.shape) == (Bs,) and shift_mask.is_contiguous()):
-            raise _lib.WitwError('match_fwd: shift_mask must be a contiguous int64 [%d] tensor on %s, got %s'
-                                 % (Bs, ov.device, (tuple(shift_mask.shape), shift_mask.dtype, shift_mask.device)
-                                    if isinstance(shift_mask, torch.Tensor) else type(shift_mask)))
+        _check_query_words('match_fwd', 'shift_mask', shift_mask, Bs, ov.device)
     ori = torch.empty((Bo, Bs), dtype=torch.int64, device=ov.device)
     dist = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device)
     score = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device) if want_score else None
@@ -575,18 +577,8 @@ def match_fwd_fixed(overhead_embed, surface_embed, shift, want_score=False, want
     distance[, score][, workspace] -- with distance and score bit-identical to match_fwd(..., shift_mask=1 << (shift & 63)). The
     workspace begins with the norms match_bwd / match_pairs read."""
     lib = _lib.load()
-    ov = _dev_f32(overhead_embed, 'overhead_embed')
-    su = _dev_f32(surface_embed, 'surface_embed')
-    if ov.dim() != 4 or su.dim() != 4 or ov.shape[1] * ov.shape[2] != 64 or ov.shape[3] != 64:
-        raise _lib.WitwError('match_fwd_fixed: overhead embedding must be [Bo,16,4,64], got %s' % (tuple(ov.shape),))
-    if su.shape[1] != ov.shape[1] or su.shape[2] != ov.shape[2]:
-        raise _lib.WitwError('match_fwd_fixed: surface embedding %s does not match overhead %s' % (tuple(su.shape), tuple(ov.shape)))
-    Bo, Bs, We = ov.shape[0], su.shape[0], su.shape[3]
-    if not (isinstance(shift, torch.Tensor) and shift.dtype == torch.int64 and shift.device == ov.device
-            and tuple(shift.shape) == (Bs,) and shift.is_contiguous()):
-        raise _lib.WitwError('match_fwd_fixed: shift must be a contiguous int64 [%d] tensor on %s, got %s'
-                             % (Bs, ov.device, (tuple(shift.shape), shift.dtype, shift.device)
-                                if isinstance(shift, torch.Tensor) else type(shift)))
+    ov, su, Bo, Bs, We = _match_operands('match_fwd_fixed', overhead_embed, surface_embed)
+    _check_query_words('match_fwd_fixed', 'shift', shift, Bs, ov.device)
     ori = torch.empty((Bo, Bs), dtype=torch.int64, device=ov.device) if want_orientation else None
     dist = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device)
     score = torch.empty((Bo, Bs), dtype=torch.float32, device=ov.device) if want_score else None
@@ -664,15 +656,9 @@ def match_fwd_dft(overhead_embed, surface_embed, spec_ov=None, spec_su=None, wan
     shift_mask: None, or int64 [Bs] as match_fwd takes it (witw_match_fwd_dft_masked): the first maximum over the allowed shifts;
     the gap is then taken over the allowed shifts, +inf where a word allows one shift."""
     lib = _lib.load()
-    ov = _dev_f32(overhead_embed, 'overhead_embed')
-    su = _dev_f32(surface_embed, 'surface_embed')
-    if ov.dim() != 4 or su.dim() != 4 or ov.shape[1] * ov.shape[2] != 64 or ov.shape[3] != 64:
-        raise _lib.WitwError('match_fwd_dft: overhead embedding must be [Bo,16,4,64], got %s' % (tuple(ov.shape),))
-    if su.shape[1] != ov.shape[1] or su.shape[2] != ov.shape[2]:
-        raise _lib.WitwError('match_fwd_dft: surface embedding %s does not match overhead %s' % (tuple(su.shape), tuple(ov.shape)))
-    Bo, Bs, We = ov.shape[0], su.shape[0], su.shape[3]
+    ov, su, Bo, Bs, We = _match_operands('match_fwd_dft', overhead_embed, surface_embed)
     if shift_mask is not None:
-        _check_shift_mask('match_fwd_dft', shift_mask, Bs, ov.device)
+        _check_query_words('match_fwd_dft', 'shift_mask', shift_mask, Bs, ov.device)
     spec_ov = match_spectrum(ov, overhead=True) if spec_ov is None else spec_ov
     spec_su = match_spectrum(su, overhead=False) if spec_su is None else spec_su
     for name, sp, n, side in (('spec_ov', spec_ov, Bo, True), ('spec_su', spec_su, Bs, False)):
@@ -736,7 +722,7 @@ def match_pairs(overhead_embed, surface_embed, wn, sn, pair_o, pair_s, want_orie
     if wn.numel() != Bo * 64 or sn.numel() != Bs:
         raise _lib.WitwError('match_pairs: wn / sn must hold [Bo,64] / [Bs] norms')
     if shift_mask is not None:
-        _check_shift_mask('match_pairs', shift_mask, Bs, ov.device)
+        _check_query_words('match_pairs', 'shift_mask', shift_mask, Bs, ov.device)
     ori = torch.empty((n,), dtype=torch.int64, device=ov.device) if want_orientation else None
     dist = torch.empty((n,), dtype=torch.float32, device=ov.device)
     if n and shift_mask is not None:
@@ -790,7 +776,7 @@ def rank_count_resolved(distance, threshold, eps, overhead_embed, surface_embed,
     if wn.numel() != Bo * 64 or sn.numel() != Bs:
         raise _lib.WitwError('rank_count_resolved: wn / sn must hold [Bo,64] / [Bs] norms')
     if shift_mask is not None:
-        _check_shift_mask('rank_count_resolved', shift_mask, Bs, d.device)
+        _check_query_words('rank_count_resolved', 'shift_mask', shift_mask, Bs, d.device)
     counts = torch.empty((Bs,), dtype=torch.int32, device=d.device)
     n = torch.empty((1,), dtype=torch.int32, device=d.device)
     cap = max(1 << 16, (Bo * Bs) // 4096)
