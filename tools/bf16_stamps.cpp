@@ -1,7 +1,7 @@
 // Diagnostic harness (not part of the product): builds conv3x3_bf16.hip with -DWITW_BF_STAMPS and prints, for one layer
 // shape, how many s_memtime ticks a wave spends in the K loop, in the vmcnt drain and at the workgroup barrier.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DWITW_BF_STAMPS -I witw_amd/csrc \
-//         tools/bf16_stamps.cpp witw_amd/csrc/api.hip -o tools/bin/bf16_stamps
+//         tools/bf16_stamps.cpp witw_amd/csrc/api.hip witw_amd/csrc/conv3x3_bf16_wres.hip -o tools/bin/bf16_stamps
 #include "../witw_amd/csrc/conv3x3_bf16.hip"
 #include <vector>
 #include <algorithm>

@@ -13,67 +13,24 @@
 //   * activations are stored bf16 (round-to-nearest-even, v_cvt_pk_bf16_f32), channel count padded to 16;
 //     the last layer writes the fp32 NCHW embedding.
 #include "common.h"
+#include "conv_launch.h"
+#include "lds_frag.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TW = 64;
 constexpr int IW = TW + 2;
 
-// Staging mode: 1 = input tile global -> VGPR -> ds_write, weight slab by LDS-DMA (buffer_load ... lds:
-// the packed slab is already the LDS image, 1 KB contiguous per wave instruction); 2 = input tile by LDS-DMA too.
-#ifndef WITW_BF_DMA
-#define WITW_BF_DMA 1
-#endif
-#ifndef WITW_BF_SWAP
-#define WITW_BF_SWAP 0          // A/B builds: 1 = MFMA operands swapped (lane = pixel, register quad = 4 consecutive channels), the
-#endif                          //     epilogue transposes through LDS with 8-byte writes (12 instead of 40 LDS instructions per M-tile).
-                                //     Parity-green, but measured SLOWER per tile (epilogue 9.1 k -> 11.9 k ticks)
-#ifndef WITW_BF_S16_DMA
-#define WITW_BF_S16_DMA 0       // 16x16x32 kernel: 1 = the input tile moves by LDS-DMA as well (A/B builds)
-#endif
-#ifndef WITW_BF_S16_PLANE16
-#define WITW_BF_S16_PLANE16 1   // 16x16x32 kernel: channel-group planes of a stage at a pitch of 0 mod 16 slots (conflict-free A reads); 0 = round 2-5 layout
-#endif
+// Staging: the input tile goes global -> VGPR -> ds_write, the weight slab by LDS-DMA (dma16, lds_frag.h: the packed slab is
+// already the LDS image, 1 KB contiguous per wave instruction).
 #ifndef WITW_BF_S16_SPREAD
 #define WITW_BF_S16_SPREAD 3    // half-units (of 8 per chunk) over which the 16x16x32 kernel issues the staging pieces of the next chunk
 #endif
 #ifndef WITW_BF_SPREAD
 #define WITW_BF_SPREAD 5        // taps over which the staging pieces of a chunk are issued (1 = all at tap 0)
 #endif
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// Raw buffer descriptor (base, stride 0, byte count, the flag word __builtin_amdgcn_make_buffer_rsrc is given elsewhere
-// in this file) as four SGPRs for the hand-issued LDS-DMA loads.
-__device__ __forceinline__ i32x4 raw_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu));
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
-
-// One wave instruction of LDS-DMA: lane l moves 16 B from rs[voff_l + soff] to LDS byte address lds_addr + 16*l
-// (out-of-range lanes store zeros). Issued as inline assembly ON PURPOSE: for the builtin form the compiler puts a
-// vmcnt wait in front of every later ds_read (it cannot tell the stage being read from the stage being filled), which
-// serialises the pipeline; here the wave drains vmcnt itself once per K chunk (stage_wait) before the barrier.
-__device__ __forceinline__ void dma16(i32x4 rs, unsigned lds_addr, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :
-                 : "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff)
-                 : "memory");      // m0 is a scratch register for the compiler too: it re-sets it right before each of its own uses
-#endif
-}
-
-__device__ __forceinline__ unsigned lds_address(const void* p) {
-    return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)p;
-}
 
 struct ConvBfArgs {
     const unsigned short* x;   // [B,H,W,Cin] NHWC bf16, Cin % 16 == 0
@@ -104,8 +61,7 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
     constexpr int W_S = 9 * 2 * TN;             // 16-B slots of one weight stage (a multiple of 64)
     constexpr int STAGE_S = IN_P + W_S;
     constexpr int NIN = (IN_S + NTHREADS - 1) / NTHREADS;
-    constexpr int NIN_D = (IN_P / 64 + NW - 1) / NW;     // LDS-DMA wave instructions per wave and stage
-    constexpr int NWT_D = (W_S / 64 + NW - 1) / NW;
+    constexpr int NWT_D = (W_S / 64 + NW - 1) / NW;      // LDS-DMA wave instructions per wave and stage
     constexpr int WGM = (TN == 128) ? NW / 2 : NW;
     constexpr int WM = (2 * TH) / WGM;
     constexpr int WN = 2;
@@ -155,9 +111,6 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
     __amdgpu_buffer_rsrc_t in_rs =
         __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b * img_elems), 0, (unsigned)(img_elems * 2), 0x00020000);
     const i32x4 w_rd = raw_rsrc(reinterpret_cast<const u32x4*>(p.wpk) + (size_t)ntile * nkc * W_S, (unsigned)nkc * W_S * 16u);
-#if WITW_BF_DMA >= 2
-    const i32x4 in_rd = raw_rsrc(p.x + (size_t)b * img_elems, (unsigned)(img_elems * 2));
-#endif
     // byte offset of halo-tile slot (pixel pix, channel group q) in the image, or OOR (loads return zero: padding)
     auto in_offset = [&](bool in_range, int pix, int q) -> unsigned {
         const int r = pix / IW, c = pix - r * IW;
@@ -176,23 +129,13 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
         }
         return ok ? (unsigned)((((size_t)gr * p.W + gc) * p.Cin + q * 8) * 2) : OOR;
     };
-#if WITW_BF_DMA >= 2
-    unsigned gin[NIN_D];        // DMA: slot s = instr * 64 + lane IS the LDS position [group][pixel]
-#pragma unroll
-    for (int i = 0; i < NIN_D; ++i) {
-        const int s = (wave + NW * i) * 64 + lane;
-        const int q = s / (IH * IW);
-        gin[i] = in_offset(s < IN_S, s - q * (IH * IW), q);
-    }
-#else
-    unsigned gin[NIN];          // registers: slot s -> pixel s/2, group s%2 (a pixel's 32 B load as one segment)
+    unsigned gin[NIN];          // slot s -> pixel s/2, group s%2 (a pixel's 32 B load as one segment)
 #pragma unroll
     for (int i = 0; i < NIN; ++i) {
         const int s = tid + i * NTHREADS;
         gin[i] = in_offset(s < IN_S, s >> 1, s & 1);
     }
     u32x4 rin[NIN];
-#endif
     const unsigned lane16 = (unsigned)lane * 16u;
 
 #ifdef WITW_DIAG_NOIN
@@ -208,33 +151,19 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
     bool first_stage = true;
     // Staging of one K chunk is cut into PIECES wave instructions per wave (input pieces first: they come over the
     // fabric, the weight pieces are L2 hits). piece p of chunk kc -> LDS stage in_s:
-#if WITW_BF_DMA >= 2
-    constexpr int P_IN = NIN_D;
-#else
-    constexpr int P_IN = NIN;
-#endif
-    constexpr int PIECES = P_IN + NWT_D;
+    constexpr int PIECES = NIN + NWT_D;
     auto stage_piece = [&](int kc, u32x4* in_s, int pc) {
         const unsigned in_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_address(in_s));
-        if (pc < P_IN) {
-            if (DIAG_IN || first_stage) {
-#if WITW_BF_DMA >= 2
-                const int j = wave_u + NW * pc;
-                if (NIN_D * NW == IN_P / 64 || j < IN_P / 64) dma16(in_rd, in_lds + (unsigned)j * 1024u, gin[pc], (unsigned)kc * 32u);
-#else
-                rin[pc] = __builtin_amdgcn_raw_buffer_load_b128(in_rs, gin[pc], (unsigned)kc * 32u, 0);
-#endif
-            }
+        if (pc < NIN) {
+            if (DIAG_IN || first_stage) rin[pc] = __builtin_amdgcn_raw_buffer_load_b128(in_rs, gin[pc], (unsigned)kc * 32u, 0);
         } else if (DIAG_W || first_stage) {
-            const int j = wave_u + NW * (pc - P_IN);
+            const int j = wave_u + NW * (pc - NIN);
             if (NWT_D * NW == W_S / 64 || j < W_S / 64)
                 dma16(w_rd, in_lds + (unsigned)(IN_P + j * 64) * 16u, lane16, (unsigned)kc * W_S * 16u + (unsigned)j * 1024u);
         }
     };
     // register-staged input tile: VGPR -> LDS
     auto stage_commit = [&](u32x4* in_s) {
-        (void)in_s;
-#if WITW_BF_DMA < 2
         if (DIAG_IN || first_stage) {
 #pragma unroll
             for (int i = 0; i < NIN; ++i) {
@@ -243,7 +172,6 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
                 *dst = rin[i];
             }
         }
-#endif
     };
     // LDS-DMA data has landed once this wave's vector-memory counter drains (then the workgroup barrier publishes it)
     auto stage_wait = [&]() {
@@ -289,13 +217,8 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
         for (int mt = 0; mt < WM; ++mt)
 #pragma unroll
             for (int nt = 0; nt < WN; ++nt)
-#if WITW_BF_SWAP
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fb[set][nt]),
-                                                                     __builtin_bit_cast(bf16x8, fa[set][mt]), acc[mt][nt], 0, 0, 0);
-#else
                 acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[set][mt]),
                                                                      __builtin_bit_cast(bf16x8, fb[set][nt]), acc[mt][nt], 0, 0, 0);
-#endif
     };
 
 #pragma unroll
@@ -369,178 +292,6 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
 #endif
     __syncthreads();      // the slabs below reuse the stages
 
-#if WITW_BF_SWAP
-    // ---- epilogue, swapped-operand form. acc[mt][nt][r] = output of PIXEL m = l31 of M-tile mt, CHANNEL
-    // nt*32 + 8*(r>>2) + 4*hq + (r&3) of this wave's 64: a register quad holds 4 consecutive channels of one pixel, so
-    // the LDS transposition writes 8 bytes of bf16 per quad (8 ds_write_b64 per M-tile instead of 32 scalar writes) into
-    // a [pixel][64 channels] slab of 128-byte rows whose 16-byte chunks are XOR-swizzled with the pixel index (and the
-    // two 8-byte halves of a chunk swapped on odd pixel octets): writes spread over all banks, the read-back is
-    // 4 ds_read_b128 per M-tile (8 channels of a pixel per lane, halves swapped back at compile time) -> 16-byte stores.
-    {
-        const int cbase = n0 + wn * 64;                 // first channel of this wave
-        const int m = l31;
-        // the bias of this lane's 8 channel quads is fetched once, up front (32 registers; fetching it where a quad is
-        // finished put a global-load latency in front of every LDS write); the Dropout2d scale, present on three layers of
-        // a training forward only, is fetched per quad
-        f32x4 bv4[WN][4];
-#pragma unroll
-        for (int nt = 0; nt < WN; ++nt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) bv4[nt][g] = *reinterpret_cast<const f32x4*>(p.bias + cbase + nt * 32 + 8 * g + 4 * hq);
-        f32x4 bq, dq = {1.f, 1.f, 1.f, 1.f};
-        auto load_quad = [&](int nt, int g) {
-            bq = bv4[nt][g];
-            if (p.dropmask != nullptr) {
-                const int c = cbase + nt * 32 + 8 * g + 4 * hq;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dq[j] = (c + j < p.Cout) ? p.dropmask[(size_t)b * p.Cout + c + j] : 1.f;
-            }
-        };
-        auto fin = [&](float v, int nt, int g, int j) {      // conv + bias -> Dropout2d scale -> ReLU, after load_quad(nt, g)
-            (void)nt; (void)g;
-            v = (v + bq[j]) * dq[j];
-            if (p.relu) v = fmaxf(v, 0.f);
-            return v;
-        };
-        auto gate_open = [](unsigned short g) { return (g & 0x7fffu) != 0 && !(g & 0x8000u); };   // bf16 value > 0
-        const int Hy = POOL ? (p.Ho >> 1) : p.Ho;
-        const int Wy = POOL ? (p.Wo >> 1) : p.Wo;
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-        constexpr int SLABB = 32 * 128;
-        char* const slab0 = reinterpret_cast<char*>((wave & 1) ? stageB : stageA) + (wave >> 1) * (2 * SLABB);
-        const int prow = lane >> 3, oct = lane & 7;
-        // byte offset of (pixel row q, channel chunk k = nt*4 + g, half hq) inside a slab
-        auto wr_off = [&](int q, int k) { return q * 128 + (((k ^ (q & 7)) << 4) | ((hq ^ ((q >> 3) & 1)) << 3)); };
-        // read-back of one slab row group: pixel rows gq*8 + prow, chunk `oct`; halves come back swapped on odd gq
-        auto rd_chunk = [&](const char* slab, int gq) {
-            const u16x8 v = *reinterpret_cast<const u16x8*>(slab + (gq * 8 + prow) * 128 + ((oct ^ prow) << 4));
-            return (gq & 1) ? (u16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]} : v;
-        };
-        auto store8 = [&](u16x8 o, int yy, int xx) {
-            const int nbase = cbase + oct * 8;
-            if (yy < Hy && xx < Wy && nbase < p.Cout) {
-                const size_t off = (((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nbase;
-                if (p.gate != nullptr) {
-                    const u16x8 gt = *reinterpret_cast<const u16x8*>(p.gate + off);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        if (!gate_open(gt[e])) o[e] = 0;
-                }
-                __builtin_nontemporal_store(o, reinterpret_cast<u16x8*>(reinterpret_cast<unsigned short*>(p.y) + off));
-            }
-        };
-        if (p.out_nchw_f32 || (p.Cout & 7) != 0) {
-            // fp32 NCHW embedding (last layer) or a ragged channel count: lanes are consecutive pixels of a row, so
-            // every register is a coalesced run along x
-            if (!POOL) {
-#pragma unroll
-                for (int mt = 0; mt < WM; ++mt) {
-                    const int yy = oy0 + trow[mt], xx = ox0 + tcol[mt] + m;
-#pragma unroll
-                    for (int nt = 0; nt < WN; ++nt)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int g = r >> 2, j = r & 3;
-                            const int c = cbase + nt * 32 + 8 * g + 4 * hq + j;
-                            if (j == 0) load_quad(nt, g);
-                            float v = fin(acc[mt][nt][r], nt, g, j);
-                            if (yy < Hy && xx < Wy && c < p.Cout) {
-                                if (p.out_nchw_f32) {
-                                    reinterpret_cast<float*>(p.y)[(((size_t)b * p.Cout + c) * Hy + yy) * Wy + xx] = v;
-                                } else {
-                                    const size_t o = (((size_t)b * Hy + yy) * Wy + xx) * p.Cout + c;
-                                    if (p.gate != nullptr && !gate_open(p.gate[o])) v = 0.f;
-                                    reinterpret_cast<__bf16*>(p.y)[o] = (__bf16)v;
-                                }
-                            }
-                        }
-                }
-            } else {
-#pragma unroll
-                for (int pr = 0; pr < WM / 2; ++pr) {
-                    const int mtA = (TN == 128) ? (pr & 1) : 0;
-                    const int mtB = (TN == 128) ? (2 + (pr & 1)) : 1;
-                    const int yy = (oy0 + trow[mtA]) >> 1, xx = ((ox0 + tcol[mtA]) >> 1) + (m >> 1);
-#pragma unroll
-                    for (int nt = 0; nt < WN; ++nt)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int g = r >> 2, j = r & 3;
-                            const int c = cbase + nt * 32 + 8 * g + 4 * hq + j;
-                            if (j == 0) load_quad(nt, g);
-                            float v = fmaxf(acc[mtA][nt][r], acc[mtB][nt][r]);
-                            v = fmaxf(v, __shfl_xor(v, 1, 64));
-                            v = fin(v, nt, g, j);
-                            if (!(m & 1) && yy < Hy && xx < Wy && c < p.Cout)
-                                reinterpret_cast<__bf16*>(p.y)[(((size_t)b * Hy + yy) * Wy + xx) * p.Cout + c] = (__bf16)v;
-                        }
-                }
-            }
-        } else if (!POOL) {
-            auto write_tile = [&](int mt, char* slab) {
-#pragma unroll
-                for (int nt = 0; nt < WN; ++nt)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        bf16x4 q;
-                        load_quad(nt, g);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) q[j] = (__bf16)fin(acc[mt][nt][4 * g + j], nt, g, j);
-                        *reinterpret_cast<bf16x4*>(slab + wr_off(m, nt * 4 + g)) = q;
-                    }
-            };
-            write_tile(0, slab0);
-#pragma unroll
-            for (int mt = 0; mt < WM; ++mt) {
-                if (mt + 1 < WM) write_tile(mt + 1, slab0 + ((mt + 1) & 1) * SLABB);
-                const char* slab = slab0 + (mt & 1) * SLABB;
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq)
-                    store8(rd_chunk(slab, gq), oy0 + trow[mt], ox0 + tcol[mt] + gq * 8 + prow);
-            }
-        } else {
-            // fused 2x2 max-pool: vertical partner = the M-tile one row below (same lane), horizontal partner = the
-            // neighbouring lane; even lanes keep the pooled pixel m/2 (16 per M-tile pair)
-#pragma unroll
-            for (int pr = 0; pr < WM / 2; ++pr) {
-                const int mtA = (TN == 128) ? (pr & 1) : 0;
-                const int mtB = (TN == 128) ? (2 + (pr & 1)) : 1;
-                const int yy = (oy0 + trow[mtA]) >> 1;
-                const int xb = (ox0 + tcol[mtA]) >> 1;
-                const int pc = m >> 1;
-                char* slab = slab0 + (pr & 1) * SLABB;
-#pragma unroll
-                for (int nt = 0; nt < WN; ++nt)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        bf16x4 q;
-                        unsigned code4 = 0;
-                        load_quad(nt, g);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float a00 = acc[mtA][nt][4 * g + j], a10 = acc[mtB][nt][4 * g + j];
-                            const float a01 = __shfl_xor(a00, 1, 64), a11 = __shfl_xor(a10, 1, 64);
-                            const float mx = fmaxf(fmaxf(a00, a01), fmaxf(a10, a11));
-                            q[j] = (__bf16)fin(mx, nt, g, j);
-                            // first position attaining the max, scan order (0,0),(0,1),(1,0),(1,1) as torch's max_pool2d
-                            const unsigned code = (a00 == mx) ? 0u : (a01 == mx) ? 1u : (a10 == mx) ? 2u : 3u;
-                            code4 |= code << (8 * j);
-                        }
-                        if (!(m & 1)) {
-                            *reinterpret_cast<bf16x4*>(slab + wr_off(pc, nt * 4 + g)) = q;
-                            const int c = cbase + nt * 32 + 8 * g + 4 * hq;
-                            if (p.pool_code != nullptr && yy < Hy && xb + pc < Wy && c < p.Cout)
-                                *reinterpret_cast<unsigned*>(p.pool_code + (((size_t)b * Hy + yy) * Wy + xb + pc) * p.Cout + c) = code4;
-                        }
-                    }
-#pragma unroll
-                for (int gq = 0; gq < 2; ++gq)
-                    store8(rd_chunk(slab, gq), yy, xb + gq * 8 + prow);
-            }
-        }
-    }
-#else
     // ---- epilogue
     float bv[WN], dm[WN];
     int nch[WN];
@@ -684,7 +435,6 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
                     }
         }
     }
-#endif      // WITW_BF_SWAP
 #ifdef WITW_BF_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0 && p.stamps != nullptr) {
@@ -699,35 +449,6 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
         o[7] = __builtin_amdgcn_s_memrealtime() - r_start;     // 100 MHz ticks
     }
 #endif
-}
-
-// Hand-issued fragment reads of the 16x16x32 kernel below: asm volatile keeps them where they are written (left to the scheduler,
-// refills are hoisted above the MFMAs that still read the old fragment and cost a second register set: 49 spills), the matching
-// s_waitcnt counts the reads issued after the one that is needed (LDS returns in order; extra LDS operations of the compiler
-// in the queue only make a wait stricter).
-__device__ __forceinline__ u32x4 s16_read(unsigned addr, int off) {      // off: a constant once the caller's loops are unrolled
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(off));
-    return v;
-}
-__device__ __forceinline__ void s16_wait(int n, u32x4& a) {
-    switch (n) {      // n is a constant once the caller's loops are unrolled
-    case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a)); break;
-    case 1: asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(a)); break;
-    case 2: asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(a)); break;
-    case 3: asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(a)); break;
-    case 4: asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(a)); break;
-    case 5: asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(a)); break;
-    case 6: asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(a)); break;
-    default: asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(a)); break;
-    }
-}
-__device__ __forceinline__ void s16_wait5(int n, u32x4& a, u32x4& b0, u32x4& b1, u32x4& b2, u32x4& b3) {
-    switch (n) {
-    case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3)); break;
-    case 1: asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(a), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3)); break;
-    default: asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(a), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3)); break;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -754,7 +475,7 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_s16_kernel(ConvBfArgs p) {
     // multiple of 16 slots (64 banks): IH*IW = 660 = 4 mod 16 put pixels 12-15 of plane 0 on the banks of pixels 8-11 of plane 1 --
     // every A read 2-way, 36-38 % of the LDS-active cycles (profiles/r05_bf16_train_lds_pmc.txt). 672 slots per plane: the stage
     // keeps its size (2 * 672 = 1344 = the 64-slot round-up of 1320 it already had).
-    constexpr int PL = WITW_BF_S16_PLANE16 ? (IH * IW + 15) / 16 * 16 : IH * IW;
+    constexpr int PL = (IH * IW + 15) / 16 * 16;
     constexpr int IN_S = 2 * PL;
     constexpr int IN_P = (IN_S + 63) / 64 * 64;
     constexpr int W_S = 9 * 2 * TN;
@@ -799,35 +520,6 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_s16_kernel(ConvBfArgs p) {
     __amdgpu_buffer_rsrc_t in_rs =
         __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b * img_elems), 0, (unsigned)(img_elems * 2), 0x00020000);
     const i32x4 w_rd = raw_rsrc(reinterpret_cast<const u32x4*>(p.wpk) + (size_t)ntile * nkc * W_S, (unsigned)nkc * W_S * 16u);
-#if WITW_BF_S16_DMA
-    // input tile by LDS-DMA too: slot s = instruction * 64 + lane IS the LDS position [group][pixel]; no register transit
-    constexpr int NIN_D = (IN_P / 64 + NW - 1) / NW;
-    const i32x4 in_rd = raw_rsrc(p.x + (size_t)b * img_elems, (unsigned)(img_elems * 2));
-    unsigned gin[NIN_D];
-#pragma unroll
-    for (int i = 0; i < NIN_D; ++i) {
-        const int s = (wave + NW * i) * 64 + lane;
-        const int q = s / PL;
-        const int pix = s - q * PL;
-        const int r = pix / IW, c = pix - r * IW;
-        int gr = oy0 - 1 + r;
-        int gc = ox0 - 1 + c;
-        bool ok = s < IN_S && pix < IH * IW && gr >= 0 && gr < p.H;
-        if (TRAIN && p.dil_h) {
-            ok = ok && !(gr & 1);
-            gr >>= 1;
-        }
-        if (p.circ) {
-            gc %= p.W;
-            if (gc < 0) gc += p.W;
-        } else {
-            ok = ok && gc >= 0 && gc < p.W;
-        }
-        gin[i] = ok ? (unsigned)((((size_t)gr * p.W + gc) * p.Cin + q * 8) * 2) : OOR;
-    }
-    constexpr int P_IN = NIN_D;
-#else
-    constexpr int P_IN = NIN;
     unsigned gin[NIN];
 #pragma unroll
     for (int i = 0; i < NIN; ++i) {
@@ -850,36 +542,25 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_s16_kernel(ConvBfArgs p) {
         gin[i] = ok ? (unsigned)((((size_t)gr * p.W + gc) * p.Cin + q * 8) * 2) : OOR;
     }
     u32x4 rin[NIN];
-#endif
     const unsigned lane16 = (unsigned)lane * 16u;
-    constexpr int PIECES = P_IN + NWT_D;
+    constexpr int PIECES = NIN + NWT_D;
     auto stage_piece = [&](int kc, u32x4* in_s, int pc) {
-        if (pc < P_IN) {
-#if WITW_BF_S16_DMA
-            const unsigned in_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_address(in_s));
-            const int j = wave_u + NW * pc;
-            if (NIN_D * NW == IN_P / 64 || j < IN_P / 64) dma16(in_rd, in_lds + (unsigned)j * 1024u, gin[pc], (unsigned)kc * 32u);
-#else
+        if (pc < NIN) {
             rin[pc] = __builtin_amdgcn_raw_buffer_load_b128(in_rs, gin[pc], (unsigned)kc * 32u, 0);
-#endif
         } else {
             const unsigned in_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_address(in_s));
-            const int j = wave_u + NW * (pc - P_IN);
+            const int j = wave_u + NW * (pc - NIN);
             if (NWT_D * NW == W_S / 64 || j < W_S / 64)
                 dma16(w_rd, in_lds + (unsigned)(IN_P + j * 64) * 16u, lane16, (unsigned)kc * W_S * 16u + (unsigned)j * 1024u);
         }
     };
     auto stage_commit = [&](u32x4* in_s) {
-#if WITW_BF_S16_DMA
-        (void)in_s; (void)dummy_slot;
-#else
 #pragma unroll
         for (int i = 0; i < NIN; ++i) {
             const int s = tid + i * NTHREADS;
             u32x4* dst = (NIN * NTHREADS == IN_S || s < IN_S) ? in_s + (s & 1) * PL + (s >> 1) : dummy_slot;
             *dst = rin[i];
         }
-#endif
     };
     auto stage_wait = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); };      // vmcnt(0)
 
@@ -898,6 +579,8 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_s16_kernel(ConvBfArgs p) {
         for (int bt = 0; bt < 4; ++bt) acc[a][bt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     u32x4 fa[4], fb[2][4];      // A: one set, refilled in place as soon as a tile's MFMAs are issued; B: one set per tap pair
+    // The fragments are read by hand (lds_read128 / lds_wait, lds_frag.h): left to the scheduler, refills are hoisted above the MFMAs
+    // that still read the old fragment and cost a second register set (49 spills).
     auto tap_off = [](int t) { return (t / 3) * IW + t % 3; };
     // Tap pairs are chosen so that the two taps of a pair differ by the same amount in most pairs and the lane-dependent part of
     // an address is one of few registers: P0 = (0,1), P1 = (3,4), P2 = (6,7) (one column apart), P3 = (2,5) (one row apart);
@@ -921,14 +604,14 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_s16_kernel(ConvBfArgs p) {
     auto read_a = [&](int st, int pr, int h, int i) -> u32x4 {      // st: 0 / 1 = a stage, 2 = the shared pair
         const int a = 4 * h + i;
         const int tile = (a >> 2) * IW + 16 * (a & 3);
-        if (st == 2) return s16_read(a_lS, tile * 16);
+        if (st == 2) return lds_read128(a_lS, tile * 16);
         const int t0 = (pr == 0) ? 0 : (pr == 1) ? 3 : (pr == 2) ? 6 : 2;
-        return s16_read((pr == 3) ? a_lW[st] : a_l1[st], (tap_off(t0) + tile) * 16);
+        return lds_read128((pr == 3) ? a_lW[st] : a_l1[st], (tap_off(t0) + tile) * 16);
     };
     auto read_b = [&](int st, int pr, int bt) -> u32x4 {
-        if (st == 2) return s16_read(w_lS, 16 * bt * 16);
+        if (st == 2) return lds_read128(w_lS, 16 * bt * 16);
         const int t0 = (pr == 0) ? 0 : (pr == 1) ? 3 : (pr == 2) ? 6 : 2;
-        return s16_read((pr == 3) ? w_l3[st] : w_l1[st], (t0 * 2 * TN + 16 * bt) * 16);
+        return lds_read128((pr == 3) ? w_l3[st] : w_l1[st], (t0 * 2 * TN + 16 * bt) * 16);
     };
 
 #pragma unroll
@@ -982,10 +665,10 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_s16_kernel(ConvBfArgs p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (h == 0) {       // the previous unit issued A0 B0 B1 A1 B2 B3 A2 A3
-                    if (i == 0) s16_wait5(2, fa[0], fb[sb][0], fb[sb][1], fb[sb][2], fb[sb][3]);
-                    else s16_wait(i == 1 ? 5 : 3, fa[i]);
+                    if (i == 0) lds_wait(2, fa[0], fb[sb][0], fb[sb][1], fb[sb][2], fb[sb][3]);
+                    else lds_wait(i == 1 ? 5 : 3, fa[i]);
                 } else {            // the previous unit issued A0 A1 A2 A3
-                    s16_wait(i == 0 ? 3 : i == 1 ? 5 : 7, fa[i]);
+                    lds_wait(i == 0 ? 3 : i == 1 ? 5 : 7, fa[i]);
                 }
 #pragma unroll
                 for (int bt = 0; bt < 4; ++bt)
@@ -1181,16 +864,8 @@ __global__ void maxpool2x2_bwd_bf16_kernel(const unsigned short* __restrict__ dy
 
 template <int TN, int SH, bool POOL, int NW>
 int launch_bf_nw(ConvBfArgs a, hipStream_t st) {
-    a.tiles_y = cdiv(a.Ho, NW);
-    const long long sp_total = (long long)a.B * a.tiles_x * a.tiles_y;
-    a.n_tiles = cdiv(a.Cout, TN);
-    a.sp_per_xcd = (int)((sp_total + 7) / 8);
-    const long long grid = a.xcd_map ? 8LL * a.sp_per_xcd * a.n_tiles : sp_total * a.n_tiles;
-    if (grid <= 0 || grid > 0x7fffffffLL || sp_total > 0x7fffffffLL) {
-        witw_set_error("conv3x3_bf16: grid %lld out of range", grid);
-        return WITW_ERR_INVALID;
-    }
-    a.sp_total = (int)sp_total;
+    const long long grid = witw_conv_grid(a, NW, TN, "conv3x3_bf16");
+    if (!grid) return WITW_ERR_INVALID;
     hipLaunchKernelGGL((conv3x3_nhwc_bf16_kernel<TN, SH, POOL, NW>), dim3((unsigned)grid), dim3(64 * NW), 0, st, a);
     WITW_CHECK_LAUNCH("conv3x3_nhwc_bf16");
     witw_note_variant("conv3x3_nhwc_bf16_kernel<%d,%d,%s,%d>", TN, SH, POOL ? "true" : "false", NW);
@@ -1209,16 +884,8 @@ int bf16_mfma16() {
 
 template <bool POOL, bool TRAIN>
 int launch_bf_s16(ConvBfArgs a, hipStream_t st) {
-    a.tiles_y = cdiv(a.Ho, 8);
-    const long long sp_total = (long long)a.B * a.tiles_x * a.tiles_y;
-    a.n_tiles = cdiv(a.Cout, 128);
-    a.sp_per_xcd = (int)((sp_total + 7) / 8);
-    const long long grid = a.xcd_map ? 8LL * a.sp_per_xcd * a.n_tiles : sp_total * a.n_tiles;
-    if (grid <= 0 || grid > 0x7fffffffLL || sp_total > 0x7fffffffLL) {
-        witw_set_error("conv3x3_bf16: grid %lld out of range", grid);
-        return WITW_ERR_INVALID;
-    }
-    a.sp_total = (int)sp_total;
+    const long long grid = witw_conv_grid(a, 8, 128, "conv3x3_bf16");
+    if (!grid) return WITW_ERR_INVALID;
     hipLaunchKernelGGL((conv3x3_bf16_s16_kernel<POOL, TRAIN>), dim3((unsigned)grid), dim3(512), 0, st, a);
     WITW_CHECK_LAUNCH("conv3x3_bf16_s16");
     witw_note_variant("conv3x3_bf16_s16_kernel<%s,%s>", POOL ? "true" : "false", TRAIN ? "true" : "false");
@@ -1319,8 +986,7 @@ int witw_conv3x3_bf16_fwd_ex(const void* x_bf16, const void* wpk_bf16, const flo
 #ifdef WITW_BF_STAMPS
     a.stamps = witw_bf16_stamps_ptr;
 #endif
-    const char* e = getenv("WITW_CONV_XCD");
-    a.xcd_map = e ? atoi(e) != 0 : 1;
+    a.xcd_map = witw_conv_xcd_map();
     hipStream_t st = (hipStream_t)stream;
     // 64 input channels, plain forward: the kernel that keeps the filter in LDS (conv3x3_bf16_wres.hip; bit-identical to the 32x32x16 kernel)
     // (round 5: also the gated form, i.e. the data gradient of a 64-channel layer -- cvig_semantic's layer 2, where layer 0 trains)

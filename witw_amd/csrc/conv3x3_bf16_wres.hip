@@ -32,11 +32,6 @@
 #ifndef WITW_WRES_DMA
 #define WITW_WRES_DMA 1         // 1: the input tile by LDS-DMA into a pixel-major, XOR-swizzled image; 0: through registers + ds_write_b128
 #endif
-#ifndef WITW_WRES_DIRECT
-#define WITW_WRES_DIRECT 0      // 1: the epilogue stores from registers (v_permlane32_swap forms 16-byte channel octets); 0: through the LDS slab.
-                                // Measured (same box): in-kernel cycles per iteration 6.7 k -> 5.6 k, wall time 0.266-0.279 -> 0.270-0.275 ms with
-                                // plain stores (0.449 with non-temporal ones: the four 32-byte pieces of a line leave L2 one by one): no gain, off
-#endif
 #ifndef WITW_WRES_DIAG
 #define WITW_WRES_DIAG 0        // diagnostic builds (wrong results): 1 = no waits on the operand reads, 2 = no operand reads, 4 = no V-phase work, 8 = no input -> LDS writes, 16 = no slab traffic in the epilogue
 #endif
@@ -90,18 +85,6 @@ struct WresArgs {
 __device__ __forceinline__ void wres_wave_sync() {      // one wave's LDS traffic is processed in issue order: drain the counter, pin the compiler
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-}
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-// global -> LDS, 16 B per lane, 1 KB of contiguous LDS per wave instruction at lds_addr (M0); out-of-range lanes write zeros
-__device__ __forceinline__ void wres_dma16(i32x4 rs, unsigned lds_addr, unsigned voff) {
-    // m0 is written here and is NOT on the clobber list: it is a reserved register for LLVM's AMDGPU back end (clang warns "clobber
-    // list contains reserved registers: m0 ... undefined behaviour" when it is listed), which keeps no value live in it across
-    // instructions and re-sets it right before each of its own uses (LDS-DMA builtins, movrel, sendmsg). ADVICE r04.
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-                 :
-                 : "s"(lds_addr), "v"(voff), "s"(rs)
-                 : "memory");
 }
 
 __device__ unsigned long long wres_stamps[2][8];     // WITW_WRES_STAMPS=1 diagnostic: phase ticks of waves 0 and 4 (one per team), third iteration of workgroup 0
@@ -227,7 +210,7 @@ __global__ __launch_bounds__(WRT, 1) void conv3x3_bf16_wres_kernel(WresArgs p) {
                 off += (m & F_LEFT) ? f_add_l : 0u;
                 off += (m & F_RIGHT) ? f_add_r : 0u;
                 off = ((m & (f_kill & 15u)) || (m >> 31)) ? OOR : off;
-                wres_dma16(d_rs, lds_img + (unsigned)(wt * DPW + j) * 1024u, off);
+                dma16(d_rs, lds_img + (unsigned)(wt * DPW + j) * 1024u, off);
             }
         }
     };
@@ -257,43 +240,14 @@ __global__ __launch_bounds__(WRT, 1) void conv3x3_bf16_wres_kernel(WresArgs p) {
     bool pvalid = false;
     // ---- epilogue, D[channel][pixel]: lane = pixel l31, registers 4j..4j+3 of accumulator nt = channels nt*32 + 8j + 4hq + {0..3};
     // one row (8 pixels) of the M-tile at a time through the slab: 8 x 128 bytes = 64 lanes x 16 bytes
-    auto epilogue = [&]() {
+    // (the captures are listed, in this order, on purpose: the closure's field order reaches the register allocation, and the
+    // allocation of this kernel is the one build.py validates)
+    auto epilogue = [&hq, &poy0, &mrow, &l31, &pox0, &mcol, &p, &pb, &cb, &acc, &relu_floor, &pvalid, &slab, &lane, &gt, &gate_mask, &gb, &bits_mask]() {
         f32x4 bq[2][4];                             // bq[nt][j][e]: channel cb*64 + nt*32 + 8j + 4hq + e <-> register 4j+e of accumulator nt
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int j = 0; j < 4; ++j) bq[nt][j] = reinterpret_cast<const f32x4*>(bias_s)[nt * 8 + 2 * j + hq];
-        if (WITW_WRES_DIRECT) {
-            // straight from the registers: lane (pixel l31, half hq) holds channels 8j + 4hq .. + 3 of every octet j as one 8-byte pair;
-            // v_permlane32_swap exchanges the upper half-wave of octet j with the lower half-wave of octet j + 1, after which a lower
-            // lane holds all 8 channels of octet j of its pixel and the upper lane of the same pixel all 8 of octet j + 1: one 16-byte
-            // store each, 32 contiguous bytes per pixel and instruction, four instructions per wave -- and no LDS traffic under the
-            // other team's operand reads (the slab form's writes and read-backs cost 7 % of the kernel in the switch-off builds)
-            const int oy = poy0 + 4 * mrow + (l31 >> 3), ox = pox0 + 8 * mcol + (l31 & 7);
-            unsigned short* dst = p.y + (((size_t)pb * p.H + oy) * p.W + ox) * p.Cout + cb * 64 + 8 * hq;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int jp = 0; jp < 2; ++jp) {
-                    unsigned x[2][2];                   // [octet of the pair][dword]
-#pragma unroll
-                    for (int o = 0; o < 2; ++o) {
-                        const int j = 2 * jp + o;
-                        x[o][0] = witw_relu_bf16x2(witw_pack_bf16x2(acc[nt][4 * j] + bq[nt][j][0], acc[nt][4 * j + 1] + bq[nt][j][1]), relu_floor);
-                        x[o][1] = witw_relu_bf16x2(witw_pack_bf16x2(acc[nt][4 * j + 2] + bq[nt][j][2], acc[nt][4 * j + 3] + bq[nt][j][3]), relu_floor);
-                    }
-                    u32x4 v;
-#pragma unroll
-                    for (int d = 0; d < 2; ++d) {
-                        const auto sw = __builtin_amdgcn_permlane32_swap(x[0][d], x[1][d], false, false);
-                        v[d] = sw[0];
-                        v[2 + d] = sw[1];
-                    }
-                    // plain stores: the four 32-byte pieces of a pixel's 128-byte line must meet in L2 before the line leaves it
-                    if (pvalid) *reinterpret_cast<u32x4*>(dst + nt * 32 + 16 * jp) = v;
-                }
-            return;
-        }
         // two rounds of two M-tile rows (16 pixels) through the slab. One wave's LDS operations execute in order, so neither the
         // read-back behind the writes nor the second round's writes behind the first round's reads need a wait of their own: the
         // only waits are the ones in front of the stores (the values' first use). (A first form synchronised four one-row rounds:

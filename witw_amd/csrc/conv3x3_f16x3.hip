@@ -14,12 +14,12 @@
 //     9 + 5 = 14 MFMA steps per 8-channel chunk (the 9th tap pairs with zeros);
 //   * packed filter per chunk: 9 slots w_hi(tap) + 5 x 2 slots w_lo(tap pair) = 19 slots of TN x 16 B.
 #include "common.h"
+#include "conv_launch.h"
+#include "lds_frag.h"
 
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TW = 64;
 constexpr int IW = TW + 2;
@@ -28,30 +28,6 @@ constexpr int NSTEP = 14;       // MFMA steps per chunk: 9 taps + 5 tap pairs
 #ifndef WITW_HX_SPREAD
 #define WITW_HX_SPREAD 5        // steps over which the staging pieces of a chunk are issued
 #endif
-
-__device__ __forceinline__ i32x4 raw_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu));
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
-
-// one wave instruction of LDS-DMA (see conv3x3_bf16.hip): lane l moves 16 B from rs[voff_l + soff] to LDS lds_addr + 16*l
-__device__ __forceinline__ void dma16(i32x4 rs, unsigned lds_addr, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :
-                 : "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff)
-                 : "memory");
-#endif
-}
-
-__device__ __forceinline__ unsigned lds_address(const void* p) {
-    return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)p;
-}
 
 struct ConvHxArgs {
     const unsigned short* x;   // [B,H,W,Cin/8,2,8] split-fp16 NHWC (Cin % 8 == 0)
@@ -525,16 +501,8 @@ __global__ void maxpool2x2_bwd_split_kernel(const unsigned short* __restrict__ d
 
 template <int TN, int SH, bool POOL, int NW>
 int launch_hx_nw(ConvHxArgs a, hipStream_t st) {
-    a.tiles_y = cdiv(a.Ho, NW);
-    const long long sp_total = (long long)a.B * a.tiles_x * a.tiles_y;
-    a.n_tiles = cdiv(a.Cout, TN);
-    a.sp_per_xcd = (int)((sp_total + 7) / 8);
-    const long long grid = a.xcd_map ? 8LL * a.sp_per_xcd * a.n_tiles : sp_total * a.n_tiles;
-    if (grid <= 0 || grid > 0x7fffffffLL || sp_total > 0x7fffffffLL) {
-        witw_set_error("conv3x3_f16x3: grid %lld out of range", grid);
-        return WITW_ERR_INVALID;
-    }
-    a.sp_total = (int)sp_total;
+    const long long grid = witw_conv_grid(a, NW, TN, "conv3x3_f16x3");
+    if (!grid) return WITW_ERR_INVALID;
     hipLaunchKernelGGL((conv3x3_nhwc_f16x3_kernel<TN, SH, POOL, NW>), dim3((unsigned)grid), dim3(64 * NW), 0, st, a);
     WITW_CHECK_LAUNCH("conv3x3_nhwc_f16x3");
     witw_note_variant("conv3x3_nhwc_f16x3_kernel<%d,%d,%s,%d>", TN, SH, POOL ? "true" : "false", NW);
@@ -624,8 +592,7 @@ int witw_conv3x3_f16x3_fwd_ex(const void* x_split, const void* wpk_f16, const fl
     a.dropmask = dropmask; a.gate = (const unsigned short*)gate_split; a.dil_h = dilate_h ? 1 : 0;
     a.pool_code = pool ? pool_code : nullptr;
     a.overflow = overflow_flag;
-    const char* e = getenv("WITW_CONV_XCD");
-    a.xcd_map = e ? atoi(e) != 0 : 1;
+    a.xcd_map = witw_conv_xcd_map();
     hipStream_t st = (hipStream_t)stream;
     if (Cout >= 128) {
         if (stride_h == 2) return launch_hx<128, 2, false>(a, st);

@@ -22,43 +22,17 @@
 // fragment they hold anyway to two v_mfma_f32_16x16x32_bf16 against a constant 'ones in row 0' operand (+1/9 MFMA
 // time on 1/(Cin/64) of the workgroups) instead of a separate pass over dZ.
 #include "common.h"
+#include "lds_frag.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int WB_P = 8;                 // output columns per chunk
 constexpr int WB_XC = WB_P + 2;         // halo columns
 constexpr int WB_TM = 64, WB_TN = 128;  // ci x co tile of a workgroup
 constexpr unsigned OOR = 0x80000000u;
-
-__device__ __forceinline__ i32x4 raw_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu));
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
-
-// one wave instruction of LDS-DMA: lane l moves 16 B from rs[voff_l + soff] to LDS byte lds_addr + 16*l
-// (out-of-range lanes store zeros); see conv3x3_bf16.hip for why this is inline assembly
-__device__ __forceinline__ void dma16(i32x4 rs, unsigned lds_addr, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :
-                 : "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff)
-                 : "memory");
-#endif
-}
-
-__device__ __forceinline__ unsigned lds_address(const void* p) {
-    return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)p;
-}
 
 struct WgradBfArgs {
     const unsigned short* x;    // [B8][H][W][Cin][8]   bf16, batch-octet layout
@@ -324,11 +298,6 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int NH_P = 16;                // output columns per k-step
 constexpr int NH_XP = 24;               // pixel pitch of a halo row in the LDS (18 used: 3 DMA instructions of 8 pixels per row)
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {      // s_waitcnt vmcnt(N) only (expcnt / lgkmcnt left alone); N <= 63
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70);
-}
 
 // Wave roles: NWM x NWN waves cover the 32-channel slabs of the tile (ci x co) that EXIST -- a layer with Cin <= 32 has one ci slab
 // (NWM = 1), one with Cout <= 64 / <= 32 two / one co slabs -- and the remaining factor KS = 8 / (NWM * NWN) splits the stage's R

@@ -13,40 +13,16 @@
 // columns: 3 x 10 halo pixels of X and 8 pixels of dZ, both planes, by LDS-DMA into a [pixel][plane][channel] image
 // (conflict-free ds_read_b128), double buffered (2 x 76 KB).
 #include "common.h"
+#include "lds_frag.h"
 
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WH_P = 8;                 // output columns per chunk
 constexpr int WH_XC = WH_P + 2;         // halo columns
 constexpr int WH_T = 64;                // ci and co tile of a workgroup
 constexpr unsigned OOR = 0x80000000u;
-
-__device__ __forceinline__ i32x4 raw_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu));
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
-
-__device__ __forceinline__ void dma16(i32x4 rs, unsigned lds_addr, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :
-                 : "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff)
-                 : "memory");
-#endif
-}
-
-__device__ __forceinline__ unsigned lds_address(const void* p) {
-    return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)p;
-}
 
 struct WgradHxArgs {
     const unsigned short* x;    // [B8][H][W][Cin][2][8]   fp16, batch-octet split layout
