@@ -1,7 +1,8 @@
-// Hand-issued memory primitives of the reduced-precision convolution kernels (gfx950): LDS-DMA loads with a counted vmcnt wait,
-// and LDS fragment reads with counted lgkmcnt waits. Every sequence below is inline assembly ON PURPOSE: it keeps the order it is
-// written in, and the kernel, not the compiler, decides where the wave waits. The three kernels that read fragments this way are
-// correct only for the register allocations validated in build.py.
+// Hand-issued memory primitives (gfx950) of the reduced-precision convolution kernels and of the spectral match (match_dft.hip,
+// which takes the LDS-DMA part and reads its fragments with helpers of its own): LDS-DMA loads with a counted vmcnt wait, and LDS
+// fragment reads with counted lgkmcnt waits. Every sequence below is inline assembly ON PURPOSE: it keeps the order it is written
+// in, and the kernel, not the compiler, decides where the wave waits. The three convolution kernels that read fragments this way
+// are correct only for the register allocations validated in build.py.
 #pragma once
 #include "common.h"
 
