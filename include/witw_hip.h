@@ -159,7 +159,9 @@ int witw_match_fwd_masked(const float* ov, const float* su, int Bo, int Bs, int 
  * distance and score are taken there and are BIT-IDENTICAL to witw_match_fwd_masked with shift_mask[s] = 1 << (shift[s] & 63) (the
  * same fp32 MFMA chain per pair, row outer, k inner). Any output may be NULL. workspace: witw_match_fixed_workspace_floats(Bo,Bs)
  * floats; it begins with the window norms [Bo,64] and surface norms [Bs] of a witw_match_fwd workspace, so witw_match_bwd,
- * witw_match_bwd_pairs and witw_match_pairs* take it as they take that one; the grouping of the surfaces by shift follows. */
+ * witw_match_bwd_pairs and witw_match_pairs* take it as they take that one; the grouping of the surfaces by shift follows. Only
+ * those first Bo * 64 + Bs floats are defined on return: the grouping table is sized for the worst case and written as far as the
+ * shifts of this batch need, the entries behind that are left as they were. */
 long long witw_match_fixed_workspace_floats(int Bo, int Bs);
 int witw_match_fwd_fixed(const float* ov, const float* su, int Bo, int Bs, int We, const long long* shift /* [Bs], device */,
                          long long* orientation, float* distance, float* score, float* workspace, void* stream);

@@ -575,7 +575,9 @@ def match_fwd_fixed(overhead_embed, surface_embed, shift, want_score=False, want
     embedding its one shift (used as shift & 63), so a pair costs 2*64*We FLOP instead of 64 times that. Returns what match_fwd
     returns -- orientation ([Bo,Bs], = shift & 63 broadcast; None with want_orientation=False, which spares its 8 bytes per pair),
     distance[, score][, workspace] -- with distance and score bit-identical to match_fwd(..., shift_mask=1 << (shift & 63)). The
-    workspace begins with the norms match_bwd / match_pairs read."""
+    workspace begins with the norms match_bwd / match_pairs read: its first Bo * 64 + Bs floats are defined. The rest is the
+    launch's own table of shift groups, sized for the worst case and written only as far as this batch's shifts need; its
+    remaining entries are undefined."""
     lib = _lib.load()
     ov, su, Bo, Bs, We = _match_operands('match_fwd_fixed', overhead_embed, surface_embed)
     _check_query_words('match_fwd_fixed', 'shift', shift, Bs, ov.device)
