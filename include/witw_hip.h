@@ -216,6 +216,13 @@ int witw_topk_smallest(const float* distance, float* values, long long* indices,
 long long witw_topk_workspace_bytes(int Bo, int Bs, int k);
 int witw_topk_smallest_ws(const float* distance, float* values, long long* indices, int Bo, int Bs, int k, long long row_offset,
                           void* workspace, void* stream);
+/* the next k places of such a list: the k smallest among the rows that lie strictly behind (after_value[q], after_index[q]) in
+ * the same order -- the bound is an entry of the list so far, usually its last: f32 [Bs] and int64 [Bs], the index a global row
+ * number as row_offset produces them. A NaN after_value counts as +inf, as a NaN distance does; after_index -1 (the pad) has
+ * nothing behind it: k pads. A list of any length is witw_topk_smallest_ws followed by calls of this entry, each bounded by the
+ * last place of the one before. Workspace as for witw_topk_smallest_ws (witw_topk_workspace_bytes). 1 <= k <= 32. */
+int witw_topk_smallest_after(const float* distance, float* values, long long* indices, int Bo, int Bs, int k, long long row_offset,
+                             const float* after_value, const long long* after_index, void* workspace, void* stream);
 /* sharded-gallery form: ranks[q] = #{o in this shard : D[o][q] <= threshold[q]} (threshold = true match's distance) */
 int witw_rank_count_thresh(const float* distance, const float* threshold, int* ranks, int Bo, int Bs, void* stream);
 

@@ -112,6 +112,8 @@ SIGNATURES = {
     'witw_topk_smallest': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_longlong, c_void_p]),
     'witw_topk_workspace_bytes': (c_longlong, [c_int, c_int, c_int]),
     'witw_topk_smallest_ws': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_longlong, c_void_p, c_void_p]),
+    'witw_topk_smallest_after': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     'witw_rank_count_thresh': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'witw_match_pairs': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 4),
     'witw_match_pairs_impl': (c_int, [c_int]),

@@ -1648,11 +1648,16 @@ namespace {
 // Gallery rows can be split over blockIdx.y (pv / pi non-null): a block then ranks rows [y*rps, (y+1)*rps) and leaves its k
 // candidates per query in the workspace, merged by topk_merge_kernel -- one block per 64 queries walking 125,000 rows alone is
 // 64 workgroups of dependent loads (16 ms per 125,000 x 4,096 launch; the matrix streams from HBM in 0.5 ms).
-template <int K>
+// AFTER (witw_topk_smallest_after): the scan resumes behind a bound per query, (after_v[q], after_i[q]) with the index a global
+// row number: only rows strictly behind it in the list's own order are admitted, so the result is the next k places of the
+// list the bound is an entry of. The bound is brought into that order first -- a NaN value is +inf as a NaN distance is, the
+// index becomes this launch's row number -- and index -1, the missing candidate that ends a list, has nothing behind it.
+template <int K, bool AFTER>
 __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ D, float* __restrict__ vals,
                                                    long long* __restrict__ idx, int Bo, int Bs, int k, long long row_offset,
                                                    int rps, float* __restrict__ pv, int* __restrict__ pi,
-                                                   const float* __restrict__ tau, int tau_stride) {
+                                                   const float* __restrict__ tau, int tau_stride,
+                                                   const float* __restrict__ after_v, const long long* __restrict__ after_i) {
     __shared__ float sv[4][K][64];
     __shared__ int si[4][K][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1670,9 +1675,24 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ D, 
     // without it every split starts from empty lists and nearly every batch of its first thousand rows triggers an insertion
     // (1.3 TB/s over the 2 GB matrix); with it the scan is loads and compares.
     const float tq = (tau != nullptr && q < Bs) ? tau[(size_t)q * tau_stride] : __builtin_inff();
+    float av = -__builtin_inff();
+    int ao = -1;
+    if constexpr (AFTER) {
+        if (q < Bs) {
+            const float a = after_v[q];
+            const long long g = after_i[q];
+            const long long l = g - row_offset;
+            av = (g == -1 || a != a) ? __builtin_inff() : a;
+            ao = (g == -1 || l > 0x7fffffffLL) ? 0x7fffffff : (l < -1 ? -1 : (int)l);      // rows are 0 .. Bo-1 < 2^31 - 1
+        }
+    }
+    auto behind = [&](float d, int o) {            // (d, o) lies strictly behind the bound; d is no NaN here
+        if constexpr (!AFTER) return true;
+        else return d > av || (d == av && o > ao);
+    };
     auto offer = [&](float d, int o) {
         if (d != d) d = __builtin_inff();          // NaN sorts last
-        if (d <= tq && (d < bv[K - 1] || (d == bv[K - 1] && o < bi[K - 1]))) {
+        if (d <= tq && behind(d, o) && (d < bv[K - 1] || (d == bv[K - 1] && o < bi[K - 1]))) {
             float cv = d;
             int ci = o;
 #pragma unroll
@@ -1718,7 +1738,8 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ D, 
                 int cu = -1;
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {      // smallest admissible (distance, row) among the rows not yet dealt with
-                    const bool adm = ((live >> u) & 1u) && d[u] <= tq && (d[u] < bv[K - 1] || (d[u] == bv[K - 1] && o + 4 * u < bi[K - 1]));
+                    const bool adm = ((live >> u) & 1u) && d[u] <= tq && behind(d[u], o + 4 * u) &&
+                                     (d[u] < bv[K - 1] || (d[u] == bv[K - 1] && o + 4 * u < bi[K - 1]));
                     if (!adm) live &= ~(1u << u);
                     if (adm && (cu < 0 || d[u] < cv)) { cv = d[u]; cu = u; }      // equal distances: the lower row (lower u) stays
                 }
@@ -1837,30 +1858,34 @@ static int topk_splits(int Bo, int Bs) {
     return s < 1 ? 1 : s;
 }
 
-template <int K>
+// AFTER: every pass over rows of D, the threshold sample included, admits only what lies behind the bound; the merges see lists
+// that were filtered already and stay as they are
+template <int K, bool AFTER>
 static void topk_launch(const float* D, float* values, long long* indices, int Bo, int Bs, int k, long long row_offset,
-                        void* workspace, hipStream_t st) {
+                        const float* after_v, const long long* after_i, void* workspace, hipStream_t st) {
     const int splits = workspace ? topk_splits(Bo, Bs) : 1;
     if (splits <= 1) {
-        hipLaunchKernelGGL((topk_kernel<K>), dim3(cdiv(Bs, 64)), dim3(256), 0, st, D, values, indices, Bo, Bs, k, row_offset, Bo,
-                           (float*)nullptr, (int*)nullptr, (const float*)nullptr, 0);
+        hipLaunchKernelGGL((topk_kernel<K, AFTER>), dim3(cdiv(Bs, 64)), dim3(256), 0, st, D, values, indices, Bo, Bs, k, row_offset, Bo,
+                           (float*)nullptr, (int*)nullptr, (const float*)nullptr, 0, after_v, after_i);
         return;
     }
     float* pv = (float*)workspace;
     int* pi = (int*)(pv + (size_t)splits * k * Bs);
     const int rps = cdiv(Bo, splits);
     // long galleries: the k best of the first TOPK_SAMPLE rows first (into `values`, which the merge overwrites at the end); their k-th
-    // distance bounds every query's k-th distance over all rows and is the main pass's admission threshold
+    // distance bounds every query's k-th distance over all rows and is the main pass's admission threshold (AFTER: the k best of
+    // the sample BEHIND the bound, whose k-th distance bounds the k-th distance behind the bound over all rows; +inf when the
+    // sample holds fewer)
     const float* tau = nullptr;
     if (Bo >= 16 * TOPK_SAMPLE && splits >= TOPK_SAMPLE_SPLITS) {      // (the sample is ranked in row splits too: the workspace is free until the main pass)
-        hipLaunchKernelGGL((topk_kernel<K>), dim3(cdiv(Bs, 64), TOPK_SAMPLE_SPLITS), dim3(256), 0, st, D, values, indices, TOPK_SAMPLE, Bs, k,
-                           row_offset, TOPK_SAMPLE / TOPK_SAMPLE_SPLITS, pv, pi, (const float*)nullptr, 0);
+        hipLaunchKernelGGL((topk_kernel<K, AFTER>), dim3(cdiv(Bs, 64), TOPK_SAMPLE_SPLITS), dim3(256), 0, st, D, values, indices, TOPK_SAMPLE,
+                           Bs, k, row_offset, TOPK_SAMPLE / TOPK_SAMPLE_SPLITS, pv, pi, (const float*)nullptr, 0, after_v, after_i);
         hipLaunchKernelGGL((topk_merge_kernel<K>), dim3(cdiv(Bs, 64)), dim3(64), 0, st, pv, pi, values, indices, Bs, k, TOPK_SAMPLE_SPLITS,
                            row_offset);
         tau = values + (k - 1);
     }
-    hipLaunchKernelGGL((topk_kernel<K>), dim3(cdiv(Bs, 64), splits), dim3(256), 0, st, D, values, indices, Bo, Bs, k, row_offset,
-                       rps, pv, pi, tau, k);
+    hipLaunchKernelGGL((topk_kernel<K, AFTER>), dim3(cdiv(Bs, 64), splits), dim3(256), 0, st, D, values, indices, Bo, Bs, k, row_offset,
+                       rps, pv, pi, tau, k, after_v, after_i);
     hipLaunchKernelGGL((topk_merge_kernel<K>), dim3(cdiv(Bs, 64)), dim3(64), 0, st, pv, pi, values, indices, Bs, k, splits, row_offset);
 }
 
@@ -1871,16 +1896,35 @@ extern "C" long long witw_topk_workspace_bytes(int Bo, int Bs, int k) {
     return splits > 1 ? (long long)splits * k * Bs * 8 : 0;
 }
 
+template <bool AFTER>
+static void topk_dispatch(const float* D, float* values, long long* indices, int Bo, int Bs, int k, long long row_offset,
+                          const float* after_v, const long long* after_i, void* workspace, hipStream_t st) {
+    if (k <= 8) topk_launch<8, AFTER>(D, values, indices, Bo, Bs, k, row_offset, after_v, after_i, workspace, st);
+    else if (k <= 16) topk_launch<16, AFTER>(D, values, indices, Bo, Bs, k, row_offset, after_v, after_i, workspace, st);
+    else topk_launch<32, AFTER>(D, values, indices, Bo, Bs, k, row_offset, after_v, after_i, workspace, st);
+}
+
 extern "C" int witw_topk_smallest_ws(const float* distance, float* values, long long* indices, int Bo, int Bs, int k,
                                      long long row_offset, void* workspace, void* stream) {
     WITW_CHECK_ARG(distance && values && indices, "topk_smallest: null pointer");
     WITW_CHECK_ARG(Bo > 0 && Bs > 0, "topk_smallest: bad shape Bo=%d Bs=%d", Bo, Bs);
     WITW_CHECK_ARG(k >= 1 && k <= 32, "topk_smallest: k=%d outside [1,32]", k);
-    hipStream_t st = (hipStream_t)stream;
-    if (k <= 8) topk_launch<8>(distance, values, indices, Bo, Bs, k, row_offset, workspace, st);
-    else if (k <= 16) topk_launch<16>(distance, values, indices, Bo, Bs, k, row_offset, workspace, st);
-    else topk_launch<32>(distance, values, indices, Bo, Bs, k, row_offset, workspace, st);
+    topk_dispatch<false>(distance, values, indices, Bo, Bs, k, row_offset, nullptr, nullptr, workspace, (hipStream_t)stream);
     WITW_CHECK_LAUNCH("topk_smallest");
+    return WITW_OK;
+}
+
+// The next k places of a list: witw_topk_smallest_ws over the rows that lie strictly behind (after_value[q], after_index[q]) in
+// the order (distance, gallery index) -- the bound is an entry of the list so far, usually its last, in global row numbers.
+extern "C" int witw_topk_smallest_after(const float* distance, float* values, long long* indices, int Bo, int Bs, int k,
+                                        long long row_offset, const float* after_value, const long long* after_index,
+                                        void* workspace, void* stream) {
+    WITW_CHECK_ARG(distance && values && indices, "topk_smallest_after: null pointer");
+    WITW_CHECK_ARG(after_value && after_index, "topk_smallest_after: null bound pointer");
+    WITW_CHECK_ARG(Bo > 0 && Bs > 0, "topk_smallest_after: bad shape Bo=%d Bs=%d", Bo, Bs);
+    WITW_CHECK_ARG(k >= 1 && k <= 32, "topk_smallest_after: k=%d outside [1,32]", k);
+    topk_dispatch<true>(distance, values, indices, Bo, Bs, k, row_offset, after_value, after_index, workspace, (hipStream_t)stream);
+    WITW_CHECK_LAUNCH("topk_smallest_after");
     return WITW_OK;
 }
 

@@ -933,7 +933,8 @@ def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=
     """Top-k retrieval (BASELINE config C5): for every query the k nearest gallery rows by the fused
     orientation-search chord distance, ordered by (distance, gallery index). With the gallery sharded over
     ranks each rank ranks its shard, the [N,k] candidate lists are all-gathered and merged by the same kernel.
-    -> (distances f32 [N,k], gallery indices int64 [N,k]) on the device, identical on every rank. shift_mask / known_shift: see
+    -> (distances f32 [N,k], gallery indices int64 [N,k]) on the device, identical on every rank. 1 <= k <= ops.TOPK_MAX (1024),
+    under every method; places beyond the gallery's rows are missing candidates (+inf, -1). shift_mask / known_shift: see
     retrieve()."""
     return retrieve(overhead_shard, surface_all, k, shard_begin, query_chunk, method, _kernels, _want_ranks=False,
                     shift_mask=shift_mask, known_shift=known_shift)[1:]
@@ -965,6 +966,9 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     2*64*E FLOP per (gallery row, query) and dominates). -> (ranks int64 [N] on the host, distances f32 [N,k],
     gallery indices int64 [N,k] on the device), identical on every rank. The gallery may be sharded raggedly (any
     number of rows per rank, including none); `_kernels` swaps the op set (CPU tests of the collective algebra).
+    1 <= k <= ops.TOPK_MAX (1024): lists longer than 32 places are ops.topk_smallest's resumed scan, per shard and in the merge
+    of the shards' lists; places beyond the gallery's rows are missing candidates (+inf, -1). Under 'dft' / 'dft_masked' lists of
+    more than 32 - DFT_MARGIN places come from the direct pass, the ranks still from the spectral one.
     method='dft': the pass runs through the row spectra (21k instead of 524k FLOP per pair) and every decision that the
     spectral distances leave within fp32 rounding -- a row within DISTANCE_EPS of a query's true-match distance, neighbours
     in a top-k list closer than 2 DISTANCE_EPS -- is re-made on distances from ops.match_pairs, which are bit-identical to the
@@ -978,6 +982,8 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     rank-count and top-k kernels: ranks, distances and indices equal method='direct' under shift_mask = 1 << known_shift exactly.
     'direct' / 'auto' with known_shift run the same pass; 'dft' / 'dft_masked' refuse it."""
     kn = _kernels or ops
+    if not 1 <= int(k) <= ops.TOPK_MAX:
+        raise _lib.WitwError('retrieve: k=%d outside [1,%d] (the longest candidate list, ops.TOPK_MAX)' % (int(k), ops.TOPK_MAX))
     prior = _Prior.of(shift_mask, known_shift, surface_all)
     resolved = _resolve_method('retrieve', method, prior)
     gallery = overhead_shard.contiguous()

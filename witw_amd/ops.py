@@ -836,19 +836,65 @@ def rank_count(distance, true_offset=0):
     return ranks
 
 
+TOPK_LIST = 32       # places per launch of the top-k kernels: the sorted list a thread keeps in registers
+TOPK_MAX = 1024      # longest list topk_smallest returns
+
+
+def _topk_slices(k, first, resume, out_v, out_i, bound_v, bound_i):
+    """Fill out_v / out_i [Bs,k] in slices of at most TOPK_LIST places. first(n) -> (values, indices) [Bs,n]: places 1..n;
+    resume(n, bound_v, bound_i) -> the n places strictly behind the bound (bound_v f32 [Bs], bound_i int64 [Bs]) in the order
+    (distance, index), which is total: places 33..64 are the 32 smallest behind place 32, and so on. Every bound is the slice
+    before's last column, copied on the device -- nothing is read back between slices. A bound that is a missing candidate
+    (+inf, -1) has nothing behind it, so the places beyond the rows present come out missing too."""
+    for j in range(0, k, TOPK_LIST):
+        n = min(TOPK_LIST, k - j)
+        if j:
+            bound_v.copy_(out_v[:, j - 1])
+            bound_i.copy_(out_i[:, j - 1])
+        v, i = resume(n, bound_v, bound_i) if j else first(n)
+        out_v[:, j:j + n] = v
+        out_i[:, j:j + n] = i
+    return out_v, out_i
+
+
 def topk_smallest(distance, k, row_offset=0):
     """Per query column of D [Bo,Bs]: the k smallest distances and their gallery rows, (distance, index) ascending.
-    -> (values f32 [Bs,k], indices int64 [Bs,k])."""
+    -> (values f32 [Bs,k], indices int64 [Bs,k]). 1 <= k <= TOPK_MAX (1024); places beyond the Bo rows present are missing
+    candidates (+inf, -1). Up to TOPK_LIST (32) places are one run of the kernels; a longer list is ceil(k / 32) runs, each
+    resuming the exact scan behind the last place of the run before (witw_topk_smallest_after), so its first 32 places are the
+    k = 32 list bit for bit."""
     lib = _lib.load()
     d = _dev_f32(distance, 'distance')
     Bo, Bs = d.shape
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise _lib.WitwError('topk_smallest: k=%d outside [1,%d]' % (k, TOPK_MAX))
     vals = torch.empty((Bs, k), dtype=torch.float32, device=d.device)
     idx = torch.empty((Bs, k), dtype=torch.int64, device=d.device)
-    nws = lib.witw_topk_workspace_bytes(Bo, Bs, int(k))
+    nws = lib.witw_topk_workspace_bytes(Bo, Bs, min(k, TOPK_LIST))
     ws = torch.empty((nws,), dtype=torch.uint8, device=d.device) if nws > 0 else None      # long galleries: rows split over workgroups
-    _lib.check(lib.witw_topk_smallest_ws(d.data_ptr(), vals.data_ptr(), idx.data_ptr(), Bo, Bs, int(k), int(row_offset), _p(ws),
-                                         _stream()), 'witw_topk_smallest_ws')
-    return vals, idx
+    if k <= TOPK_LIST:
+        _lib.check(lib.witw_topk_smallest_ws(d.data_ptr(), vals.data_ptr(), idx.data_ptr(), Bo, Bs, k, int(row_offset), _p(ws),
+                                             _stream()), 'witw_topk_smallest_ws')
+        return vals, idx
+
+    def first(n):
+        v = torch.empty((Bs, n), dtype=torch.float32, device=d.device)
+        i = torch.empty((Bs, n), dtype=torch.int64, device=d.device)
+        _lib.check(lib.witw_topk_smallest_ws(d.data_ptr(), v.data_ptr(), i.data_ptr(), Bo, Bs, n, int(row_offset), _p(ws), _stream()),
+                   'witw_topk_smallest_ws')
+        return v, i
+
+    def resume(n, bound_v, bound_i):
+        v = torch.empty((Bs, n), dtype=torch.float32, device=d.device)
+        i = torch.empty((Bs, n), dtype=torch.int64, device=d.device)
+        _lib.check(lib.witw_topk_smallest_after(d.data_ptr(), v.data_ptr(), i.data_ptr(), Bo, Bs, n, int(row_offset),
+                                                bound_v.data_ptr(), bound_i.data_ptr(), _p(ws), _stream()), 'witw_topk_smallest_after')
+        return v, i
+
+    bound_v = torch.empty((Bs,), dtype=torch.float32, device=d.device)
+    bound_i = torch.empty((Bs,), dtype=torch.int64, device=d.device)
+    return _topk_slices(k, first, resume, vals, idx, bound_v, bound_i)
 
 
 def rank_count_thresh(distance, threshold):
