@@ -126,7 +126,20 @@ int witw_maxpool2x2_bwd(const float* dy, const unsigned char* pool_code, float* 
 int witw_nchw_to_nhwc(const float* x, float* y, int B, int C, int H, int W, int Cpad, void* stream);
 /* Weight / bias gradient of one conv layer. x: the layer's NHWC input [B,H,W,Cin], dz: gradient at its output
  * [B,Ho,W,Cout] NHWC (ReLU / dropout gates already applied). dw: torch layout [Cout][cin_real][3][3];
- * db: [Cout] or NULL; accumulate != 0 adds into dw/db. workspace: witw_conv3x3_wgrad_workspace_floats(). */
+ * db: [Cout] or NULL; accumulate != 0 adds into dw/db. workspace: witw_conv3x3_wgrad_workspace_floats().
+ *
+ * Contract of every weight-gradient entry (witw_conv3x3_wgrad, _wgrad_taps4, _wgrad_bf16, _wgrad_bf16_nhwc, _wgrad_f16x3), as
+ * tested by tests/test_wgrad_edges_gpu.py:
+ *   accumulate: with accumulate != 0 each element of dw [Cout][cin_real][3][3] and of db (when not NULL) becomes
+ *     old value + (the value accumulate == 0 would have stored): ONE fp32 add per element, bit for bit, no other arithmetic on
+ *     the old value. Under _wgrad_taps4 the five taps outside {1,2}^2 are not touched at all (accumulate == 0 sets them to +0).
+ *     Nothing outside dw's cin_real channels and db's Cout elements is written in either mode.
+ *   workspace: its contents on entry are irrelevant (NaN included): every partial the reduction reads has been stored by the
+ *     same call, also for K splits whose chunk range is empty. It needs the size of the matching *_workspace_floats() at the
+ *     same arguments (and, for _wgrad_bf16_nhwc, the same witw_conv3x3_wgrad_bf16_mfma16 setting) and is scratch afterwards.
+ *   refusals: a call that returns an error (Cin / Cout not a multiple of 4 -- 8 for the bf16 and fp16x3 entries --, cin_real
+ *     outside (0, Cin], stride_h not 1 or 2, the f16x3 bias gradient at a Cout whose eighth does not divide 256) has launched
+ *     nothing and written nothing. */
 int witw_conv3x3_wgrad_splits(int B, int Ho, int Wo, int Cin, int Cout);
 long long witw_conv3x3_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout, int stride_h);
 int witw_conv3x3_wgrad(const float* x, const float* dz, float* dw, float* db, float* workspace, int B, int H, int W, int Cin,
