@@ -304,11 +304,15 @@ def test_space_to_depth_quad_form_equals_the_scalar_form(case):
 
 
 @pytest.mark.parametrize('case', [(3, 10, 12, (9, 11), 64, False), (2, 8, 8, (7, 7), 128, True), (2, 6, 10, (6, 9), 6, False),
-                                  (4, 64, 64, (61, 61), 64, True)])
+                                  (4, 64, 64, (61, 61), 64, True),
+                                  (2, 6, 10, (6, 9), 12, False), (2, 6, 10, (6, 9), 12, True),        # C = 12, 20: the scalar sums
+                                  (2, 6, 10, (5, 10), 20, False), (2, 6, 10, (5, 10), 20, True),      # (C/4 does not divide 256), quad apply
+                                  (5, 300, 3, (300, 3), 8, False), (5, 300, 3, (300, 3), 8, True)])   # 1,500 rows: two rows per block
 def test_bn_lrelu_backward_against_autograd(case):
     """witw_bn_lrelu_bwd(_ex) (channel-quad form for C % 4 == 0, scalar otherwise; gradient in place or in the space-to-depth
     layout of the next block's data-gradient conv) against torch autograd through BatchNorm2d(train)(LeakyReLU(z)) in float64
-    over the valid region (model/cvig_baseline.py:267-275)."""
+    over the valid region (model/cvig_baseline.py:267-275). The sums take the row kernel when C / 4 divides 256 and the scalar
+    one otherwise, whichever apply kernel follows."""
     import torch
     from witw_amd import ops
     B, Hp, Wp, (H, W), C, s2d = case

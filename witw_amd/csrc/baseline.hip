@@ -188,11 +188,22 @@ __global__ __launch_bounds__(256) void pairwise_sqdist_kernel(const float* __res
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= Nb) return;
     const float* br = bm + (size_t)j * n;
-    float s = 0.f;
-    for (int k = 0; k < n; ++k) {
-        const float d = br[k] - arow[k];
-        s += d * d;
+    // four running sums (k mod 4), added pairwise at the end: one running sum over n = 1536 squares drifts 16x further from the
+    // exact sum than torch's blocked sum does (its rounding grows with sqrt(n) x the sum so far), and is one dependent chain
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int k = 0;
+    for (; k + 3 < n; k += 4) {
+        const float d0 = br[k] - arow[k], d1 = br[k + 1] - arow[k + 1], d2 = br[k + 2] - arow[k + 2], d3 = br[k + 3] - arow[k + 3];
+        s0 += d0 * d0;
+        s1 += d1 * d1;
+        s2 += d2 * d2;
+        s3 += d3 * d3;
     }
+    for (; k < n; ++k) {
+        const float d = br[k] - arow[k];
+        s0 += d * d;
+    }
+    const float s = (s0 + s1) + (s2 + s3);
     D[(size_t)i * Nb + j] = take_sqrt ? sqrtf(s) : s;
 }
 
@@ -236,8 +247,11 @@ __global__ __launch_bounds__(256) void sum_finish_kernel(const float* __restrict
 // Training-mode pieces (model/cvig_baseline.py:267-284 under .train(), autograd of :286-315): batch statistics of
 // BatchNorm2d, its backward fused with the LeakyReLU backward, GeM / normalisation / loss backward, depth-to-space.
 
-// per-channel partial sums over the valid region: part[blk][0][c] = sum a, part[blk][1][c] = sum a^2
-// (bwd form: a2 != nullptr -> sum g and sum g*xhat with xhat = (a - mean[c]) * invstd[c], g = second tensor)
+// per-channel partial sums over the valid region: part[blk][0][c] = sum (a - p), part[blk][1][c] = sum (a - p)^2 about the pivot
+// p[c] = a[0,0,0,c], the channel's first valid value: mean = p + s0/n and var = s1/n - (s0/n)^2 then subtract numbers of the size
+// of the spread, not of the mean (plain sums of a and a^2 lose r^2 x 6e-8 of the variance at |mean| = r x std: 4e-4 of invstd at
+// r = 64, and block 7 of a training step, 3 values per channel, reaches r = 14).
+// (bwd form: g != nullptr -> sum g and sum g*xhat with xhat = (a - mean[c]) * invstd[c], g = second tensor)
 __global__ __launch_bounds__(256) void channel_sums_kernel(const float* __restrict__ a, const float* __restrict__ g,
                                                             const float* __restrict__ mean, const float* __restrict__ invstd,
                                                             float* __restrict__ part, int Hp, int Wp, int H, int W, int C,
@@ -248,6 +262,7 @@ __global__ __launch_bounds__(256) void channel_sums_kernel(const float* __restri
     float s0 = 0.f, s1 = 0.f;
     if (c < C) {
         const float mu = g ? mean[c] : 0.f, is = g ? invstd[c] : 0.f;
+        const float pv = g ? 0.f : a[c];
         for (size_t px = p0 + ph; px < p1; px += 4) {      // px enumerates VALID pixels (b, h<H, w<W)
             const size_t w = px % W, t = px / W, h = t % H, b = t / H;
             const size_t off = ((b * Hp + h) * Wp + w) * C + c;
@@ -259,8 +274,9 @@ __global__ __launch_bounds__(256) void channel_sums_kernel(const float* __restri
                 s0 += gv;
                 s1 += gv * ((v - mu) * is);
             } else {
-                s0 += v;
-                s1 += v * v;
+                const float d = v - pv;
+                s0 += d;
+                s1 += d * d;
             }
         }
     }
@@ -287,9 +303,12 @@ __global__ __launch_bounds__(256) void channel_sums_rows_kernel(const float* __r
     const int r0 = blockIdx.x * rows_per_block, r1 = min(nrows, r0 + rows_per_block);
     f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
     f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = {0.f, 0.f, 0.f, 0.f};
+    f32x4 pv = {0.f, 0.f, 0.f, 0.f};                      // the pivot of the forward form (see channel_sums_kernel)
     if (g) {
         mu = *reinterpret_cast<const f32x4*>(mean + 4 * q);
         is = *reinterpret_cast<const f32x4*>(invstd + 4 * q);
+    } else {
+        pv = *reinterpret_cast<const f32x4*>(a + 4 * q);
     }
     for (int r = r0; r < r1; ++r) {
         const int b = r / H, h = r - b * H;
@@ -302,8 +321,9 @@ __global__ __launch_bounds__(256) void channel_sums_rows_kernel(const float* __r
                 s0 += gv;
                 s1 += gv * ((v - mu) * is);
             } else {
-                s0 += v;
-                s1 += v * v;
+                const f32x4 d = v - pv;
+                s0 += d;
+                s1 += d * d;
             }
         }
     }
@@ -348,16 +368,18 @@ __device__ __forceinline__ bool bn_finish_sums(const float* __restrict__ part, i
 }
 
 // BatchNorm2d training statistics: mean / biased var -> scale = gamma*invstd, shift = beta - mean*scale, and the
-// running-stat update running = (1-m)*running + m*stat (unbiased variance), torch semantics.
-__global__ __launch_bounds__(BNF_CH * BNF_LANES) void bn_stats_finish_kernel(const float* __restrict__ part, int nparts, int C, float n, const float* __restrict__ gamma,
+// running-stat update running = (1-m)*running + m*stat (unbiased variance), torch semantics. The sums are about pivot[c].
+__global__ __launch_bounds__(BNF_CH * BNF_LANES) void bn_stats_finish_kernel(const float* __restrict__ part, int nparts, int C, float n, const float* __restrict__ pivot,
+                                       const float* __restrict__ gamma,
                                        const float* __restrict__ beta, float eps, float momentum, float* __restrict__ mean,
                                        float* __restrict__ invstd, float* __restrict__ scale, float* __restrict__ shift,
                                        float* __restrict__ running_mean, float* __restrict__ running_var) {
     int c;
     float s0, s1;
     if (!bn_finish_sums(part, nparts, C, c, s0, s1)) return;
-    const float mu = s0 / n;
-    const float var = fmaxf(s1 / n - mu * mu, 0.f);
+    const float dm = s0 / n;
+    const float mu = pivot[c] + dm;
+    const float var = fmaxf(s1 / n - dm * dm, 0.f);
     const float is = 1.f / sqrtf(var + eps);
     mean[c] = mu;
     invstd[c] = is;
@@ -719,7 +741,7 @@ int witw_bn_train_stats(const float* a, int B, int Hp, int Wp, int H, int W, int
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)B * H * W;
     const int nparts = bl_launch_sums(a, nullptr, nullptr, nullptr, workspace, B, Hp, Wp, H, W, C, st);
-    hipLaunchKernelGGL(bn_stats_finish_kernel, dim3(cdiv(C, BNF_CH)), dim3(BNF_CH * BNF_LANES), 0, st, workspace, nparts, C, (float)npix, gamma, beta,
+    hipLaunchKernelGGL(bn_stats_finish_kernel, dim3(cdiv(C, BNF_CH)), dim3(BNF_CH * BNF_LANES), 0, st, workspace, nparts, C, (float)npix, a, gamma, beta,
                        eps, momentum, mean, invstd, scale, shift, running_mean, running_var);
     WITW_CHECK_LAUNCH("bn_train_stats");
     return WITW_OK;
