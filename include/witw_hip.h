@@ -483,6 +483,17 @@ int witw_gem_pool(const float* x, float* f, int B, int Hp, int Wp, int H, int W,
 int witw_embed_normalize(float* f, int B, int n, void* stream);
 /* D[i][j] = |a_i - b_j|^2 (or its square root: Euclidean ranking distance of :457-458) */
 int witw_pairwise_sqdist(const float* a, const float* b, float* D, int Na, int Nb, int n, int take_sqrt, void* stream);
+/* Gallery retrieval on [rows, n] embeddings at GEMM cost (witw_amd/cvig_baseline.py: retrieve), 1 <= n <= 12288.
+ * witw_row_sqnorm: out[i] = |x_i|^2, one wave per row.
+ * witw_sqdist_gemm: D[i][j] = max(0, gn[i] + qn[j] - 2 g_i.q_j) (squared, no root) by a tiled fp32 MFMA GEMM; gn / qn = the
+ * witw_row_sqnorm of g / q. Any Ng, Nq >= 1 (Ng is NOT bounded by 65,535). The product form cancels on near pairs: D is within
+ * 3 gamma_(n+16) (max gn + max qn) of the value below (gamma_m = m u / (1 - m u), u = 2^-24), not its bits.
+ * witw_sqdist_pairs: out[p] = the value witw_pairwise_sqdist(g, q, ..., take_sqrt) writes at [pair_g[p]][pair_q[p]], bit for
+ * bit (the same difference-form sum in the same order), one thread per pair; indices must be inside the operands' rows; P may be 0. */
+int witw_row_sqnorm(const float* x, float* out, int N, int n, void* stream);
+int witw_sqdist_gemm(const float* g, const float* q, const float* gn, const float* qn, float* D, int Ng, int Nq, int n, void* stream);
+int witw_sqdist_pairs(const float* g, const float* q, const int* pair_g, const int* pair_q, float* out, int P, int n, int take_sqrt,
+                      void* stream);
 /* exhaustive_minibatch_triplet_loss (:286-315) from D[i][j] = |embed1_i - embed2_j|^2; workspace B floats */
 int witw_exhaustive_triplet_loss(const float* D, int B, int soft_margin, float alpha, float margin, float* loss,
                                  float* workspace, void* stream);

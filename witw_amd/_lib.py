@@ -92,6 +92,9 @@ SIGNATURES = {
     'witw_exhaustive_triplet_loss_bwd': (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_float, c_float, c_void_p, c_void_p]),
     'witw_embed_normalize': (c_int, [c_void_p, c_int, c_int, c_void_p]),
     'witw_pairwise_sqdist': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'witw_row_sqnorm': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'witw_sqdist_gemm': (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
+    'witw_sqdist_pairs': (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     'witw_exhaustive_triplet_loss': (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     'witw_match_bwd_scratch_floats': (c_longlong, [c_int, c_int, c_int]),
     'witw_match_bwd': (c_int, [c_void_p] * 9 + [c_int] * 3 + [c_void_p]),

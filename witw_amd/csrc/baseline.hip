@@ -9,6 +9,7 @@
 // pooling (:276-282), the final f/sqrt(|f|) (:284), squared-Euclidean distance matrix and the
 // exhaustive minibatch triplet loss (:286-315).
 #include "common.h"
+#include "sqdist_row.h"
 
 namespace {
 
@@ -187,23 +188,7 @@ __global__ __launch_bounds__(256) void pairwise_sqdist_kernel(const float* __res
     __syncthreads();
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= Nb) return;
-    const float* br = bm + (size_t)j * n;
-    // four running sums (k mod 4), added pairwise at the end: one running sum over n = 1536 squares drifts 16x further from the
-    // exact sum than torch's blocked sum does (its rounding grows with sqrt(n) x the sum so far), and is one dependent chain
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int k = 0;
-    for (; k + 3 < n; k += 4) {
-        const float d0 = br[k] - arow[k], d1 = br[k + 1] - arow[k + 1], d2 = br[k + 2] - arow[k + 2], d3 = br[k + 3] - arow[k + 3];
-        s0 += d0 * d0;
-        s1 += d1 * d1;
-        s2 += d2 * d2;
-        s3 += d3 * d3;
-    }
-    for (; k < n; ++k) {
-        const float d = br[k] - arow[k];
-        s0 += d * d;
-    }
-    const float s = (s0 + s1) + (s2 + s3);
+    const float s = witw_sqdist_row(arow, bm + (size_t)j * n, n);      // shared with the pair re-scoring of baseline_retrieval.hip
     D[(size_t)i * Nb + j] = take_sqrt ? sqrtf(s) : s;
 }
 

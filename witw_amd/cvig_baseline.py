@@ -384,6 +384,224 @@ def ranks(overhead_embed, surface_embed):
     return ops.rank_count(D, 0).cpu().numpy().astype('int64')
 
 
+# ----------------------------------------------------------------------------- gallery retrieval
+DIRECT_ROWS = 65535      # gallery rows per ops.pairwise_sqdist call (its row index is gridDim.y)
+GEMM_MARGIN = 32         # candidates kept beyond place k by the GEMM pass's top-k: one more slice of ops.topk_smallest
+GEMM_FROM = _fov.SPECTRAL_FROM      # 'auto' is 'gemm' from this many queries on (measured against 'direct')
+
+_RETRIEVE_TLS = __import__('threading').local()
+
+
+def last_retrieve_stats():
+    """Re-scoring statistics of the calling thread's last retrieve(method='gemm'): pairs, rescored_true / _rank / _topk,
+    fallback_queries, eps (retrieve.last_stats is process-wide)."""
+    return dict(getattr(_RETRIEVE_TLS, 'stats', None) or {})
+
+
+def band_eps(n, gn_max, qn_max):
+    """Half-width of the band around a squared threshold inside which a witw_sqdist_gemm value decides nothing. Worst case, not
+    an observation; u = 2^-24, gamma_m = m u / (1 - m u), S = |g|^2 + |q|^2, s = |g - q|^2 <= 2 S:
+      * the dot product, in any summation order:      |fl(g.q) - g.q| <= gamma_n |g||q| <= gamma_n S / 2, doubled: gamma_n S
+      * the two norms, in any order:                  |gn + qn - S| <= gamma_n S
+      * the epilogue's two additions (2 x dot exact): u (gn + qn) + u |result| <= 3 u S (1 + gamma_n)
+        so |D - s| <= (2 gamma_n + 3 u (1 + gamma_n)) S; max(0, .) only moves D towards s >= 0
+      * the exact kernel (difference, square, n/4 - 1 + 2 additions):  |s_x - s| <= gamma_(n/4+5) s <= 2 gamma_(n/4+5) S
+      * the threshold fl(d_true^2), d_true = sqrtf(s_x):               within 3 u (1 + 3 u) of s_x <= 2 S (1 + gamma): 6.1 u S
+      * two squares that sqrtf must not merge or swap (the comparison is on the rooted values, roots on the host may be an ulp
+        off the kernel's):                                            4 u s <= 8 u S
+    in all (2.5 n + 28) u S (1 + O(n u)) with S <= (gn_max + qn_max) / (1 - gamma_n) in the COMPUTED norms; for every n <= 12288
+    that is below 3 gamma_(n+16) (gn_max + qn_max), which leaves the float32 rounding of eps and of the band kernel's own
+    threshold - eps room as well."""
+    m = (n + 16) * 2.0 ** -24
+    return 3.0 * (m / (1.0 - m)) * (float(gn_max) + float(qn_max))
+
+
+def _default_kernels():
+    from types import SimpleNamespace
+    from . import baseline_retrieval as br
+    return SimpleNamespace(pairwise_sqdist=ops.pairwise_sqdist, rank_count_thresh=ops.rank_count_thresh, rank_count_band=ops.rank_count_band,
+                           topk_smallest=ops.topk_smallest, row_sqnorm=br.row_sqnorm, sqdist_gemm=br.sqdist_gemm, sqdist_pairs=br.sqdist_pairs)
+
+
+def _direct_kernels(kn):
+    """the op set cvig_fov._direct_pass runs on: its `match` is ops.pairwise_sqdist(take_sqrt=True) over blocks of at most
+    DIRECT_ROWS gallery rows"""
+    from types import SimpleNamespace
+
+    def match_fwd(gallery, queries, **_kw):
+        blocks = [kn.pairwise_sqdist(gallery[r0:r0 + DIRECT_ROWS], queries, take_sqrt=True) for r0 in range(0, gallery.shape[0], DIRECT_ROWS)]
+        return None, (blocks[0] if len(blocks) == 1 else torch.cat(blocks))
+    return SimpleNamespace(match_fwd=match_fwd, rank_count_thresh=kn.rank_count_thresh, topk_smallest=kn.topk_smallest)
+
+
+def _direct(kn, gallery, surface_all, shard_begin, query_chunk, k, want_ranks):
+    return _fov._direct_pass(_direct_kernels(kn), gallery, surface_all, _fov._NO_PRIOR, shard_begin, query_chunk, k, want_ranks)
+
+
+def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='gemm', _kernels=None):
+    """The k nearest gallery rows of every query by Euclidean distance, ordered by (distance, gallery index): -> (distances f32
+    [N,k], gallery indices int64 [N,k]) on the device, identical on every rank; see retrieve()."""
+    return retrieve(overhead_shard, surface_all, k, shard_begin, query_chunk, method, _kernels, _want_ranks=False)[1:]
+
+
+def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='gemm', _kernels=None, _want_ranks=True,
+             _want_lists=True):
+    """Ranks and top-k lists of cvig_baseline embeddings from ONE distance pass per query chunk, name for name what
+    cvig_fov.retrieve is for the orientation search: this rank holds overhead_shard = gallery rows [shard_begin, shard_begin + n)
+    (any number per rank, including none), surface_all [N, E] is replicated, query q's true row is gallery row q.
+    -> (ranks int64 [N] on the host = #{rows : d <= d_true}, distances f32 [N,k], gallery indices int64 [N,k] on the device,
+    ordered by (distance, index)), identical on every rank. Distances are Euclidean, as ranks() returns them. 1 <= k <=
+    ops.TOPK_MAX; places beyond the rows present are (+inf, -1).
+    method='direct': ops.pairwise_sqdist (the difference form) over gallery blocks of at most DIRECT_ROWS rows feeding
+    ops.rank_count_thresh / ops.topk_smallest; the shards' lists are merged by cvig_fov._merge_topk.
+    method='gemm': |g|^2 + |q|^2 - 2 g.q on the fp32 MFMA (witw_sqdist_gemm), known to band_eps only; every decision inside that
+    band is re-made on witw_sqdist_pairs, whose values are the direct kernel's bit for bit: rows within eps of d_true^2 are
+    re-scored and compared as rooted values; ALL k + GEMM_MARGIN candidates per shard and query are re-scored and ordered
+    exactly, and a query whose exact k-th distance is not strictly below sqrt(best squared distance outside the lists - eps)
+    takes the direct pass. Ranks, indices AND listed distances equal method='direct' exactly. Lists of more than TOPK_MAX -
+    GEMM_MARGIN places come from the direct pass, the ranks still from the GEMM pass.
+    method='auto': 'gemm' from GEMM_FROM queries on. `_kernels` swaps the op set (CPU tests of the host pass)."""
+    kn = _kernels or _default_kernels()
+    if not 1 <= int(k) <= ops.TOPK_MAX:
+        raise _lib.WitwError('retrieve: k=%d outside [1,%d] (the longest candidate list, ops.TOPK_MAX)' % (int(k), ops.TOPK_MAX))
+    if method not in ('auto', 'direct', 'gemm'):
+        raise _lib.WitwError("retrieve: method must be 'auto', 'direct' or 'gemm', got %r" % (method,))
+    if overhead_shard.dim() != 2 or surface_all.dim() != 2 or overhead_shard.shape[1] != surface_all.shape[1]:
+        raise _lib.WitwError('retrieve: need [rows, E] embeddings of one width, got %s and %s' % (tuple(overhead_shard.shape), tuple(surface_all.shape)))
+    k = int(k)
+    if method == 'auto':
+        method = 'gemm' if surface_all.shape[0] >= GEMM_FROM else 'direct'
+    gallery, surface_all = overhead_shard.contiguous(), surface_all.contiguous()
+    ranks_out = v = i = None
+    if method == 'gemm':
+        lists = _want_lists and k + GEMM_MARGIN <= ops.TOPK_MAX
+        done = _retrieve_gemm(kn, gallery, surface_all, k if lists else None, shard_begin, query_chunk, _want_ranks)
+        if done is not None:
+            ranks_out, v, i = done
+            _want_ranks = False
+            _want_lists = _want_lists and not lists
+        # else: norms that are not finite admit no band -- the whole call is the direct pass
+    if _want_ranks or _want_lists:
+        counts, dv, di = _direct(kn, gallery, surface_all, shard_begin, query_chunk, k if _want_lists else None, _want_ranks)
+        if _want_ranks:
+            ranks_out = counts.cpu().numpy().astype('int64')
+        if _want_lists:
+            v, i = dv, di
+    return ranks_out, v, i
+
+
+def _retrieve_gemm(kn, gallery, surface_all, k, shard_begin, query_chunk, want_ranks):
+    """retrieve() on the GEMM pass (see there). k None: no lists. -> (ranks or None, values, indices), or None when some norm is
+    not finite (decided on all-reduced data: the same on every rank)."""
+    import math
+    import torch.distributed as dist_
+    from . import parallel
+    dev = surface_all.device
+    n_q, n_g, n = surface_all.shape[0], gallery.shape[0], surface_all.shape[1]
+    if not want_ranks and k is None:
+        return None, None, None
+    gn = kn.row_sqnorm(gallery) if n_g else None
+    qn_all = kn.row_sqnorm(surface_all) if n_q else torch.zeros((0,), dtype=torch.float32, device=dev)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    worst = torch.stack((gn.max() if n_g else zero, qn_all.max() if n_q else zero))
+    if parallel.world() > 1:
+        dist_.all_reduce(worst, op=dist_.ReduceOp.MAX)
+    worst = worst.tolist()
+    eps = getattr(kn, 'BAND_EPS', None)                  # an injected op set states the error of its own GEMM form
+    eps = band_eps(n, worst[0], worst[1]) if eps is None else float(eps)
+    if not (math.isfinite(worst[0]) and math.isfinite(worst[1]) and math.isfinite(eps)):
+        return None
+    kc = None if k is None else k + GEMM_MARGIN
+    stats = {'method': 'gemm', 'pairs': float(n_g) * n_q, 'rescored_true': 0, 'rescored_rank': 0, 'rescored_topk': 0, 'fallback_queries': 0,
+             'eps': eps}
+    counts = torch.zeros((n_q,), dtype=torch.int32, device=dev)
+    vals, idxs = [], []
+    for q0 in range(0, n_q, query_chunk):
+        q1 = min(n_q, q0 + query_chunk)
+        nq = q1 - q0
+        su = surface_all[q0:q1]
+        D = kn.sqdist_gemm(gallery, su, gn, qn_all[q0:q1]) if n_g else None          # [n_g, nq], squared
+        if want_ranks:
+            lo, hi = max(q0, shard_begin), min(q1, shard_begin + n_g)         # the queries whose true row lives in this shard
+            d_true = torch.zeros((nq,), dtype=torch.float32, device=dev)
+            if hi > lo:                                                       # the owner's EXACT distance of every true pair
+                pg = torch.arange(lo - shard_begin, hi - shard_begin, dtype=torch.int32, device=dev)
+                pq = torch.arange(lo - q0, hi - q0, dtype=torch.int32, device=dev)
+                d_true[lo - q0:hi - q0] = kn.sqdist_pairs(gallery, su, pg, pq, take_sqrt=True)
+                stats['rescored_true'] += hi - lo
+            parallel.all_reduce_sum_(d_true)
+            if n_g:
+                c, pg, pq = kn.rank_count_band(D, (d_true * d_true).contiguous(), eps)
+                if pg.numel():        # compared as ranks() compares: on the rooted exact values (sqrtf can merge neighbouring squares)
+                    d_x = kn.sqdist_pairs(gallery, su, pg, pq, take_sqrt=True)
+                    c.index_add_(0, pq.long(), (d_x <= d_true[pq.long()]).to(torch.int32))
+                    stats['rescored_rank'] += int(pg.numel())
+                counts[q0:q1] = c
+        if kc is not None:
+            cv, ci = kn.topk_smallest(D, kc, shard_begin) if n_g else _fov._empty_topk(nq, kc, dev)
+            vals.append(cv)
+            idxs.append(ci)
+    ranks_out = v = i = None
+    if want_ranks:
+        parallel.all_reduce_sum_(counts)
+        ranks_out = counts.cpu().numpy().astype('int64')
+    if kc is not None:
+        if n_q:
+            v, i = _settle_lists(kn, gallery, surface_all, k, kc, shard_begin, query_chunk, eps, torch.cat(vals), torch.cat(idxs), stats)
+        else:
+            v, i = _fov._empty_topk(0, k, dev)
+    retrieve.last_stats = stats
+    _RETRIEVE_TLS.stats = stats
+    return ranks_out, v, i
+
+
+def _settle_lists(kn, gallery, surface_all, k, kc, shard_begin, query_chunk, eps, v, i, stats):
+    """The shards' candidate lists (v, i: [N, kc] by GEMM-form squared distance) -> the first k places as the direct pass lists
+    them. Every gathered candidate is re-scored exactly (N kc pairs per shard: nothing next to the pass) and ordered by (exact
+    distance, index). No row outside the lists has a GEMM-form value below `outsider`, the smallest last place of a full list, so
+    its exact squared distance is >= outsider - eps and its rooted one >= sqrt(outsider - eps): a query whose exact k-th distance is
+    strictly below that is settled, any other takes the direct pass."""
+    from . import parallel
+    dev = surface_all.device
+    n_q, n_g = surface_all.shape[0], gallery.shape[0]
+    w = parallel.world()
+    outsider = v[:, kc - 1].clone()                      # +inf where the shard has fewer than kc rows: nothing outside its list
+    if w > 1:
+        i = parallel._all_gather_cat(i.unsqueeze(0)).permute(1, 0, 2).reshape(n_q, w * kc)
+        outsider = parallel._all_gather_cat(outsider.unsqueeze(0)).min(dim=0).values
+    mine = (i >= shard_begin) & (i < shard_begin + n_g)
+    exact = torch.zeros(i.shape, dtype=torch.float32, device=dev)
+    if n_g and bool(mine.any()):
+        pg = (i - shard_begin)[mine].to(torch.int32).contiguous()
+        pq = torch.arange(n_q, device=dev)[:, None].expand_as(i)[mine].to(torch.int32).contiguous()
+        exact[mine] = kn.sqdist_pairs(gallery, surface_all, pg, pq, take_sqrt=True)
+        stats['rescored_topk'] += int(pg.numel())
+    parallel.all_reduce_sum_(exact)
+    exact = torch.where(i < 0, torch.full_like(exact, float('inf')), exact)
+    ev, ei = _fov._sort_by_value_then_index(exact, i)
+    beyond = torch.sqrt((outsider - eps).clamp(min=0))
+    safe = (ev[:, min(k, ev.shape[1]) - 1] < beyond) | torch.isinf(outsider)
+    ev, ei = ev[:, :k].contiguous(), ei[:, :k].contiguous()
+    fallback = torch.nonzero(~safe).squeeze(1)           # identical on every rank: computed from gathered data
+    if fallback.numel():     # more near-ties than candidates kept: those queries take the direct pass
+        stats['fallback_queries'] = int(fallback.numel())
+        _counts, fv, fi = _direct(kn, gallery, surface_all[fallback].contiguous(), shard_begin, query_chunk, k, False)
+        ev[fallback], ei[fallback] = fv, fi
+    return ev, ei
+
+
+def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, method='auto'):
+    """The ranks test() tabulates, int64 [N] on the host, identical on every rank. `overhead_embed` / `surface_embed` are THIS
+    rank's rows (world > 1: the queries are gathered, the gallery rows stay sharded from shard_begin on). method: 'direct',
+    'gemm' (the same ranks, see retrieve) or 'auto' = 'gemm' from GEMM_FROM queries on. Unlike ranks() neither is bounded by
+    65,535 gallery rows."""
+    from . import parallel
+    if method not in ('auto', 'direct', 'gemm'):         # refused before the gather
+        raise _lib.WitwError("evaluation_ranks: method must be 'auto', 'direct' or 'gemm', got %r" % (method,))
+    surface_all = parallel.all_gather_ragged(surface_embed) if world > 1 else surface_embed
+    return retrieve(overhead_embed, surface_all, k=1, shard_begin=shard_begin, method=method, _want_lists=False)[0]
+
+
 # ----------------------------------------------------------------------------- drivers
 def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_epochs=999999, csv_path=None):
     """model/cvig_baseline.py:318-404 on the HIP kernels: same flow, prints and checkpoint names; Adam with torch's
@@ -438,9 +656,11 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
     return best_loss
 
 
-def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None):
+def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_method=None):
     """model/cvig_baseline.py:405-475: embed the test set (SyncedRotation stays on, as in the reference :410-414),
-    rank every query against the whole gallery on the GPU, print the recall table."""
+    rank every query against the whole gallery on the GPU, print the recall table. match_method: None = ranks() (one dense
+    matrix, at most 65,535 pairs); 'direct', 'gemm' or 'auto' = evaluation_ranks(method=...): the same ranks from the chunked
+    pass, 'gemm' at GEMM cost with exact re-scoring (retrieve)."""
     csv_path = csv_path or Globals.dataset_paths[dataset]['test']
     prep = GpuPreprocess(dataset)
     test_set = ImagePairDataset(dataset=dataset, csv_path=csv_path)
@@ -458,7 +678,8 @@ def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None):
         with torch.no_grad():
             su_parts.append(surface_encoder(data['surface']))
             ov_parts.append(overhead_encoder(data['overhead']))
-    rk = ranks(torch.cat(ov_parts, dim=0), torch.cat(su_parts, dim=0))
+    ov_all, su_all = torch.cat(ov_parts, dim=0), torch.cat(su_parts, dim=0)
+    rk = ranks(ov_all, su_all) if match_method is None else evaluation_ranks(ov_all, su_all, method=match_method)
     t = recall_table(rk)
     print('Top  1: {:.2f}%'.format(t['top_1']))
     print('Top  5: {:.2f}%'.format(t['top_5']))
@@ -476,11 +697,15 @@ def main(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('--mode', default='train', choices=['train', 'test'], help='Run mode. [Default = train]')
     parser.add_argument('--dataset', default='cvusa', choices=['cvusa', 'witw'], help='Dataset to use. [Default = cvusa]')
+    parser.add_argument('--match-method', default=None, choices=['direct', 'gemm', 'auto'],
+                        help="Test mode: rank through evaluation_ranks -- 'direct' = the chunked difference-form pass, 'gemm' = the fp32 MFMA "
+                             "distance GEMM with exact re-scoring (the same ranks), 'auto' = 'gemm' for large test sets. [Default = one dense "
+                             "matrix, at most 65,535 pairs]")
     args = parser.parse_args(argv)
     if args.mode == 'train':
         train(dataset=args.dataset)
     elif args.mode == 'test':
-        test(dataset=args.dataset)
+        test(dataset=args.dataset, match_method=args.match_method)
 
 
 if __name__ == '__main__':
