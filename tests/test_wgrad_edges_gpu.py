@@ -18,6 +18,10 @@ bf16 operands are bf16-exact fp32 values (exact products, so again only the summ
 each operand as fp16 hi + fp16 lo (22 significant bits) and drops the lo * lo product; measured on its own, its three cases need
 no room for that: the worst is 1.36 ulp of the scale at a ratio of 1.36, so it is held to the same bound as the others.
 
+The parity bounds cannot see a change of summation ORDER in the split-K reduction (they sit 4 x above another order), so
+test_reduction_is_the_stated_fp32_order pins it: it reads the partials a launch left in the caller's workspace, adds them on the
+CPU in the documented order (csrc/wgrad_common.h) with one fp32 tensor add per partial, and demands the bits of dw and db.
+
 Measured on the MI355X (profiles/wgrad_edges.json, written by tools/wgrad_edge_ratios.py from these cases): see DESIGN.md section 4.3.
 """
 import collections
@@ -76,7 +80,8 @@ def chunks_of(c):
 
 
 def splits_of(c, cu_count=256):
-    """witw_conv3x3_wgrad_splits, wgrad_bf16_splits, wgrad_nh_splits, wgrad_hx_splits"""
+    """wgrad_splits (csrc/wgrad_common.h) on each entry's WgradTiling: witw_conv3x3_wgrad_splits / WG_F32, wgrad_bf16_tiling,
+    wgrad_nh_tiling, WG_HX"""
     if c.entry in ('f32', 'taps4'):
         want = cdiv(1024, cdiv(c.Cin, 64) * cdiv(c.Cout, 64))
     elif c.entry == 'bf16_octet':
@@ -298,6 +303,69 @@ def test_accumulate_is_one_fp32_add(c):
     if c.entry == 'taps4':
         for t in (a_w, aa_w, n_w):
             assert same_bits(t[:, :, 0, :], G0[:, :, 0, :]) and same_bits(t[:, :, :, 0], G0[:, :, :, 0])
+
+
+def _order_cases():
+    """existing cases whose workspace is re-reduced on the CPU: both fp32 reduce kernels at their threshold, empty splits, padded
+    input channels, both forms of the 2x2 sub-window, and every case of the 16-bit entries that runs on 32x32x16 (plus the
+    16x16x32 case with empty splits)"""
+    f32 = [c for c in F32 if c.entry == 'f32']
+    picked = [c for c in f32 if c.splits in (31, 32) or (c.B, c.H, c.W, c.Cin, c.Cout) == (3, 100, 12, 128, 128)]
+    picked += [c for c in f32 if c.cin_real < c.Cin][:1]
+    picked += TAPS4_ACC
+    picked += [c for c in LOW if not c.mfma16 or c.empty == 14]
+    return picked
+
+
+def _fp32_sum(parts, wide):
+    """parts [k][...] fp32 on the CPU -> their sum in the kernels' order, one elementwise fp32 add per partial.
+    serial (wgrad_reduce_kernel): ((0 + p[0]) + p[1]) + ...; wide (wgrad_reduce_wide_kernel): eight group sums over
+    k = g, g + 8, ..., each serial from zero, then group 0's sum + group 1's + ... + group 7's"""
+    def serial(seq):
+        s = torch.zeros_like(parts[0])
+        for p in seq:
+            s = s + p
+        return s
+    if not wide:
+        return serial(parts)
+    groups = [serial(parts[g::8]) for g in range(8)]
+    s = groups[0]
+    for g in range(1, 8):
+        s = s + groups[g]
+    return s
+
+
+@pytest.mark.parametrize('c', _order_cases(), ids=case_id)
+def test_reduction_is_the_stated_fp32_order(c):
+    """dw and db are, bit for bit, the partials the launch left in the workspace added in the documented order: serial from
+    zero everywhere, except the fp32 entries at >= 32 splits (eight interleaved group sums, then the groups in order).
+    Workspace: weight partials [parts][taps][Cin][Cout], bias partials [bparts][Cout] at float offset parts * 9 * Cin * Cout."""
+    from witw_amd import _lib
+    ref = reference(c)
+    arena = Arena('cuda:0')
+    with kernel_form(c):
+        check_premise(c)
+        rc, dw, db, ws = A.call(c.entry, A.operands(c.entry, ref['x'], ref['dz']), dims(c), c.cin_real, c.circ, arena)
+    _lib.check(rc, 'wgrad entry %r' % c.entry)
+    arena.check((dw, db))
+    ws, dw, db = ws.cpu(), dw.cpu(), db.cpu()
+    taps = 4 if c.entry == 'taps4' else 9
+    parts = 2 * c.splits if c.entry == 'f16x3' else c.splits
+    bparts = A.f16x3_bias_parts(c.B, c.H, c.W, c.sh) if c.entry == 'f16x3' else c.splits
+    wide = c.entry in ('f32', 'taps4') and c.splits >= 32
+    n, b0 = taps * c.Cin * c.Cout, parts * 9 * c.Cin * c.Cout
+    assert ws.numel() == b0 + bparts * c.Cout
+    s_w = _fp32_sum(ws[:parts * n].view(parts, taps, c.Cin, c.Cout), wide)[:, :c.cin_real]      # [taps][cin_real][Cout]
+    s_b = _fp32_sum(ws[b0:].view(bparts, c.Cout), wide)
+    if taps == 9:
+        want = s_w.view(3, 3, c.cin_real, c.Cout).permute(3, 2, 0, 1)
+    else:
+        want = torch.zeros((c.Cout, c.cin_real, 3, 3))
+        for t in range(4):
+            want[:, :, 1 + (t >> 1), 1 + (t & 1)] = s_w[t].t()
+    assert bool(torch.isfinite(want).all()) and bool(torch.isfinite(s_b).all()), 'a partial was left unwritten'
+    assert same_bits(dw, want.contiguous()), 'dw: %d element(s) differ' % int((bits(dw) != bits(want)).sum())
+    assert same_bits(db, s_b), 'db: %d element(s) differ' % int((bits(db) != bits(s_b)).sum())
 
 
 REFUSALS = [  # entry, (B, H, W, Cin, Cout, stride_h), cin_real, what

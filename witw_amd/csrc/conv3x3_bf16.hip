@@ -14,6 +14,7 @@
 //     the last layer writes the fp32 NCHW embedding.
 #include "common.h"
 #include "conv_launch.h"
+#include "layout16.h"
 #include "lds_frag.h"
 
 namespace {
@@ -834,34 +835,6 @@ __global__ void nchw_f32_to_nhwc_bf16_kernel(const float* __restrict__ x, __bf16
     *reinterpret_cast<bf16x8*>(y + (b * hw + r) * Cp + (size_t)g * 8) = v;
 }
 
-// Backward of the fused MaxPool2d(2,2) on bf16 NHWC tensors: dy [B,Hp,Wp,C] is routed to the position the forward
-// recorded (code = dy*2+dx); dx [B,H,W,C], H >= 2Hp, W >= 2Wp (a dropped odd row / column keeps its memset zeros).
-// One thread per pooled pixel and channel octet (16-byte accesses).
-__global__ void maxpool2x2_bwd_bf16_kernel(const unsigned short* __restrict__ dy, const unsigned char* __restrict__ code,
-                                           unsigned short* __restrict__ dx, int Hp, int Wp, int H, int W, int C, size_t total) {
-    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-    typedef unsigned char u8x8 __attribute__((ext_vector_type(8)));
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int C8 = C >> 3;
-    const int c8 = idx % C8;
-    size_t t = idx / C8;
-    const int w = t % Wp;
-    t /= Wp;
-    const int h = t % Hp;
-    const size_t b = t / Hp;
-    const size_t src = (((b * Hp + h) * Wp + w) * C) + (size_t)c8 * 8;
-    const u16x8 g = *reinterpret_cast<const u16x8*>(dy + src);
-    const u8x8 k = *reinterpret_cast<const u8x8*>(code + src);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        u16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (k[e] == q) ? g[e] : (unsigned short)0;
-        *reinterpret_cast<u16x8*>(dx + ((b * H + 2 * h + (q >> 1)) * W + 2 * w + (q & 1)) * C + (size_t)c8 * 8) = o;
-    }
-}
-
 template <int TN, int SH, bool POOL, int NW>
 int launch_bf_nw(ConvBfArgs a, hipStream_t st) {
     const long long grid = witw_conv_grid(a, NW, TN, "conv3x3_bf16");
@@ -1027,7 +1000,7 @@ int witw_maxpool2x2_bwd_bf16(const void* dy_bf16, const unsigned char* code, voi
         return WITW_ERR_LAUNCH;
     }
     const size_t total = (size_t)B * Hp * Wp * (C / 8);
-    hipLaunchKernelGGL(maxpool2x2_bwd_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(maxpool2x2_bwd16_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                        (const unsigned short*)dy_bf16, code, (unsigned short*)dx_bf16, Hp, Wp, H, W, C, total);
     WITW_CHECK_LAUNCH("maxpool2x2_bwd_bf16");
     return WITW_OK;

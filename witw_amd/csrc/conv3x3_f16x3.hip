@@ -15,6 +15,7 @@
 //   * packed filter per chunk: 9 slots w_hi(tap) + 5 x 2 slots w_lo(tap pair) = 19 slots of TN x 16 B.
 #include "common.h"
 #include "conv_launch.h"
+#include "layout16.h"
 #include "lds_frag.h"
 
 namespace {
@@ -465,40 +466,6 @@ __global__ void split_to_f32_kernel(const unsigned short* __restrict__ x, float*
     y[idx] = (float)xh[o] + (float)xh[o + 8];
 }
 
-// Backward of the fused MaxPool2d(2,2) on split-fp16 tensors: dy [B,Hp,Wp,C/8,2,8] is routed (both planes) to the position
-// the forward recorded (code uint8 [B,Hp,Wp,C]); dx [B,H,W,C/8,2,8], H >= 2Hp, W >= 2Wp (a dropped odd row / column keeps its
-// zeros). One thread per pooled pixel and channel octet.
-__global__ void maxpool2x2_bwd_split_kernel(const unsigned short* __restrict__ dy, const unsigned char* __restrict__ code,
-                                            unsigned short* __restrict__ dx, int Hp, int Wp, int H, int W, int C, size_t total) {
-    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-    typedef unsigned char u8x8 __attribute__((ext_vector_type(8)));
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int C8 = C >> 3;
-    const int c8 = idx % C8;
-    size_t t = idx / C8;
-    const int w = t % Wp;
-    t /= Wp;
-    const int h = t % Hp;
-    const size_t b = t / Hp;
-    const size_t pp = (b * Hp + h) * Wp + w;
-    const u16x8 ghi = *reinterpret_cast<const u16x8*>(dy + ((pp * C8 + c8) * 2) * 8);
-    const u16x8 glo = *reinterpret_cast<const u16x8*>(dy + ((pp * C8 + c8) * 2 + 1) * 8);
-    const u8x8 k = *reinterpret_cast<const u8x8*>(code + pp * C + (size_t)c8 * 8);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        u16x8 ohi, olo;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            ohi[e] = (k[e] == q) ? ghi[e] : (unsigned short)0;
-            olo[e] = (k[e] == q) ? glo[e] : (unsigned short)0;
-        }
-        u16x8* dst = reinterpret_cast<u16x8*>(dx + ((((b * H + 2 * h + (q >> 1)) * W + 2 * w + (q & 1)) * C8 + c8) * 2) * 8);
-        dst[0] = ohi;
-        dst[1] = olo;
-    }
-}
-
 template <int TN, int SH, bool POOL, int NW>
 int launch_hx_nw(ConvHxArgs a, hipStream_t st) {
     const long long grid = witw_conv_grid(a, NW, TN, "conv3x3_f16x3");
@@ -612,7 +579,7 @@ int witw_maxpool2x2_bwd_split(const void* dy_split, const unsigned char* code, v
         return WITW_ERR_LAUNCH;
     }
     const size_t total = (size_t)B * Hp * Wp * (C / 8);
-    hipLaunchKernelGGL(maxpool2x2_bwd_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(maxpool2x2_bwd16_kernel<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                        (const unsigned short*)dy_split, code, (unsigned short*)dx_split, Hp, Wp, H, W, C, total);
     WITW_CHECK_LAUNCH("maxpool2x2_bwd_split");
     return WITW_OK;

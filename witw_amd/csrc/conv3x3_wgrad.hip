@@ -12,8 +12,11 @@
 // loads whose descriptor is built per row from scalars: padded rows get a zero-length
 // descriptor, padded columns an out-of-range offset (both return 0), so there is no per-load
 // VALU work next to the f32 MFMAs. Split-K partials go to a workspace and are summed in a
-// fixed order by the reduce kernel (bitwise reproducible), which also writes torch's KCRS layout.
+// fixed order by the reduce kernels below (bitwise reproducible), which also write torch's KCRS layout:
+// witw_wgrad_reduce, the one reduction of every weight-gradient entry (the bf16 and fp16x3 files call it
+// too). The launch prologue (argument checks, split geometry) is wgrad_common.h's.
 #include "common.h"
+#include "wgrad_common.h"
 
 namespace {
 
@@ -188,10 +191,11 @@ __global__ __launch_bounds__(WT, 2) void conv3x3_wgrad_kernel(WgradArgs p) {
     }
 }
 
-// dW[co][ci][kh][kw] (+)= sum_split ws[split][tap][ci][co]; one thread per (tap, ci, co), co fastest.
-// Threads past the weight elements sum the bias partials: db[co] (+)= sum_split bias_part[split][co].
-__global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Cin, int Cout, int splits,
-                                    int accumulate, int cin_real, int taps, const float* __restrict__ bias_part,
+// dW[co][ci][kh][kw] (+)= sum_k ws[k][tap][ci][co], k < parts; one thread per (tap, ci, co), co fastest.
+// Threads past the weight elements sum the bias partials: db[co] (+)= sum_k bias_part[k][co], k < bias_parts (the fp16x3
+// entry's bias partials come from a pass of their own and are not one per weight partial).
+__global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Cin, int Cout, int parts,
+                                    int bias_parts, int accumulate, int cin_real, int taps, const float* __restrict__ bias_part,
                                     float* __restrict__ db) {
     const size_t n = (size_t)taps * Cin * Cout;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -199,7 +203,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restr
         const size_t co = idx - n;
         if (db != nullptr && co < (size_t)Cout) {
             float s = 0.f;
-            for (int k = 0; k < splits; ++k) s += bias_part[(size_t)k * Cout + co];
+            for (int k = 0; k < bias_parts; ++k) s += bias_part[(size_t)k * Cout + co];
             db[co] = accumulate ? db[co] + s : s;
         }
         return;
@@ -210,7 +214,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restr
     int tap = (int)(t / Cin);
     if (taps == 4) tap = (1 + (tap >> 1)) * 3 + 1 + (tap & 1);      // 2x2 sub-window -> its place in the 3x3 filter
     float s = 0.f;
-    for (int k = 0; k < splits; ++k) s += ws[(size_t)k * n + idx];
+    for (int k = 0; k < parts; ++k) s += ws[(size_t)k * n + idx];
     if (ci >= cin_real) return;   // zero-padded input channels have no weight
     float* d = dw + ((size_t)co * cin_real + ci) * 9 + tap;
     *d = accumulate ? (*d + s) : s;
@@ -219,7 +223,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restr
 // The same sums when there are many splits and few weights (first layers: one 64 x 64 tile, ~1000 splits — one thread per
 // element would walk them serially on a handful of workgroups): a workgroup owns 32 consecutive elements, its 8 groups of
 // 32 lanes each add every 8th split, and the group sums are added in group order. The order is fixed (reproducible), but
-// differs from wgrad_reduce_kernel's; the launcher chooses by `splits` alone.
+// differs from wgrad_reduce_kernel's; witw_wgrad_reduce chooses by the entry's form and `splits` alone.
 constexpr int RW_E = 32, RW_G = 8;
 __global__ __launch_bounds__(RW_E * RW_G) void wgrad_reduce_wide_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Cin,
                                                                          int Cout, int splits, int accumulate, int cin_real, int taps,
@@ -327,22 +331,34 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamTable t, floa
 
 }  // namespace
 
-extern "C" {
-
-// number of K splits the launcher will use and the workspace it needs (floats)
-int witw_conv3x3_wgrad_splits(int B, int Ho, int Wo, int Cin, int Cout) {
-    const int tiles = cdiv(Cin, 64) * cdiv(Cout, 64);
-    const int chunks = B * Ho * cdiv(Wo, 64);
-    int splits = cdiv(1024, tiles);           // aim at ~1024 workgroups (2 per CU x 256 CUs x 2 rounds)
-    if (splits > chunks) splits = chunks;
-    if (splits < 1) splits = 1;
-    return splits;
+// witw_wgrad_reduce (wgrad_common.h)
+int witw_wgrad_reduce(const float* ws, const float* bias_part, float* dw, float* db, int Cin, int cin_real, int Cout, int taps, int parts,
+                      int bias_parts, int accumulate, WgradReduceForm form, void* stream) {
+    const size_t n = (size_t)taps * Cin * Cout;
+    if (form == WGRAD_WIDE_AT_32 && parts >= 32)
+        hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((n + Cout + RW_E - 1) / RW_E)), dim3(RW_E * RW_G), 0,
+                           (hipStream_t)stream, ws, dw, Cin, Cout, parts, accumulate, cin_real, taps, bias_part, db);
+    else
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + Cout + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, dw, Cin,
+                           Cout, parts, bias_parts, accumulate, cin_real, taps, bias_part, db);
+    WITW_CHECK_LAUNCH("wgrad_reduce");
+    return WITW_OK;
 }
 
+// one output row x up to 64 columns of one image per K chunk, 64 x 64 tiles, ~1024 workgroups (2 per CU x 256 CUs x 2 rounds)
+static constexpr WgradTiling WG_F32 = {1024, 64, 64, 1, 64};
+
+extern "C" {
+
+// number of K splits the launcher will use
+int witw_conv3x3_wgrad_splits(int B, int Ho, int Wo, int Cin, int Cout) {
+    return wgrad_splits(WG_F32.target, cdiv(Cin, WG_F32.tile_ci) * cdiv(Cout, WG_F32.tile_co), B * Ho * cdiv(Wo, WG_F32.cols));
+}
+
+// the workspace it needs (floats)
 long long witw_conv3x3_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout, int stride_h) {
-    const int Ho = (H + 2 - 3) / stride_h + 1;
-    const long long splits = witw_conv3x3_wgrad_splits(B, Ho, W, Cin, Cout);
-    return splits * 9 * Cin * Cout + splits * Cout;
+    const WgradGeom g = wgrad_geom(WG_F32, B, 1, H, W, Cin, Cout, stride_h);
+    return wgrad_workspace_floats(g, g.splits, Cout);
 }
 
 // x [B,H,W,Cin] NHWC (the conv's input), dz [B,Ho,W,Cout] NHWC (gradient at its output),
@@ -350,25 +366,22 @@ long long witw_conv3x3_wgrad_workspace_floats(int B, int H, int W, int Cin, int 
 // db [Cout] or NULL. accumulate != 0 adds to dw/db instead of overwriting.
 static int wgrad_launch(const float* x, const float* dz, float* dw, float* db, float* workspace, int B, int H, int W, int Cin,
                         int cin_real, int Cout, int stride_h, int pad_circular, int accumulate, int taps, void* stream) {
-    WITW_CHECK_ARG(x && dz && dw && workspace, "conv3x3_wgrad: null pointer");
-    WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_wgrad: bad shape");
-    WITW_CHECK_ARG((Cin % 4) == 0 && (Cout % 4) == 0, "conv3x3_wgrad: Cin=%d and Cout=%d must be multiples of 4", Cin, Cout);
-    WITW_CHECK_ARG(cin_real > 0 && cin_real <= Cin, "conv3x3_wgrad: cin_real=%d outside (0,%d]", cin_real, Cin);
-    WITW_CHECK_ARG(stride_h == 1 || stride_h == 2, "conv3x3_wgrad: stride_h=%d unsupported", stride_h);
+    WgradGeom g;
+    if (int rc = wgrad_prologue(g, "conv3x3_wgrad", 4, WG_F32, B, 1, x, dz, dw, db, workspace, B, H, W, Cin, cin_real, Cout, stride_h))
+        return rc;
     WITW_CHECK_ARG((size_t)W * Cin * 4 < 0xfffffff0ull && (size_t)W * Cout * 4 < 0xfffffff0ull, "conv3x3_wgrad: row too large");
     hipStream_t st = (hipStream_t)stream;
     WgradArgs a;
     a.x = x; a.dz = dz; a.ws = workspace;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    a.Ho = (H + 2 - 3) / stride_h + 1;
+    a.Ho = g.Ho;
     a.Wo = W;
     a.SH = stride_h; a.circ = pad_circular;
-    a.nseg = cdiv(a.Wo, 64);
-    a.chunks = B * a.Ho * a.nseg;
-    const int splits = witw_conv3x3_wgrad_splits(B, a.Ho, a.Wo, Cin, Cout);
-    a.cps = cdiv(a.chunks, splits);
-    a.bias_part = db ? workspace + (size_t)splits * 9 * Cin * Cout : nullptr;     // behind the weight partials
-    const dim3 grid(cdiv(Cin, 64), cdiv(Cout, 64), splits);
+    a.nseg = g.nseg;
+    a.chunks = g.chunks;
+    a.cps = g.cps;
+    a.bias_part = g.bias_part;
+    const dim3 grid(cdiv(Cin, 64), cdiv(Cout, 64), g.splits);
     if (taps == 4) {
         // the five taps outside the 2x2 sub-window get an exact zero gradient
         if (!accumulate && hipMemsetAsync(dw, 0, sizeof(float) * (size_t)Cout * cin_real * 9, st) != hipSuccess) {
@@ -383,15 +396,7 @@ static int wgrad_launch(const float* x, const float* dz, float* dw, float* db, f
         hipLaunchKernelGGL((conv3x3_wgrad_kernel<9, false>), grid, dim3(WT), 0, st, a);
     }
     WITW_CHECK_LAUNCH("conv3x3_wgrad");
-    const size_t n = (size_t)taps * Cin * Cout;
-    if (splits >= 32)
-        hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((n + Cout + RW_E - 1) / RW_E)), dim3(RW_E * RW_G), 0, st,
-                           workspace, dw, Cin, Cout, splits, accumulate, cin_real, taps, a.bias_part, db);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + Cout + 255) / 256)), dim3(256), 0, st, workspace, dw, Cin, Cout,
-                           splits, accumulate, cin_real, taps, a.bias_part, db);
-    WITW_CHECK_LAUNCH("wgrad_reduce");
-    return WITW_OK;
+    return witw_wgrad_reduce(workspace, g.bias_part, dw, db, Cin, cin_real, Cout, taps, g.parts, g.splits, accumulate, WGRAD_WIDE_AT_32, stream);
 }
 
 int witw_conv3x3_wgrad(const float* x, const float* dz, float* dw, float* db, float* workspace, int B, int H, int W, int Cin,

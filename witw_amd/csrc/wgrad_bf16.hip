@@ -17,17 +17,19 @@
 // accumulator tiles (144 registers; 18 tiles per wave do not fit the 256 accumulator registers). One K chunk = one image octet x R output rows x 8 output columns: the (R-1)*SH+3 halo rows x 10 columns
 // of X and the R x 8 pixels of dZ move into LDS by LDS-DMA (buffer_load ... lds: a (pixel, 64 channels) run is
 // 1 KB contiguous in both HBM and LDS; padding = out-of-range offsets, which store zeros), double buffered.
-// Split-K partials go to a workspace and are summed in a fixed order (bitwise reproducible).
+// Split-K partials go to a workspace and are summed in a fixed order (bitwise reproducible) by witw_wgrad_reduce
+// (conv3x3_wgrad.hip), in its serial form at every split count; the launch prologue is wgrad_common.h's.
 // The bias gradient db[co] = sum dZ rides along: the waves of the first ci tile that own ci rows 0-31 feed the dZ
 // fragment they hold anyway to two v_mfma_f32_16x16x32_bf16 against a constant 'ones in row 0' operand (+1/9 MFMA
 // time on 1/(Cin/64) of the workgroups) instead of a separate pass over dZ.
 #include "common.h"
+#include "layout16.h"
 #include "lds_frag.h"
+#include "wgrad_common.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int WB_P = 8;                 // output columns per chunk
 constexpr int WB_XC = WB_P + 2;         // halo columns
@@ -205,67 +207,9 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16_kernel(WgradBfArgs p) 
     }
 }
 
-// dW[co][ci][kh][kw] (+)= sum_split ws[split][tap][ci][co]; one thread per (tap, ci, co), co fastest.
-// Threads past the weight elements sum the bias partials: db[co] (+)= sum_split bias_part[split][co].
-__global__ void wgrad_bf16_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Cin, int Cout, int splits,
-                                         int accumulate, int cin_real, const float* __restrict__ bias_part,
-                                         float* __restrict__ db) {
-    const size_t n = (size_t)9 * Cin * Cout;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) {
-        const size_t co = idx - n;
-        if (db != nullptr && co < (size_t)Cout) {
-            float s = 0.f;
-            for (int k = 0; k < splits; ++k) s += bias_part[(size_t)k * Cout + co];
-            db[co] = accumulate ? db[co] + s : s;
-        }
-        return;
-    }
-    const int co = idx % Cout;
-    const size_t t = idx / Cout;
-    const int ci = t % Cin;
-    const int tap = (int)(t / Cin);
-    float s = 0.f;
-    for (int k = 0; k < splits; ++k) s += ws[(size_t)k * n + idx];
-    if (ci >= cin_real) return;
-    float* d = dw + ((size_t)co * cin_real + ci) * 9 + tap;
-    *d = accumulate ? (*d + s) : s;
-}
-
-// NHWC bf16 [B][HW][C] -> batch-octet [ceil(B/8)][HW][C][8] (images past B are zeros). One thread per
-// (octet, pixel, channel octet): 8 loads of 16 B (8 channels of one image), an 8x8 transpose in registers,
-// 8 stores of 16 B (one channel, 8 images) = 128 contiguous bytes.
-__global__ void nhwc_to_octet_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y, int B, size_t HW, int C,
-                                     size_t total) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int C8 = C >> 3;
-    const int c8 = idx % C8;
-    const size_t t = idx / C8;
-    const size_t pix = t % HW;
-    const size_t b8 = t / HW;
-    u16x8 in[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const size_t b = b8 * 8 + i;
-        if (b < (size_t)B)
-            in[i] = *reinterpret_cast<const u16x8*>(x + ((b * HW + pix) * C + (size_t)c8 * 8));
-        else
-            in[i] = (u16x8){0, 0, 0, 0, 0, 0, 0, 0};
-    }
-    u16x8* out = reinterpret_cast<u16x8*>(y + (((b8 * HW + pix) * C + (size_t)c8 * 8) * 8));
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        u16x8 o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = in[i][j];
-        out[j] = o;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // Round 5: the same weight gradient straight from the NHWC tensors the forward / dgrad kernels write -- no batch-octet copies
-// (nhwc_to_octet_kernel was 1.05 ms of the 15.0 ms bf16 training step, 2.5 ms of cvig_semantic's 29 ms; profiles/r05_*).
+// (the batch-octet re-layout was 1.05 ms of the 15.0 ms bf16 training step, 2.5 ms of cvig_semantic's 29 ms; profiles/r05_*).
 //
 // The contraction index k of the MFMA is now the PIXEL: one k-step = 16 consecutive output columns of one row of one image
 // (lanes 0-31 take columns 0-7, lanes 32-63 columns 8-15). In NHWC a lane's 8 k values are 8 pixels = 8 far-apart 2-byte
@@ -812,26 +756,15 @@ int wgrad_nh_ksplit(int Cin, int Cout, int stride_h) {
 // is instantiated.
 int wgrad_nh_rows(int stride_h) { return stride_h == 2 ? 4 : 8; }
 
-int wgrad_nh_splits(int B, int Ho, int Wo, int Cin, int Cout, int stride_h) {
-    const int tiles = cdiv(Cin, WB_TM) * cdiv(Cout, WB_TN);
-    const bool k16 = wgrad_nh16_applies(Wo, Cin, Cout, stride_h);      // stage = 4 rows x 32 columns instead of 8 x 16
-    const int chunks = k16 ? B * cdiv(Ho, 4) * cdiv(Wo, N16_P) : B * cdiv(Ho, wgrad_nh_rows(stride_h)) * cdiv(Wo, NH_P);
-    int splits = cdiv(witw_cu_count(), tiles);       // one workgroup per CU; every extra split costs a 36*Cin*Cout-byte partial
-    if (splits > chunks) splits = chunks;
-    if (splits < 1) splits = 1;
-    return splits;
+// 32x32x16: image x R rows x 16 columns per K chunk (16x16x32: 4 rows x 32 columns), 64 x 128 tiles, one workgroup per CU; every
+// extra split costs a 36*Cin*Cout-byte partial
+WgradTiling wgrad_nh_tiling(int Wo, int Cin, int Cout, int stride_h) {
+    if (wgrad_nh16_applies(Wo, Cin, Cout, stride_h)) return {witw_cu_count(), WB_TM, WB_TN, 4, N16_P};
+    return {witw_cu_count(), WB_TM, WB_TN, wgrad_nh_rows(stride_h), NH_P};
 }
 
-int wgrad_bf16_rows(int stride_h) { return stride_h == 2 ? 1 : 2; }
-
-int wgrad_bf16_splits(int B8, int Ho, int Wo, int Cin, int Cout, int stride_h) {
-    const int tiles = cdiv(Cin, WB_TM) * cdiv(Cout, WB_TN);
-    const int chunks = B8 * cdiv(Ho, wgrad_bf16_rows(stride_h)) * cdiv(Wo, WB_P);
-    int splits = cdiv(256, tiles);            // one workgroup per CU; every extra split costs a 36*Cin*Cout-byte partial
-    if (splits > chunks) splits = chunks;
-    if (splits < 1) splits = 1;
-    return splits;
-}
+// batch-octet kernel: image octet x 2 rows (1 at stride 2) x 8 columns per K chunk, one workgroup per CU
+WgradTiling wgrad_bf16_tiling(int stride_h) { return {256, WB_TM, WB_TN, stride_h == 2 ? 1 : 2, WB_P}; }
 
 }  // namespace
 
@@ -844,55 +777,43 @@ int witw_nhwc_bf16_to_octet(const void* x_bf16, void* y_bf16, int B, int H, int 
     WITW_CHECK_ARG(x_bf16 && y_bf16, "nhwc_bf16_to_octet: null pointer");
     WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && (C % 8) == 0, "nhwc_bf16_to_octet: bad shape (C=%d must be a multiple of 8)", C);
     const size_t total = (size_t)cdiv(B, 8) * H * W * (C / 8);
-    hipLaunchKernelGGL(nhwc_to_octet_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(to_octet_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)x_bf16, (unsigned short*)y_bf16, B, (size_t)H * W, C, total);
     WITW_CHECK_LAUNCH("nhwc_bf16_to_octet");
     return WITW_OK;
 }
 
 long long witw_conv3x3_wgrad_bf16_workspace_floats(int B, int H, int W, int Cin, int Cout, int stride_h) {
-    const int Ho = (H + 2 - 3) / stride_h + 1;
-    const long long splits = wgrad_bf16_splits(cdiv(B, 8), Ho, W, Cin, Cout, stride_h);
-    return splits * 9 * Cin * Cout + splits * Cout;
+    const WgradGeom g = wgrad_geom(wgrad_bf16_tiling(stride_h), cdiv(B, 8), 1, H, W, Cin, Cout, stride_h);
+    return wgrad_workspace_floats(g, g.splits, Cout);
 }
 
 // x_oct [B8][H][W][Cin][8], dz_oct [B8][Ho][W][Cout][8] (batch-octet bf16, witw_nhwc_bf16_to_octet).
 // dw [Cout][cin_real][3][3] fp32 (torch layout), db [Cout] fp32 or NULL. accumulate != 0 adds instead of overwriting.
 int witw_conv3x3_wgrad_bf16(const void* x_oct, const void* dz_oct, float* dw, float* db, float* workspace, int B, int H, int W,
                             int Cin, int cin_real, int Cout, int stride_h, int pad_circular, int accumulate, void* stream) {
-    WITW_CHECK_ARG(x_oct && dz_oct && dw && workspace, "conv3x3_wgrad_bf16: null pointer");
-    WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_wgrad_bf16: bad shape");
-    WITW_CHECK_ARG((Cin % 8) == 0 && (Cout % 8) == 0, "conv3x3_wgrad_bf16: Cin=%d and Cout=%d must be multiples of 8", Cin, Cout);
-    WITW_CHECK_ARG(cin_real > 0 && cin_real <= Cin, "conv3x3_wgrad_bf16: cin_real=%d outside (0,%d]", cin_real, Cin);
-    WITW_CHECK_ARG(stride_h == 1 || stride_h == 2, "conv3x3_wgrad_bf16: stride_h=%d unsupported", stride_h);
     const int B8 = cdiv(B, 8);
-    const int Ho = (H + 2 - 3) / stride_h + 1;
-    WITW_CHECK_ARG((size_t)B8 * H * W * Cin * 16 < 0x80000000ull && (size_t)B8 * Ho * W * Cout * 16 < 0x80000000ull,
+    WgradGeom g;
+    if (int rc = wgrad_prologue(g, "conv3x3_wgrad_bf16", 8, wgrad_bf16_tiling(stride_h), B8, 1, x_oct, dz_oct, dw, db, workspace, B, H, W, Cin,
+                                cin_real, Cout, stride_h))
+        return rc;
+    WITW_CHECK_ARG((size_t)B8 * H * W * Cin * 16 < 0x80000000ull && (size_t)B8 * g.Ho * W * Cout * 16 < 0x80000000ull,
                    "conv3x3_wgrad_bf16: operand too large for one buffer descriptor");
     hipStream_t st = (hipStream_t)stream;
     WgradBfArgs a;
     a.x = (const unsigned short*)x_oct; a.dz = (const unsigned short*)dz_oct; a.ws = workspace;
-    a.B8 = B8; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Ho = Ho; a.Wo = W;
+    a.B8 = B8; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Ho = g.Ho; a.Wo = W;
     a.circ = pad_circular;
-    const int R = wgrad_bf16_rows(stride_h);
-    a.nseg = cdiv(a.Wo, WB_P);
-    a.nrg = cdiv(Ho, R);
-    a.chunks = B8 * a.nrg * a.nseg;
-    const int splits = wgrad_bf16_splits(B8, Ho, a.Wo, Cin, Cout, stride_h);
-    a.cps = cdiv(a.chunks, splits);
-    const size_t n = (size_t)9 * Cin * Cout;
-    a.bias_part = db ? workspace + (size_t)splits * n : nullptr;
-    const dim3 grid(cdiv(Cin, WB_TM), cdiv(Cout, WB_TN), splits);
+    a.nseg = g.nseg; a.nrg = g.nrg; a.chunks = g.chunks; a.cps = g.cps;
+    a.bias_part = g.bias_part;
+    const dim3 grid(cdiv(Cin, WB_TM), cdiv(Cout, WB_TN), g.splits);
     if (stride_h == 2)
         hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<2, 1>), grid, dim3(512), 0, st, a);
     else
         hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<1, 2>), grid, dim3(512), 0, st, a);
     WITW_CHECK_LAUNCH("conv3x3_wgrad_bf16");
     // (a split whose chunk range came out empty has written zero partials)
-    hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3((unsigned)((n + Cout + 255) / 256)), dim3(256), 0, st, workspace, dw, Cin,
-                       Cout, splits, accumulate, cin_real, a.bias_part, db);
-    WITW_CHECK_LAUNCH("wgrad_bf16_reduce");
-    return WITW_OK;
+    return witw_wgrad_reduce(workspace, g.bias_part, dw, db, Cin, cin_real, Cout, 9, g.parts, g.splits, accumulate, WGRAD_SERIAL, stream);
 }
 
 
@@ -906,9 +827,8 @@ int witw_conv3x3_wgrad_bf16_mfma16(int enable) {
 }
 
 long long witw_conv3x3_wgrad_bf16_nhwc_workspace_floats(int B, int H, int W, int Cin, int Cout, int stride_h) {
-    const int Ho = (H + 2 - 3) / stride_h + 1;
-    const long long splits = wgrad_nh_splits(B, Ho, W, Cin, Cout, stride_h);
-    return splits * 9 * Cin * Cout + splits * Cout;
+    const WgradGeom g = wgrad_geom(wgrad_nh_tiling(W, Cin, Cout, stride_h), B, 1, H, W, Cin, Cout, stride_h);
+    return wgrad_workspace_floats(g, g.splits, Cout);
 }
 
 // The same gradient from the NHWC tensors themselves: x [B][H][W][Cin], dz [B][Ho][W][Cout] bf16 (what the bf16 forward and
@@ -917,32 +837,25 @@ long long witw_conv3x3_wgrad_bf16_nhwc_workspace_floats(int B, int H, int W, int
 // entry (different summation order within a split).
 int witw_conv3x3_wgrad_bf16_nhwc(const void* x_nhwc, const void* dz_nhwc, float* dw, float* db, float* workspace, int B, int H, int W,
                                  int Cin, int cin_real, int Cout, int stride_h, int pad_circular, int accumulate, void* stream) {
-    WITW_CHECK_ARG(x_nhwc && dz_nhwc && dw && workspace, "conv3x3_wgrad_bf16_nhwc: null pointer");
-    WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_wgrad_bf16_nhwc: bad shape");
-    WITW_CHECK_ARG((Cin % 8) == 0 && (Cout % 8) == 0, "conv3x3_wgrad_bf16_nhwc: Cin=%d and Cout=%d must be multiples of 8", Cin, Cout);
-    WITW_CHECK_ARG(cin_real > 0 && cin_real <= Cin, "conv3x3_wgrad_bf16_nhwc: cin_real=%d outside (0,%d]", cin_real, Cin);
-    WITW_CHECK_ARG(stride_h == 1 || stride_h == 2, "conv3x3_wgrad_bf16_nhwc: stride_h=%d unsupported", stride_h);
-    const int Ho = (H + 2 - 3) / stride_h + 1;
-    WITW_CHECK_ARG((size_t)B * H * W * Cin * 2 < 0x80000000ull && (size_t)B * Ho * W * Cout * 2 < 0x80000000ull,
+    const bool k16 = wgrad_nh16_applies(W, Cin, Cout, stride_h);
+    const WgradTiling t = wgrad_nh_tiling(W, Cin, Cout, stride_h);
+    WgradGeom g;
+    if (int rc = wgrad_prologue(g, "conv3x3_wgrad_bf16_nhwc", 8, t, B, 1, x_nhwc, dz_nhwc, dw, db, workspace, B, H, W, Cin, cin_real, Cout,
+                                stride_h))
+        return rc;
+    WITW_CHECK_ARG((size_t)B * H * W * Cin * 2 < 0x80000000ull && (size_t)B * g.Ho * W * Cout * 2 < 0x80000000ull,
                    "conv3x3_wgrad_bf16_nhwc: operand too large for one buffer descriptor");
     hipStream_t st = (hipStream_t)stream;
     WgradNhArgs a;
     a.x = (const unsigned short*)x_nhwc; a.dz = (const unsigned short*)dz_nhwc; a.ws = workspace;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Ho = Ho; a.Wo = W;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Ho = g.Ho; a.Wo = W;
     a.circ = pad_circular;
-    const bool k16 = wgrad_nh16_applies(a.Wo, Cin, Cout, stride_h);
-    const int R = k16 ? 4 : wgrad_nh_rows(stride_h);
-    a.nseg = cdiv(a.Wo, k16 ? N16_P : NH_P);
-    a.nrg = cdiv(Ho, R);
-    a.chunks = B * a.nrg * a.nseg;
+    a.nseg = g.nseg; a.nrg = g.nrg; a.chunks = g.chunks; a.cps = g.cps;
     a.tiles_ci = cdiv(Cin, WB_TM); a.tiles_co = cdiv(Cout, WB_TN);
-    a.splits = wgrad_nh_splits(B, Ho, a.Wo, Cin, Cout, stride_h);
-    a.cps = cdiv(a.chunks, a.splits);
-    const size_t n = (size_t)9 * Cin * Cout;
+    a.splits = g.splits;
+    a.bias_part = g.bias_part;
     int nwm, nwn;
     wgrad_nh_roles(Cin, Cout, stride_h, &nwm, &nwn);
-    const int parts = a.splits;                          // partial tiles in the workspace
-    a.bias_part = db ? workspace + (size_t)parts * n : nullptr;
     const dim3 grid((unsigned)(a.tiles_ci * a.tiles_co * a.splits));
 #define WITW_NH_LAUNCH(SH_, R_, NWM_, NWN_) \
     hipLaunchKernelGGL((conv3x3_wgrad_bf16_nhwc_kernel<SH_, R_, 2, NWM_, NWN_>), grid, dim3(512), 0, st, a)
@@ -963,11 +876,10 @@ int witw_conv3x3_wgrad_bf16_nhwc(const void* x_nhwc, const void* dz_nhwc, float*
     }
 #undef WITW_NH_LAUNCH
     WITW_CHECK_LAUNCH("conv3x3_wgrad_bf16_nhwc");
-    hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3((unsigned)((n + Cout + 255) / 256)), dim3(256), 0, st, workspace, dw, Cin,
-                       Cout, parts, accumulate, cin_real, a.bias_part, db);
-    WITW_CHECK_LAUNCH("wgrad_bf16_reduce");
-    if (k16) witw_note_variant("conv3x3_wgrad_bf16_nhwc16_kernel<%d,%d>", stride_h, R);
-    else witw_note_variant("conv3x3_wgrad_bf16_nhwc_kernel<%d,%d,%d,%d>", stride_h, R, nwm, nwn);
+    if (int rc = witw_wgrad_reduce(workspace, g.bias_part, dw, db, Cin, cin_real, Cout, 9, g.parts, g.splits, accumulate, WGRAD_SERIAL, stream))
+        return rc;
+    if (k16) witw_note_variant("conv3x3_wgrad_bf16_nhwc16_kernel<%d,%d>", stride_h, t.rows);
+    else witw_note_variant("conv3x3_wgrad_bf16_nhwc_kernel<%d,%d,%d,%d>", stride_h, t.rows, nwm, nwn);
     return WITW_OK;
 }
 

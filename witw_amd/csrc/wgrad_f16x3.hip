@@ -11,9 +11,13 @@
 // Workgroup = 8 waves, tile 64 (ci) x 64 (co) of all 9 taps; wave (wm, wn, kq): 32 ci x 32 co, pixel pairs {2kq, 2kq+1} of
 // the chunk's four (the two kq groups write separate split-K partials). One K chunk = one image octet x one output row x 8
 // columns: 3 x 10 halo pixels of X and 8 pixels of dZ, both planes, by LDS-DMA into a [pixel][plane][channel] image
-// (conflict-free ds_read_b128), double buffered (2 x 76 KB).
+// (conflict-free ds_read_b128), double buffered (2 x 76 KB). The partials (two per split) and the bias partials of
+// split_channel_sums_kernel are summed by witw_wgrad_reduce (conv3x3_wgrad.hip, serial form); the launch prologue is
+// wgrad_common.h's.
 #include "common.h"
+#include "layout16.h"
 #include "lds_frag.h"
+#include "wgrad_common.h"
 
 namespace {
 
@@ -166,61 +170,8 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_f16x3_kernel(WgradHxArgs p)
     }
 }
 
-// dW[co][ci][kh][kw] (+)= sum_k ws[k][tap][ci][co]; one thread per (tap, ci, co), co fastest.
-__global__ void wgrad_f16x3_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Cin, int Cout, int parts,
-                                          int accumulate, int cin_real) {
-    const size_t n = (size_t)9 * Cin * Cout;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    const int co = idx % Cout;
-    const size_t t = idx / Cout;
-    const int ci = t % Cin;
-    const int tap = (int)(t / Cin);
-    float s = 0.f;
-    for (int k = 0; k < parts; ++k) s += ws[(size_t)k * n + idx];
-    if (ci >= cin_real) return;
-    float* d = dw + ((size_t)co * cin_real + ci) * 9 + tap;
-    *d = accumulate ? (*d + s) : s;
-}
-
-// split-fp16 NHWC [B][HW][C/8][2][8] -> batch-octet split [ceil(B/8)][HW][C][2][8] (images past B are zeros). One thread
-// per (octet, pixel, channel octet): 16 loads of 16 B, two 8x8 transposes in registers, 16 stores of 16 B (512 contiguous bytes).
-__global__ void split_to_octet_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y, int B, size_t HW, int C,
-                                      size_t total) {
-    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int C8 = C >> 3;
-    const int c8 = idx % C8;
-    const size_t t = idx / C8;
-    const size_t pix = t % HW;
-    const size_t b8 = t / HW;
-    u16x8 in[2][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const size_t b = b8 * 8 + i;
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-            if (b < (size_t)B)
-                in[pl][i] = *reinterpret_cast<const u16x8*>(x + (((b * HW + pix) * C8 + c8) * 2 + pl) * 8);
-            else
-                in[pl][i] = (u16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    }
-    u16x8* out = reinterpret_cast<u16x8*>(y + (((b8 * HW + pix) * C + (size_t)c8 * 8) * 2) * 8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-            u16x8 o;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o[i] = in[pl][i][j];
-            out[j * 2 + pl] = o;
-        }
-}
-
 // bias gradient db[co] = sum over images and pixels of dZ (hi + lo) from the split-fp16 NHWC gradient: thread -> (channel
-// octet, pixel phase), fixed-order combination through LDS, partials [blocks][C] summed by the finish kernel
+// octet, pixel phase), fixed-order combination through LDS, partials [blocks][C] summed by the reduce kernel
 __global__ __launch_bounds__(256) void split_channel_sums_kernel(const unsigned short* __restrict__ dz, float* __restrict__ part,
                                                                   size_t npix, int C, int rows_per_block) {
     __shared__ float sh[256][9];
@@ -253,26 +204,18 @@ __global__ __launch_bounds__(256) void split_channel_sums_kernel(const unsigned 
     }
 }
 
-__global__ void split_bias_finish_kernel(const float* __restrict__ part, float* __restrict__ db, int C, int nparts, int accumulate) {
-    const int co = blockIdx.x * blockDim.x + threadIdx.x;
-    if (co >= C) return;
-    float s = 0.f;
-    for (int k = 0; k < nparts; ++k) s += part[(size_t)k * C + co];
-    db[co] = accumulate ? db[co] + s : s;
-}
-
-int hx_bias_rows(size_t npix) {         // ~96 partials: the finish kernel walks them serially per channel
+int hx_bias_rows(size_t npix) {         // ~96 partials: the reduce kernel walks them serially per channel
     size_t r = (npix + 95) / 96;
     return (int)(r < 32 ? 32 : r);
 }
 
-int wgrad_hx_splits(int B8, int Ho, int Wo, int Cin, int Cout) {
-    const int tiles = cdiv(Cin, WH_T) * cdiv(Cout, WH_T);
-    const int chunks = B8 * Ho * cdiv(Wo, WH_P);
-    int splits = cdiv(256, tiles);            // one workgroup per CU
-    if (splits > chunks) splits = chunks;
-    return splits < 1 ? 1 : splits;
+long long hx_bias_parts(int B, int Ho, int W) {
+    const size_t npix = (size_t)B * Ho * W;
+    return (long long)((npix + hx_bias_rows(npix) - 1) / hx_bias_rows(npix));
 }
+
+// image octet x one row x 8 columns per K chunk, 64 x 64 tiles, one workgroup per CU
+constexpr WgradTiling WG_HX = {256, WH_T, WH_T, 1, WH_P};
 
 }  // namespace
 
@@ -285,18 +228,15 @@ int witw_split_f16_to_octet(const void* x_split, void* y_oct, int B, int H, int 
     WITW_CHECK_ARG(x_split && y_oct, "split_f16_to_octet: null pointer");
     WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && (C % 8) == 0, "split_f16_to_octet: bad shape (C=%d must be a multiple of 8)", C);
     const size_t total = (size_t)cdiv(B, 8) * H * W * (C / 8);
-    hipLaunchKernelGGL(split_to_octet_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(to_octet_kernel<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)x_split, (unsigned short*)y_oct, B, (size_t)H * W, C, total);
     WITW_CHECK_LAUNCH("split_f16_to_octet");
     return WITW_OK;
 }
 
 long long witw_conv3x3_wgrad_f16x3_workspace_floats(int B, int H, int W, int Cin, int Cout, int stride_h) {
-    const int Ho = (H + 2 - 3) / stride_h + 1;
-    const long long splits = wgrad_hx_splits(cdiv(B, 8), Ho, W, Cin, Cout);
-    const size_t npix = (size_t)B * Ho * W;
-    const long long bias_parts = (long long)((npix + hx_bias_rows(npix) - 1) / hx_bias_rows(npix));
-    return 2 * splits * 9 * Cin * Cout + bias_parts * Cout;
+    const WgradGeom g = wgrad_geom(WG_HX, cdiv(B, 8), 2, H, W, Cin, Cout, stride_h);
+    return wgrad_workspace_floats(g, hx_bias_parts(B, g.Ho, W), Cout);
 }
 
 // x_oct [B8][H][W][Cin][2][8], dz_oct [B8][Ho][W][Cout][2][8] (witw_split_f16_to_octet), dz_split = the same gradient as
@@ -304,47 +244,36 @@ long long witw_conv3x3_wgrad_f16x3_workspace_floats(int B, int H, int W, int Cin
 int witw_conv3x3_wgrad_f16x3(const void* x_oct, const void* dz_oct, const void* dz_split, float* dw, float* db, float* workspace,
                              int B, int H, int W, int Cin, int cin_real, int Cout, int stride_h, int pad_circular, int accumulate,
                              void* stream) {
-    WITW_CHECK_ARG(x_oct && dz_oct && dw && workspace, "conv3x3_wgrad_f16x3: null pointer");
-    WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_wgrad_f16x3: bad shape");
-    WITW_CHECK_ARG((Cin % 8) == 0 && (Cout % 8) == 0, "conv3x3_wgrad_f16x3: Cin=%d and Cout=%d must be multiples of 8", Cin, Cout);
-    WITW_CHECK_ARG(cin_real > 0 && cin_real <= Cin, "conv3x3_wgrad_f16x3: cin_real=%d outside (0,%d]", cin_real, Cin);
-    WITW_CHECK_ARG(stride_h == 1 || stride_h == 2, "conv3x3_wgrad_f16x3: stride_h=%d unsupported", stride_h);
+    const int B8 = cdiv(B, 8);
+    WgradGeom g;
+    if (int rc = wgrad_prologue(g, "conv3x3_wgrad_f16x3", 8, WG_HX, B8, 2, x_oct, dz_oct, dw, db, workspace, B, H, W, Cin, cin_real, Cout,
+                                stride_h))
+        return rc;
     WITW_CHECK_ARG(!db || dz_split, "conv3x3_wgrad_f16x3: the bias gradient needs dz_split");
     WITW_CHECK_ARG(!db || (256 % (Cout / 8)) == 0, "conv3x3_wgrad_f16x3: bias gradient needs Cout/8 to divide 256 (Cout=%d)", Cout);
-    const int B8 = cdiv(B, 8);
-    const int Ho = (H + 2 - 3) / stride_h + 1;
-    WITW_CHECK_ARG((size_t)H * W * Cin * 32 < 0x80000000ull && (size_t)Ho * W * Cout * 32 < 0x80000000ull,
+    WITW_CHECK_ARG((size_t)H * W * Cin * 32 < 0x80000000ull && (size_t)g.Ho * W * Cout * 32 < 0x80000000ull,
                    "conv3x3_wgrad_f16x3: one image octet of an operand exceeds a buffer descriptor");
     hipStream_t st = (hipStream_t)stream;
     WgradHxArgs a;
     a.x = (const unsigned short*)x_oct; a.dz = (const unsigned short*)dz_oct; a.ws = workspace;
-    a.B8 = B8; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Ho = Ho; a.Wo = W;
+    a.B8 = B8; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Ho = g.Ho; a.Wo = W;
     a.circ = pad_circular;
-    a.nseg = cdiv(a.Wo, WH_P);
-    a.chunks = B8 * Ho * a.nseg;
-    const int splits = wgrad_hx_splits(B8, Ho, a.Wo, Cin, Cout);
-    a.cps = cdiv(a.chunks, splits);
-    const dim3 grid(cdiv(Cin, WH_T), cdiv(Cout, WH_T), splits);
+    a.nseg = g.nseg; a.chunks = g.chunks; a.cps = g.cps;
+    const dim3 grid(cdiv(Cin, WH_T), cdiv(Cout, WH_T), g.splits);
     if (stride_h == 2)
         hipLaunchKernelGGL((conv3x3_wgrad_f16x3_kernel<2>), grid, dim3(512), 0, st, a);
     else
         hipLaunchKernelGGL((conv3x3_wgrad_f16x3_kernel<1>), grid, dim3(512), 0, st, a);
     WITW_CHECK_LAUNCH("conv3x3_wgrad_f16x3");
-    const size_t n = (size_t)9 * Cin * Cout;
-    hipLaunchKernelGGL(wgrad_f16x3_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, workspace, dw, Cin, Cout,
-                       2 * splits, accumulate, cin_real);
-    WITW_CHECK_LAUNCH("wgrad_f16x3_reduce");
+    int bias_parts = 0;
     if (db != nullptr) {
-        float* part = workspace + (size_t)2 * splits * n;
-        const size_t npix = (size_t)B * Ho * W;
-        const int rows = hx_bias_rows(npix);
-        const int nparts = (int)((npix + rows - 1) / rows);
-        hipLaunchKernelGGL(split_channel_sums_kernel, dim3(nparts), dim3(256), 0, st, (const unsigned short*)dz_split, part, npix, Cout,
-                           rows);
-        hipLaunchKernelGGL(split_bias_finish_kernel, dim3(cdiv(Cout, 256)), dim3(256), 0, st, part, db, Cout, nparts, accumulate);
+        const size_t npix = (size_t)B * g.Ho * W;
+        bias_parts = (int)hx_bias_parts(B, g.Ho, W);
+        hipLaunchKernelGGL(split_channel_sums_kernel, dim3(bias_parts), dim3(256), 0, st, (const unsigned short*)dz_split, g.bias_part, npix,
+                           Cout, hx_bias_rows(npix));
         WITW_CHECK_LAUNCH("bias_grad_f16x3");
     }
-    return WITW_OK;
+    return witw_wgrad_reduce(workspace, g.bias_part, dw, db, Cin, cin_real, Cout, 9, g.parts, bias_parts, accumulate, WGRAD_SERIAL, stream);
 }
 
 }  // extern "C"

@@ -442,6 +442,24 @@ def maxpool2x2_bwd(dy, code, out_hw):
     return dx
 
 
+def _wgrad_setup(name, B, H, W, Cout, cin_real, stride_h, dz_lead_shape, device, want_bias, out):
+    """What the weight-gradient wrappers share: dz [B,Ho,W,..] must belong to x [B,H,W,..] under stride (stride_h, 1);
+    out = (dW, db) is validated (contiguous fp32 GPU tensors [Cout,cin_real,3,3] and [Cout]), otherwise fresh tensors are
+    allocated (db only if want_bias). -> (Ho, dW, db)"""
+    Ho = (H + 2 - 3) // stride_h + 1
+    if tuple(dz_lead_shape) != (B, Ho, W):
+        raise _lib.WitwError('%s: dz %s.. does not match x %s.. (stride %d)' % (name, tuple(dz_lead_shape), (B, H, W), stride_h))
+    if out is None:
+        dw = torch.empty((Cout, cin_real, 3, 3), dtype=torch.float32, device=device)
+        db = torch.empty((Cout,), dtype=torch.float32, device=device) if want_bias else None
+        return Ho, dw, db
+    dw, db = out
+    if not (dw.is_contiguous() and tuple(dw.shape) == (Cout, cin_real, 3, 3) and dw.dtype == torch.float32 and dw.is_cuda
+            and db is not None and db.is_contiguous() and db.numel() == Cout and db.dtype == torch.float32 and db.is_cuda):
+        raise _lib.WitwError('%s: out must be contiguous float32 GPU tensors [%d,%d,3,3] and [%d]' % (name, Cout, cin_real, Cout))
+    return Ho, dw, db
+
+
 def conv3x3_wgrad(x_nhwc, dz_nhwc, cin_real, stride_h=1, circular=False, want_bias=True, taps4=False, out=None):
     """-> (dW [Cout,cin_real,3,3], db [Cout] or None) for one conv layer. taps4: only the taps {1,2}^2 are computed
     (filters whose first tap row/column are structurally zero), the others come back as exact zeros. out = (dW, db): write
@@ -450,18 +468,8 @@ def conv3x3_wgrad(x_nhwc, dz_nhwc, cin_real, stride_h=1, circular=False, want_bi
     x = _dev_f32(x_nhwc, 'x')
     dz = _dev_f32(dz_nhwc, 'dz')
     B, H, W, Cin = x.shape
-    Ho = (H + 2 - 3) // stride_h + 1
     Cout = dz.shape[3]
-    if tuple(dz.shape[:3]) != (B, Ho, W):
-        raise _lib.WitwError('conv3x3_wgrad: dz %s does not match x %s (stride %d)' % (tuple(dz.shape), tuple(x.shape), stride_h))
-    if out is not None:
-        dw, db = out
-        if not (dw.is_contiguous() and tuple(dw.shape) == (Cout, cin_real, 3, 3) and dw.dtype == torch.float32 and dw.is_cuda
-                and db is not None and db.is_contiguous() and db.numel() == Cout):
-            raise _lib.WitwError('conv3x3_wgrad: out must be contiguous float32 GPU tensors [%d,%d,3,3] and [%d]' % (Cout, cin_real, Cout))
-    else:
-        dw = torch.empty((Cout, cin_real, 3, 3), dtype=torch.float32, device=x.device)
-        db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    _, dw, db = _wgrad_setup('conv3x3_wgrad', B, H, W, Cout, cin_real, stride_h, dz.shape[:3], x.device, want_bias, out)
     ws = torch.empty(lib.witw_conv3x3_wgrad_workspace_floats(B, H, W, Cin, Cout, stride_h), dtype=torch.float32,
                      device=x.device)
     if taps4:
@@ -1569,7 +1577,7 @@ def nhwc_bf16_to_octet(x):
     return y
 
 
-def conv3x3_wgrad_bf16(x_nhwc, dz_nhwc, cin_real, stride_h=1, circular=False, want_bias=True, x_oct=None, layout='nhwc', out=None):
+def conv3x3_wgrad_bf16(x_nhwc, dz_nhwc, cin_real, stride_h=1, circular=False, want_bias=True, layout='nhwc', out=None):
     """bf16 MFMA weight gradient of one conv layer: x_nhwc [B,H,W,Cin] (its input), dz_nhwc [B,Ho,W,Cout] (gradient at
     its output), both bf16 NHWC -> (dW [Cout,cin_real,3,3] fp32, db [Cout] fp32 or None).
     layout='nhwc' (round 5, default): witw_conv3x3_wgrad_bf16_nhwc reads the two tensors as they are (pixels are the MFMA's k
@@ -1583,20 +1591,9 @@ def conv3x3_wgrad_bf16(x_nhwc, dz_nhwc, cin_real, stride_h=1, circular=False, wa
     if layout not in ('nhwc', 'octet'):
         raise _lib.WitwError("conv3x3_wgrad_bf16: layout must be 'nhwc' or 'octet'")
     B, H, W, Cin = x_nhwc.shape
-    Ho = (H + 2 - 3) // stride_h + 1
     Cout = dz_nhwc.shape[3]
-    if tuple(dz_nhwc.shape[:3]) != (B, Ho, W):
-        raise _lib.WitwError('conv3x3_wgrad_bf16: dz %s does not match x %s (stride %d)' % (tuple(dz_nhwc.shape),
-                                                                                          tuple(x_nhwc.shape), stride_h))
+    Ho, dw, db = _wgrad_setup('conv3x3_wgrad_bf16', B, H, W, Cout, cin_real, stride_h, dz_nhwc.shape[:3], x_nhwc.device, want_bias, out)
     prof = _prof_begin()
-    if out is not None:
-        dw, db = out
-        if not (dw.is_contiguous() and tuple(dw.shape) == (Cout, cin_real, 3, 3) and dw.dtype == torch.float32 and dw.is_cuda
-                and db is not None and db.is_contiguous() and db.numel() == Cout and db.dtype == torch.float32):
-            raise _lib.WitwError('conv3x3_wgrad_bf16: out must be contiguous float32 GPU tensors [%d,%d,3,3] and [%d]' % (Cout, cin_real, Cout))
-    else:
-        dw = torch.empty((Cout, cin_real, 3, 3), dtype=torch.float32, device=x_nhwc.device)
-        db = torch.empty((Cout,), dtype=torch.float32, device=x_nhwc.device) if want_bias else None
     if layout == 'nhwc':
         ws = torch.empty(lib.witw_conv3x3_wgrad_bf16_nhwc_workspace_floats(B, H, W, Cin, Cout, stride_h), dtype=torch.float32,
                          device=x_nhwc.device)
@@ -1604,9 +1601,7 @@ def conv3x3_wgrad_bf16(x_nhwc, dz_nhwc, cin_real, stride_h=1, circular=False, wa
                                                     B, H, W, Cin, cin_real, Cout, stride_h, int(circular), 0, _stream()),
                    'witw_conv3x3_wgrad_bf16_nhwc')
     else:
-        if x_oct is None:
-            x_oct = nhwc_bf16_to_octet(x_nhwc)
-        dz_oct = nhwc_bf16_to_octet(dz_nhwc)
+        x_oct, dz_oct = nhwc_bf16_to_octet(x_nhwc), nhwc_bf16_to_octet(dz_nhwc)
         ws = torch.empty(lib.witw_conv3x3_wgrad_bf16_workspace_floats(B, H, W, Cin, Cout, stride_h), dtype=torch.float32,
                          device=x_nhwc.device)
         _lib.check(lib.witw_conv3x3_wgrad_bf16(x_oct.data_ptr(), dz_oct.data_ptr(), dw.data_ptr(), _p(db),
@@ -1728,22 +1723,18 @@ def split_f16_to_octet(x_split):
     return y
 
 
-def conv3x3_wgrad_f16x3(x_split, dz_split, cin_real, stride_h=1, circular=False, want_bias=True):
+def conv3x3_wgrad_f16x3(x_split, dz_split, cin_real, stride_h=1, circular=False, want_bias=True, out=None):
     """Weight gradient with fp32-grade products on the fp16 MFMA: x_split [B,H,W,Cin/8,2,8] (the layer's input), dz_split
-    [B,Ho,W,Cout/8,2,8] (gradient at its output) -> (dW [Cout,cin_real,3,3] fp32, db [Cout] fp32 or None)."""
+    [B,Ho,W,Cout/8,2,8] (gradient at its output) -> (dW [Cout,cin_real,3,3] fp32, db [Cout] fp32 or None); out = (dW, db) as in
+    conv3x3_wgrad."""
     lib = _lib.load()
     if not (_is_split(x_split) and _is_split(dz_split)):
         raise _lib.WitwError('conv3x3_wgrad_f16x3: operands must be contiguous float16 GPU tensors shaped [B,H,W,C/8,2,8]')
     B, H, W, Ci8 = x_split.shape[:4]
     Cin, Cout = Ci8 * 8, dz_split.shape[3] * 8
-    Ho = (H + 2 - 3) // stride_h + 1
-    if tuple(dz_split.shape[:3]) != (B, Ho, W):
-        raise _lib.WitwError('conv3x3_wgrad_f16x3: dz %s does not match x %s (stride %d)' % (tuple(dz_split.shape),
-                                                                                           tuple(x_split.shape), stride_h))
+    Ho, dw, db = _wgrad_setup('conv3x3_wgrad_f16x3', B, H, W, Cout, cin_real, stride_h, dz_split.shape[:3], x_split.device, want_bias, out)
     prof = _prof_begin()
     x_oct, dz_oct = split_f16_to_octet(x_split), split_f16_to_octet(dz_split)
-    dw = torch.empty((Cout, cin_real, 3, 3), dtype=torch.float32, device=x_split.device)
-    db = torch.empty((Cout,), dtype=torch.float32, device=x_split.device) if want_bias else None
     ws = torch.empty(lib.witw_conv3x3_wgrad_f16x3_workspace_floats(B, H, W, Cin, Cout, stride_h), dtype=torch.float32,
                      device=x_split.device)
     _lib.check(lib.witw_conv3x3_wgrad_f16x3(x_oct.data_ptr(), dz_oct.data_ptr(), dz_split.data_ptr(), dw.data_ptr(), _p(db),
