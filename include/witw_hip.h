@@ -526,6 +526,30 @@ int witw_embed_normalize_bwd(const float* g, const float* df, float* dg, int B, 
 int witw_exhaustive_triplet_loss_bwd(const float* e1, const float* e2, const float* D, const float* grad_loss, float* de1,
                                      float* de2, int B, int n, int soft_margin, float alpha, float margin, float* workspace,
                                      void* stream);
+/* The same loss (:286-315) over the GLOBAL batch of B pairs when each of the ranks holds b of them (the reference gathers its
+ * nn.DataParallel replicas' embeddings and takes the loss over all B, :339-343): this rank's COLUMN SLAB T [B,b],
+ * T[g][c] = |x_g - y_c|^2 from witw_pairwise_sqdist(x, y), x [B,n] the all-gathered embeddings of one side, y [b,n] this rank's
+ * of the other, column c being column col0 + c of the global matrix (col0 = rank * b). diag [B]: the global diagonal,
+ * diag[col0 + c] = T[col0 + c][c] on the owning rank, all-gathered. l(x) = log(1 + exp(alpha x)) if soft_margin else
+ * max(x + margin, 0) (:297-301), l' its derivative. B >= 2, 1 <= b <= B, 0 <= col0, col0 + b <= B; no pointer may be NULL.
+ * Every sum has a fixed order, nothing is accumulated atomically: a call repeated gives the same bits.
+ * _fwd: partial[0] = sum_c sum_{g != col0+c} l(diag[col0+c] - T[g][c]) + l(diag[g] - T[g][c]), un-normalised: the caller sums
+ *       the ranks' partials and divides by 2B(B-1) (:313-315). workspace: B floats.
+ * _sig: colsig[c] = sum_{g != col0+c} l'(diag[col0+c] - T[g][c]) (b floats, complete) and rowsig[g] = sum_{c: col0+c != g}
+ *       l'(diag[g] - T[g][c]) (B floats, this slab's part: the caller sums it over the ranks).
+ * _bwd: G [B,b] = dL/dT for grad_loss (device scalar) of the GLOBAL loss, sc = grad_loss / (2B(B-1)):
+ *       G[g][c] = -(l'(diag[col0+c] - T[g][c]) + l'(diag[g] - T[g][c])) sc off the diagonal, G[col0+c][c] = (rowsig[col0+c] +
+ *       colsig[c]) sc on it; rowsig = the SUMMED row sums. */
+int witw_exhaustive_loss_slab_fwd(const float* T, const float* diag, int B, int b, int col0, int soft_margin, float alpha, float margin,
+                                  float* partial, float* workspace, void* stream);
+int witw_exhaustive_loss_slab_sig(const float* T, const float* diag, int B, int b, int col0, int soft_margin, float alpha, float margin,
+                                  float* rowsig, float* colsig, void* stream);
+int witw_exhaustive_loss_slab_bwd(const float* T, const float* diag, const float* rowsig, const float* colsig, const float* grad_loss,
+                                  float* G, int B, int b, int col0, int soft_margin, float alpha, float margin, void* stream);
+/* Backward of T = witw_pairwise_sqdist(x [B,n], y [b,n]) for any B, b >= 1, n <= 12288 (autograd of :307-308):
+ * dx[g] = 2 sum_c G[g][c] (x_g - y_c) [B,n], dy[c] = 2 sum_g G[g][c] (y_c - x_g) [b,n]; dx or dy may be NULL (not both).
+ * A workgroup keeps 8 (2 on a short side) output rows in registers against one read of the other side. */
+int witw_sqdist_rect_bwd(const float* x, const float* y, const float* G, float* dx, float* dy, int B, int b, int n, void* stream);
 
 /* ---- data path: Resize (:100-134), ImageNormalization (:137-149; semantic: cvig_semantic.py:167-176),
  *      PolarTransform (:156-209). NCHW fp32. mean/stdv: HOST arrays of C floats (NULL = resize only). */

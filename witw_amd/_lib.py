@@ -90,6 +90,10 @@ SIGNATURES = {
     'witw_gem_pool_bwd': (c_int, [c_void_p] * 6 + [c_int] * 8 + [c_float, c_int, c_void_p]),
     'witw_embed_normalize_bwd': (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p]),
     'witw_exhaustive_triplet_loss_bwd': (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_float, c_float, c_void_p, c_void_p]),
+    'witw_exhaustive_loss_slab_fwd': (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float, c_float] + [c_void_p] * 3),
+    'witw_exhaustive_loss_slab_sig': (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float, c_float] + [c_void_p] * 3),
+    'witw_exhaustive_loss_slab_bwd': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_float, c_float, c_void_p]),
+    'witw_sqdist_rect_bwd': (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     'witw_embed_normalize': (c_int, [c_void_p, c_int, c_int, c_void_p]),
     'witw_pairwise_sqdist': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'witw_row_sqnorm': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -9,6 +9,7 @@
 // pooling (:276-282), the final f/sqrt(|f|) (:284), squared-Euclidean distance matrix and the
 // exhaustive minibatch triplet loss (:286-315).
 #include "common.h"
+#include "exhaustive_terms.h"
 #include "sqdist_row.h"
 
 namespace {
@@ -190,10 +191,6 @@ __global__ __launch_bounds__(256) void pairwise_sqdist_kernel(const float* __res
     if (j >= Nb) return;
     const float s = witw_sqdist_row(arow, bm + (size_t)j * n, n);      // shared with the pair re-scoring of baseline_retrieval.hip
     D[(size_t)i * Nb + j] = take_sqrt ? sqrtf(s) : s;
-}
-
-__device__ __forceinline__ float trip(float x, int soft, float alpha, float margin) {
-    return soft ? logf(1.f + expf(alpha * x)) : fmaxf(x + margin, 0.f);
 }
 
 // part[i] = sum_{j != i} l(D_ii - D_ij) + l(D_ii - D_ji); D[i][j] = |e1_i - e2_j|^2
@@ -513,10 +510,6 @@ __global__ __launch_bounds__(256) void embed_normalize_bwd_kernel(const float* _
     const float nrm = sqrtf(nn);
     const float c0 = 1.f / sqrtf(nrm), c1 = 0.5f * gd / (nrm * nrm * sqrtf(nrm));
     for (int i = threadIdx.x; i < n; i += 256) dg[(size_t)blockIdx.x * n + i] = dr[i] * c0 - c1 * gr[i];
-}
-
-__device__ __forceinline__ float trip_d(float x, int soft, float alpha, float margin) {
-    return soft ? alpha / (1.f + expf(-alpha * x)) : ((x + margin > 0.f) ? 1.f : 0.f);
 }
 
 // G = dL/dD for the exhaustive loss; one block per row a (diagonal entry gathers the row and column terms).

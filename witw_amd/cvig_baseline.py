@@ -14,7 +14,7 @@ from . import _lib, ops
 from . import cvig_fov as _fov
 from .cvig_fov import Adam, recall_table  # noqa: F401  (same table, model/cvig_baseline.py:461-466)
 
-device = torch.device('cuda:0' if torch.cuda.is_available() else 'cpu')   # model/cvig_baseline.py:20
+device = _fov.device      # model/cvig_baseline.py:20 (cuda:0); under torch.distributed.run every process takes the GPU of its LOCAL_RANK
 device_parallel = False
 device_ids = None
 
@@ -378,6 +378,85 @@ def exhaustive_minibatch_triplet_loss(embed1, embed2, soft_margin=False, alpha=1
     return ops.exhaustive_triplet_loss(D, soft_margin, alpha, margin)
 
 
+def _slab_kernels():
+    from types import SimpleNamespace
+    from . import baseline_parallel as bp
+    return SimpleNamespace(pairwise_sqdist=ops.pairwise_sqdist, exhaustive_loss_slab_fwd=bp.exhaustive_loss_slab_fwd,
+                           exhaustive_loss_slab_sig=bp.exhaustive_loss_slab_sig, exhaustive_loss_slab_bwd=bp.exhaustive_loss_slab_bwd,
+                           sqdist_rect_bwd=bp.sqdist_rect_bwd)
+
+
+class _ShardedExhaustiveLossFn(torch.autograd.Function):
+    """exhaustive_minibatch_triplet_loss over the GLOBAL batch with the distance matrix sharded by COLUMNS over the ranks, shaped
+    like cvig_fov._ShardedMatchLossFn: rank r evaluates all B overhead embeddings against its own b surface embeddings (a [B,b]
+    slab of squared distances; the loss is symmetric in its two arguments, so which side is gathered is free). Exchanges:
+    forward = all-gather of the overhead embeddings and of the diagonal (B floats), all-reduce of the loss partial; backward =
+    all-reduce of the row sums of l' (B floats), reduce-scatter of the overhead-embedding gradients (every rank holds the part
+    that flows through ITS surfaces). The surface gradients are complete locally. One rank runs the same kernels on the one slab
+    b = B, col0 = 0, without a collective."""
+
+    @staticmethod
+    def forward(ctx, surface_local, overhead_local, soft_margin, alpha, margin, k):
+        from . import parallel
+        world = parallel.world()
+        y = surface_local.contiguous()
+        b = y.shape[0]
+        if overhead_local.shape != y.shape or y.dim() != 2:
+            raise _lib.WitwError('sharded_exhaustive_loss: need [b, n] embeddings of one shape, got %s and %s'
+                                 % (tuple(surface_local.shape), tuple(overhead_local.shape)))
+        if world > 1:
+            with parallel.phase('batch_share_all_gather'):       # decided on gathered data: every rank raises, none is left waiting
+                shares = parallel._all_gather_cat(torch.tensor([b], dtype=torch.int64, device=y.device)).tolist()
+            if len(set(shares)) != 1:
+                raise _lib.WitwError('sharded_exhaustive_loss: unequal batch shares across the ranks %s -- every rank must bring the '
+                                     'same number of pairs (train with drop_last)' % (shares,))
+            with parallel.phase('overhead_all_gather'):
+                x = parallel._all_gather_cat(overhead_local.contiguous())
+        else:
+            x = overhead_local.contiguous()
+        col0 = parallel.rank() * b
+        B = x.shape[0]
+        with parallel.phase('slab_distances'):
+            T = k.pairwise_sqdist(x, y)
+        own = T[col0:col0 + b].diagonal().contiguous()
+        if world > 1:
+            with parallel.phase('diagonal_all_gather'):
+                diag = parallel._all_gather_cat(own)
+        else:
+            diag = own
+        with parallel.phase('loss_partial_all_reduce'):
+            part = k.exhaustive_loss_slab_fwd(T, diag, col0, soft_margin, alpha, margin)
+            parallel.all_reduce_sum_(part)
+        ctx.save_for_backward(x, y, T, diag)
+        ctx.cfg = (col0, b, soft_margin, alpha, margin, k)
+        return (part / (2. * B * (B - 1))).reshape(())
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        from . import parallel
+        x, y, T, diag = ctx.saved_tensors
+        col0, b, soft_margin, alpha, margin, k = ctx.cfg
+        with parallel.phase('row_sums_all_reduce'):
+            rowsig, colsig = k.exhaustive_loss_slab_sig(T, diag, col0, soft_margin, alpha, margin)
+            parallel.all_reduce_sum_(rowsig)
+        with parallel.phase('slab_backward'):
+            G = k.exhaustive_loss_slab_bwd(T, diag, rowsig, colsig, g_loss.contiguous(), col0, soft_margin, alpha, margin)
+            dx, dy = k.sqdist_rect_bwd(x, y, G, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        if dx is not None:
+            with parallel.phase('overhead_grad_reduce_scatter'):
+                dx = parallel.reduce_scatter_rows(dx, b)
+        return dy, dx, None, None, None, None
+
+
+def sharded_exhaustive_loss(surface_local, overhead_local, soft_margin=False, alpha=10., margin=1., _kernels=None):
+    """exhaustive_minibatch_triplet_loss (model/cvig_baseline.py:286-315) of the GLOBAL batch from this rank's b pairs: what the
+    reference computes on the embeddings gathered from its nn.DataParallel replicas (:339-343), normaliser 2B(B-1) with the global
+    B. Every rank must call it with the same b (else a WitwError, on every rank). Differentiable; identical on every rank. With no
+    process group it is the same slab path at b = B. `_kernels` swaps the op set (CPU tests of the collective algebra)."""
+    return _ShardedExhaustiveLossFn.apply(surface_local, overhead_local, bool(soft_margin), float(alpha), float(margin),
+                                          _kernels or _slab_kernels())
+
+
 def ranks(overhead_embed, surface_embed):
     """model/cvig_baseline.py:454-460: Euclidean distances, rank = #{gallery : d <= d_true}."""
     D = ops.pairwise_sqdist(overhead_embed.contiguous(), surface_embed.contiguous(), take_sqrt=True)   # [gallery, query]
@@ -603,56 +682,134 @@ def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, meth
 
 
 # ----------------------------------------------------------------------------- drivers
-def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_epochs=999999, csv_path=None):
+class GlobalBatchShares(object):
+    """batch_sampler of the sharded validation phase: the n items go in order into global batches of `batch_size` (the last one
+    ragged), exactly the batches of DataLoader(shuffle=False, drop_last=False), and this rank takes its contiguous
+    parallel.shard_range share of each -- possibly none. parallel.all_gather_ragged of the ranks' shares is the global batch, in
+    order; no item is padded in or repeated, as a DistributedSampler would."""
+
+    def __init__(self, n, batch_size, rank, world):
+        self.n, self.batch_size, self.rank, self.world = int(n), int(batch_size), int(rank), int(world)
+
+    def __iter__(self):
+        from . import parallel
+        for i0 in range(0, self.n, self.batch_size):
+            lo, hi = parallel.shard_range(min(self.batch_size, self.n - i0), self.rank, self.world)
+            yield list(range(i0 + lo, i0 + hi))
+
+    def __len__(self):
+        return (self.n + self.batch_size - 1) // self.batch_size
+
+
+def _embed_share(prep, surface_encoder, overhead_encoder, raw):
+    """eval-mode embeddings of this rank's share of a batch; an empty share gives [0, 1536] tensors"""
+    if not raw['surface']:
+        return torch.zeros((0, 1536), dtype=torch.float32, device=device), torch.zeros((0, 1536), dtype=torch.float32, device=device)
+    data = prep(raw)
+    with torch.no_grad():
+        return surface_encoder(data['surface']), overhead_encoder(data['overhead'])
+
+
+def _bn_modules(*encoders):
+    return [getattr(e, 'bn%d' % i) for e in encoders for i in range(1, 8)]
+
+
+def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_epochs=999999, csv_path=None, seed=0):
     """model/cvig_baseline.py:318-404 on the HIP kernels: same flow, prints and checkpoint names; Adam with torch's
-    defaults (lr 1e-3) over every encoder parameter. Single GPU: the reference's optional nn.DataParallel (:338-342)
-    would change the BatchNorm statistics per replica and is not reproduced."""
+    defaults (lr 1e-3) over every encoder parameter.
+    Under an initialised process group (N ranks, one per GPU) it is the reference's nn.DataParallel run (:339-343) with a rank in
+    the place of each replica: `batch_size` stays the GLOBAL batch (N must divide it), every rank draws batch_size / N pairs of each
+    step from a DistributedSampler and normalises them with its OWN batch statistics, as a replica does; the loss couples the
+    global batch (sharded_exhaustive_loss), the weight gradients are summed (parallel.OverlappedGradReducer). The running
+    statistics that count are rank 0's (parallel.broadcast_buffers before every validation phase and before saving). Validation
+    embeds each global batch in contiguous shares and evaluates the dense loss on the gathered batch, so its numbers are those of
+    the one-process loop on the same split. Rank 0 prints and saves. `seed` fixes the train / validation split, which every rank
+    must draw alike; it is not used on one rank."""
     import pathlib
     import time
+    from . import parallel
+    world, rank = parallel.world(), parallel.rank()
+    if world > 1 and batch_size % world:
+        raise _lib.WitwError('train: the global batch_size %d is not a multiple of the %d ranks' % (batch_size, world))
+    if world > 1 and device.type == 'cuda':
+        torch.cuda.set_device(device)
     pathlib.Path('./weights').mkdir(parents=True, exist_ok=True)
     csv_path = csv_path or Globals.dataset_paths[dataset]['train']
     prep = GpuPreprocess(dataset)
     trainval_set = ImagePairDataset(dataset=dataset, csv_path=csv_path)
-    train_set, val_set = torch.utils.data.random_split(trainval_set, [len(trainval_set) - val_quantity, val_quantity])
-    train_loader = torch.utils.data.DataLoader(train_set, batch_size=batch_size, shuffle=True, drop_last=True,
-                                               num_workers=num_workers, collate_fn=_fov.collate_raw)
-    val_loader = torch.utils.data.DataLoader(val_set, batch_size=batch_size, shuffle=False, drop_last=False,
-                                             num_workers=num_workers, collate_fn=_fov.collate_raw)
+    split_gen = torch.Generator().manual_seed(seed) if world > 1 else None      # every rank must draw the same split
+    train_set, val_set = torch.utils.data.random_split(trainval_set, [len(trainval_set) - val_quantity, val_quantity],
+                                                       generator=split_gen)
+    if world > 1:
+        train_sampler = torch.utils.data.distributed.DistributedSampler(train_set, shuffle=True, drop_last=True)
+        train_loader = torch.utils.data.DataLoader(train_set, batch_size=batch_size // world, sampler=train_sampler, drop_last=True,
+                                                   num_workers=num_workers, collate_fn=_fov.collate_raw)
+        val_loader = torch.utils.data.DataLoader(val_set, batch_sampler=GlobalBatchShares(len(val_set), batch_size, rank, world),
+                                                 num_workers=num_workers, collate_fn=_fov.collate_raw)
+    else:
+        train_sampler = None
+        train_loader = torch.utils.data.DataLoader(train_set, batch_size=batch_size, shuffle=True, drop_last=True,
+                                                   num_workers=num_workers, collate_fn=_fov.collate_raw)
+        val_loader = torch.utils.data.DataLoader(val_set, batch_size=batch_size, shuffle=False, drop_last=False,
+                                                 num_workers=num_workers, collate_fn=_fov.collate_raw)
     surface_encoder = SurfaceEncoder().to(device)
     overhead_encoder = OverheadEncoder().to(device)
-    loss_func = exhaustive_minibatch_triplet_loss
+    encoders = [surface_encoder, overhead_encoder]
+    parallel.broadcast_parameters(encoders)
+    loss_func = sharded_exhaustive_loss if world > 1 else exhaustive_minibatch_triplet_loss
     optimizer = Adam(list(surface_encoder.parameters()) + list(overhead_encoder.parameters()))
+    reducer = parallel.OverlappedGradReducer(encoders) if world > 1 else None      # SUM: the loss is normalised by the global batch
+
+    def say(*a):
+        if rank == 0:
+            print(*a)
 
     best_loss = None
     for epoch in range(num_epochs):
-        print('Epoch %d, %s' % (epoch + 1, time.ctime(time.time())))
+        say('Epoch %d, %s' % (epoch + 1, time.ctime(time.time())))
+        if train_sampler is not None:
+            train_sampler.set_epoch(epoch)
         for phase in ['train', 'val']:
             running_count = 0
             running_loss = 0.
             loader = train_loader if phase == 'train' else val_loader
             surface_encoder.train(phase == 'train')
             overhead_encoder.train(phase == 'train')
+            if phase == 'val':
+                parallel.broadcast_buffers(_bn_modules(*encoders))      # the first replica's running statistics
             for batch, raw in enumerate(loader):
-                data = prep(raw)
-                with torch.set_grad_enabled(phase == 'train'):
-                    surface_embed = surface_encoder(data['surface'])
-                    overhead_embed = overhead_encoder(data['overhead'])
-                    loss = loss_func(surface_embed, overhead_embed)
-                    if phase == 'train':
-                        optimizer.zero_grad()
-                        loss.backward()
-                        optimizer.step()
-                count = surface_embed.size(0)
+                if phase == 'val' and world > 1:
+                    su, ov = _embed_share(prep, surface_encoder, overhead_encoder, raw)
+                    surface_embed, overhead_embed = parallel.all_gather_ragged(su), parallel.all_gather_ragged(ov)
+                    with torch.no_grad():
+                        loss = exhaustive_minibatch_triplet_loss(surface_embed, overhead_embed)
+                    count = surface_embed.size(0)
+                else:
+                    data = prep(raw)
+                    with torch.set_grad_enabled(phase == 'train'):
+                        surface_embed = surface_encoder(data['surface'])
+                        overhead_embed = overhead_encoder(data['overhead'])
+                        loss = loss_func(surface_embed, overhead_embed)
+                        if phase == 'train':
+                            optimizer.zero_grad()
+                            loss.backward()
+                            if reducer is not None:
+                                reducer.wait()
+                            optimizer.step()
+                    count = surface_embed.size(0) * (world if phase == 'train' else 1)
                 running_count += count
                 running_loss += loss.item() * count
-                print('epoch = {} {}, iter = {}, count = {}, loss = {:.4f}'.format(epoch + 1, phase, batch, running_count,
-                                                                                 loss.item()))
-            print('  %5s: avg loss = %f' % (phase, running_loss / max(1, running_count)))
+                say('epoch = {} {}, iter = {}, count = {}, loss = {:.4f}'.format(epoch + 1, phase, batch, running_count,
+                                                                                loss.item()))
+            say('  %5s: avg loss = %f' % (phase, running_loss / max(1, running_count)))
         if running_count and (best_loss is None or running_loss / running_count < best_loss):
-            print('-------> new best')
+            say('-------> new best')
             best_loss = running_loss / running_count
-            torch.save(surface_encoder.state_dict(), './weights/surface_best.pth')
-            torch.save(overhead_encoder.state_dict(), './weights/overhead_best.pth')
+            if rank == 0:      # the running statistics are rank 0's own: nothing has trained since the broadcast before validation
+                torch.save(surface_encoder.state_dict(), './weights/surface_best.pth')
+                torch.save(overhead_encoder.state_dict(), './weights/overhead_best.pth')
+    if reducer is not None:
+        reducer.close()
     return best_loss
 
 
@@ -660,11 +817,20 @@ def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_met
     """model/cvig_baseline.py:405-475: embed the test set (SyncedRotation stays on, as in the reference :410-414),
     rank every query against the whole gallery on the GPU, print the recall table. match_method: None = ranks() (one dense
     matrix, at most 65,535 pairs); 'direct', 'gemm' or 'auto' = evaluation_ranks(method=...): the same ranks from the chunked
-    pass, 'gemm' at GEMM cost with exact re-scoring (retrieve)."""
+    pass, 'gemm' at GEMM cost with exact re-scoring (retrieve).
+    Under an initialised process group every rank embeds a contiguous share of the test set and keeps its gallery rows; the
+    queries are gathered and the rank counts summed inside evaluation_ranks, rank 0 prints. None then means 'auto': the dense
+    ranks() cannot be sharded."""
+    from . import parallel
+    world, rank = parallel.world(), parallel.rank()
+    if world > 1 and device.type == 'cuda':
+        torch.cuda.set_device(device)
     csv_path = csv_path or Globals.dataset_paths[dataset]['test']
     prep = GpuPreprocess(dataset)
     test_set = ImagePairDataset(dataset=dataset, csv_path=csv_path)
-    test_loader = torch.utils.data.DataLoader(test_set, batch_size=batch_size, shuffle=False, drop_last=False,
+    shard_begin, shard_end = parallel.shard_range(len(test_set))
+    shard = torch.utils.data.Subset(test_set, range(shard_begin, shard_end)) if world > 1 else test_set
+    test_loader = torch.utils.data.DataLoader(shard, batch_size=batch_size, shuffle=False, drop_last=False,
                                               num_workers=num_workers, collate_fn=_fov.collate_raw)
     surface_encoder = SurfaceEncoder().to(device)
     overhead_encoder = OverheadEncoder().to(device)
@@ -674,13 +840,21 @@ def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_met
     overhead_encoder.eval()
     su_parts, ov_parts = [], []
     for raw in test_loader:
-        data = prep(raw)
-        with torch.no_grad():
-            su_parts.append(surface_encoder(data['surface']))
-            ov_parts.append(overhead_encoder(data['overhead']))
+        su, ov = _embed_share(prep, surface_encoder, overhead_encoder, raw)
+        su_parts.append(su)
+        ov_parts.append(ov)
+    if world > 1 and not su_parts:      # a rank without rows (more ranks than items) still joins the collectives
+        su, ov = _embed_share(prep, surface_encoder, overhead_encoder, {'surface': []})
+        su_parts.append(su)
+        ov_parts.append(ov)
     ov_all, su_all = torch.cat(ov_parts, dim=0), torch.cat(su_parts, dim=0)
-    rk = ranks(ov_all, su_all) if match_method is None else evaluation_ranks(ov_all, su_all, method=match_method)
+    if world > 1:
+        rk = evaluation_ranks(ov_all, su_all, shard_begin, world, method=match_method or 'auto')
+    else:
+        rk = ranks(ov_all, su_all) if match_method is None else evaluation_ranks(ov_all, su_all, method=match_method)
     t = recall_table(rk)
+    if rank != 0:
+        return t
     print('Top  1: {:.2f}%'.format(t['top_1']))
     print('Top  5: {:.2f}%'.format(t['top_5']))
     print('Top 10: {:.2f}%'.format(t['top_10']))
@@ -702,6 +876,7 @@ def main(argv=None):
                              "distance GEMM with exact re-scoring (the same ranks), 'auto' = 'gemm' for large test sets. [Default = one dense "
                              "matrix, at most 65,535 pairs]")
     args = parser.parse_args(argv)
+    _fov.init_distributed()       # under `python -m torch.distributed.run --nproc-per-node N`: one process per GPU; else nothing
     if args.mode == 'train':
         train(dataset=args.dataset)
     elif args.mode == 'test':

@@ -12,6 +12,9 @@ model/cvig_baseline.py:339-343; normaliser 2B(B-1) with B = global batch, model/
   3. weight gradients (57.9 MB for both encoders) are summed with one all-reduce over a flat bucket.
 Retrieval (gallery >> queries) shards the gallery rows instead: rank counts are summed with an
 all-reduce of int32[queries].
+cvig_baseline's encoders DO have BatchNorm: there a rank stands for an nn.DataParallel replica -- batch statistics per rank, never
+synchronised, rank 0's running statistics kept (broadcast_buffers); its loss couples the global batch the same way
+(cvig_baseline.sharded_exhaustive_loss).
 
 Everything here is backend-agnostic host logic (tested on CPU with gloo, world_size 2).
 """
@@ -337,6 +340,20 @@ def broadcast_parameters(modules, src=0):
     for m in modules:
         for t in list(m.parameters()) + list(m.buffers()):
             dist.broadcast(t.data, src)
+
+
+def broadcast_buffers(modules, src=0):
+    """Make every rank hold rank `src`'s BUFFERS (the running statistics and batch counters of BatchNorm layers). Under
+    nn.DataParallel the statistics that survive a step are those of the replica on the first device -- the buffers are the wrapped
+    module's own, the other replicas' updates are discarded (model/cvig_baseline.py:339-343) -- so a rank-per-GPU run takes rank
+    0's before it evaluates or saves. The broadcast writes through .data, which torch's version counter does not see:
+    _witw_version is bumped, as the C-ABI updates do, so that anything folded from a buffer is rebuilt."""
+    if world() == 1:
+        return
+    for m in modules:
+        for t in m.buffers():
+            dist.broadcast(t.data, src)
+            t._witw_version = getattr(t, '_witw_version', 0) + 1
 
 
 def shard_range(n, r=None, n_ranks=None):
