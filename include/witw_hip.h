@@ -94,7 +94,16 @@ int witw_conv3x3_first_fwd(const float* x, const float* wf, const float* bias, v
  * H is the dilated height) — the data gradient of a stride-(2,1) conv is then this same kernel on the
  * transpose_flip filter (autograd of torch.nn.Conv2d at model/cvig_fov.py:460). relu: 0 none, 1 ReLU,
  * 2 LeakyReLU(lrelu_slope); post_scale/post_shift (NULL or [Cout]): per-channel affine after the activation
- * (eval-mode BatchNorm2d of model/cvig_baseline.py:267-275). */
+ * (eval-mode BatchNorm2d of model/cvig_baseline.py:267-275).
+ *
+ * Epilogue contract of the unpooled launch, shared by witw_conv3x3_bf16_fwd_ex and witw_conv3x3_f16x3_fwd_ex (which have no
+ * LeakyReLU / affine), as tested bit for bit by tests/test_conv_epilogue_gpu.py against tests/conv_epilogue_ref.py:
+ *   - order: conv + bias -> Dropout2d scale (dropmask[b][c]) -> activation -> post affine -> gate;
+ *   - the gate is a SELECT, open exactly where gate > 0 (for a split-fp16 gate: where its hi half is): +0.0, -0.0, negative values
+ *     and NaN close it, the smallest positive subnormal and +inf open it;
+ *   - a closed output is +0.0 (all bits zero), also where the value was negative, scaled by 0, infinite or NaN; an open output is
+ *     the value, unchanged;
+ *   - the gate is indexed like y: NCHW under out_nchw, NHWC otherwise. */
 int witw_conv3x3_fwd_ex(const float* x, const float* wpk, const float* bias, const float* dropmask, const float* gate,
                         const float* post_scale, const float* post_shift, float* y, unsigned char* pool_code, int B, int H,
                         int W, int Cin, int Cout, int stride_h, int pad_circular, int relu, float lrelu_slope, int pool,
@@ -371,7 +380,8 @@ int witw_split_f16_to_f32(const void* x_split, float* y /*[pixels][C]*/, long lo
 int witw_conv3x3_f16x3_fwd(const void* x_split, const void* wpk_f16, const float* bias, void* y, int B, int H, int W, int Cin,
                            int Cout, int stride_h, int pad_circular, int relu, int pool, int out_nchw_f32, void* stream);
 /* training forms, as witw_conv3x3_bf16_fwd_ex / witw_conv3x3_bf16_pack_weights_ex: Dropout2d scale, ReLU gate (a split-fp16
- * tensor shaped like y), zero-interleaved rows; transpose_flip packs the dgrad filter of the source [cin][cout][3][3] */
+ * tensor shaped like y; the epilogue contract at witw_conv3x3_fwd_ex, the gate's sign read from its hi half; tests/
+ * test_conv_epilogue_gpu.py), zero-interleaved rows; transpose_flip packs the dgrad filter of the source [cin][cout][3][3] */
 int witw_conv3x3_f16x3_pack_weights_ex(const float* w_kcrs, void* wpk_f16, int cout, int cin, int transpose_flip, void* stream);
 int witw_conv3x3_f16x3_fwd_ex(const void* x_split, const void* wpk_f16, const float* bias, const float* dropmask,
                               const void* gate_split, void* y, unsigned char* pool_code, int* overflow_flag, int B, int H, int W,
@@ -400,7 +410,9 @@ int witw_conv3x3_wgrad_f16x3(const void* x_oct, const void* dz_oct, const void* 
  * backward of a dgrad launch, which is this kernel on witw_conv3x3_bf16_pack_weights of the transposed, tap-rotated
  * filter); dilate_h = x holds (H-1)/2+1 physical rows standing for H zero-interleaved rows (dgrad of a stride-(2,1) layer);
  * pool_code = NULL or uint8 [B,Hy,Wy,Cout]: arg-max position (dy*2+dx) of the fused max-pool, consumed by
- * witw_maxpool2x2_bwd_bf16 (dy bf16 [B,Hp,Wp,C] -> dx bf16 [B,H,W,C]). */
+ * witw_maxpool2x2_bwd_bf16 (dy bf16 [B,Hp,Wp,C] -> dx bf16 [B,H,W,C]). Order of the epilogue and the gate: the contract stated
+ * at witw_conv3x3_fwd_ex (open exactly where the bf16 gate is > 0, NaN closes it, a closed output is +0.0), tests/
+ * test_conv_epilogue_gpu.py. */
 int witw_conv3x3_bf16_fwd_ex(const void* x_bf16, const void* wpk_bf16, const float* bias, const float* dropmask,
                              const void* gate_bf16, void* y, unsigned char* pool_code, int B, int H, int W, int Cin, int Cout,
                              int stride_h, int pad_circular, int relu, int pool, int out_nchw_f32, int dilate_h, void* stream);

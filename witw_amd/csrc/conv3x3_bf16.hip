@@ -309,7 +309,8 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_bf16_kernel(ConvBfArgs p
         if (p.relu) v = fmaxf(v, 0.f);
         return v;
     };
-    auto gate_open = [](unsigned short g) { return (g & 0x7fffu) != 0 && !(g & 0x8000u); };   // bf16 value > 0
+    // bf16 value > 0, as the fp32 kernel's `gate > 0.f` (include/witw_hip.h, witw_conv3x3_fwd_ex): +-0.0, negatives and NaN close it
+    auto gate_open = [](unsigned short g) { return (unsigned short)(g - 1u) < 0x7f80u; };
     const int Hy = POOL ? (p.Ho >> 1) : p.Ho;
     const int Wy = POOL ? (p.Wo >> 1) : p.Wo;
     auto emit = [&](float v, int nt, int yy, int xx) {
@@ -742,7 +743,7 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_s16_kernel(ConvBfArgs p) {
                 if (TRAIN && p.gate != nullptr) {      // zero where the forward's output was <= 0
 #pragma unroll
                     for (int e = 0; e < 8; ++e)
-                        if ((gt[g][e] & 0x7fffu) == 0 || (gt[g][e] & 0x8000u)) o[e] = (__bf16)0.f;
+                        if (!((unsigned short)(gt[g][e] - 1u) < 0x7f80u)) o[e] = (__bf16)0.f;      // open on 0 < gate <= inf: a NaN closes it
                 }
                 __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(reinterpret_cast<__bf16*>(p.y) + off));
             }

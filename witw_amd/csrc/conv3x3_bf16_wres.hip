@@ -232,8 +232,8 @@ __global__ __launch_bounds__(WRT, 1) void conv3x3_bf16_wres_kernel(WresArgs p) {
         return (((byte >> (2 * e)) & 1u) ? 0x0000ffffu : 0u) | (((byte >> (2 * e + 1)) & 1u) ? 0xffff0000u : 0u);
     };
     auto gate_mask = [](unsigned w) -> unsigned {      // 0xffff per bf16 half that is > 0 (conv3x3_bf16.hip: gate_open)
-        const unsigned lo = ((w & 0x7fffu) != 0u && !(w & 0x8000u)) ? 0x0000ffffu : 0u;
-        const unsigned hi = ((w & 0x7fff0000u) != 0u && !(w & 0x80000000u)) ? 0xffff0000u : 0u;
+        const unsigned lo = (((w & 0xffffu) - 1u) < 0x7f80u) ? 0x0000ffffu : 0u;      // 0 < half <= inf: a NaN closes it, as `gate > 0.f`
+        const unsigned hi = (((w >> 16) - 1u) < 0x7f80u) ? 0xffff0000u : 0u;
         return lo | hi;
     };
     int pb = 0, poy0 = 0, pox0 = 0;                 // the tile whose accumulators are waiting for their epilogue

@@ -270,7 +270,8 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_f16x3_kernel(ConvHxArgs 
     };
     // a split-fp16 value is > 0 iff its hi part is (lo only refines it; hi = 0 means the value itself was 0 or tiny positive:
     // a saved ReLU output below the smallest fp16 subnormal counts as closed, like an exact zero)
-    auto gate_open = [](unsigned short g) { return (g & 0x7fffu) != 0 && !(g & 0x8000u); };
+    // open on 0 < hi <= inf, as the fp32 kernel's `gate > 0.f` (include/witw_hip.h, witw_conv3x3_fwd_ex): +-0.0, negatives and NaN close it
+    auto gate_open = [](unsigned short g) { return (unsigned short)(g - 1u) < 0x7c00u; };
     const int Hy = POOL ? (p.Ho >> 1) : p.Ho;
     const int Wy = POOL ? (p.Wo >> 1) : p.Wo;
     _Float16* const yh = reinterpret_cast<_Float16*>(p.y);
