@@ -562,6 +562,37 @@ int witw_exhaustive_loss_slab_bwd(const float* T, const float* diag, const float
  * dx[g] = 2 sum_c G[g][c] (x_g - y_c) [B,n], dy[c] = 2 sum_g G[g][c] (y_c - x_g) [b,n]; dx or dy may be NULL (not both).
  * A workgroup keeps 8 (2 on a short side) output rows in registers against one read of the other side. */
 int witw_sqdist_rect_bwd(const float* x, const float* y, const float* G, float* dx, float* dy, int B, int b, int n, void* stream);
+/* Batch-hard form of the same loss on the same column slab (opt-in, not in the reference; Hermans et al. 2017): every anchor against
+ * its hardest negative of the GLOBAL batch only. With Tm = T whose global diagonal is +inf: rv/ri [B] = minimum / argmin of every
+ * global row of Tm, cv/ci [b] = of every column of the slab, mined by witw_batch_hard_slab_mine(T, B, b, col0) and, over the ranks,
+ * witw_batch_hard_merge_rows (their selection rule; int64 global indices, constants for the gradient). d_k = the global diagonal,
+ * l and l' as above (l'(x) = [x + margin > 0] for the hard margin; a NaN argument stays a NaN in l).
+ *   loss = (sum_i l(d_i - rv[i]) + sum_j l(d_j - cv[j])) / 2B
+ *   sc = grad_loss / 2B, w_r[i] = sc l'(d_i - rv[i]), w_c[j] = sc l'(d_j - cv[j]);  dL/dT = +w_r[i] + w_c[i] at (i, i),
+ *   -w_r[i] at (i, ri[i]), -w_c[j] at (ci[j], j): at most 3B non-zeros, never built as a matrix.
+ * B >= 2, 1 <= b, 0 <= col0, col0 + b <= B; no pointer may be NULL. Fixed-order sums, no atomics: a call repeated gives the same bits.
+ * _slab_loss: partial[0] = sum over the slab's columns c, k = col0 + c, of l(T[k][c] - rv[k]) + l(T[k][c] - cv[c]) (the row terms of
+ *       the anchors the slab owns, rv the GLOBAL row minima, + the column terms of its columns), un-normalised: the caller sums the
+ *       ranks' partials and divides by 2B.
+ * _pairs: the non-zeros of dL/dT that lie in the slab's columns, 2b + B entries laid out as witw_batch_hard_pairs lays them out:
+ *       [0, b) the diagonal (col0 + j, j, +w_r[col0+j] + w_c[j]); [b, 2b) (ci[j], j, -w_c[j]); [2b, 2b + B) (i, ri[i] - col0, -w_r[i])
+ *       when the slab holds column ri[i]. (-1, -1, 0) where it does not, or where the mined index is -1. pair_g = global row,
+ *       pair_c = LOCAL column, pair_w includes grad_loss (device scalar); diag [B] = the global diagonal. */
+int witw_baseline_hard_slab_loss(const float* T, const float* rv, const float* cv, int B, int b, int col0, int soft_margin, float alpha,
+                                 float margin, float* partial, void* stream);
+int witw_baseline_hard_pairs(const float* diag, const float* rv, const long long* ri, const float* cv, const long long* ci,
+                             const float* grad_loss, int B, int b, int col0, int soft_margin, float alpha, float margin, int* pair_g,
+                             int* pair_c, float* pair_w, void* stream);
+/* Backward of T = witw_pairwise_sqdist(x [B,n], y [b,n]) for dL/dT given as a list of P >= 0 pairs (dL/dT[g][c] = the sum of pair_w
+ * over the pairs (g, c); duplicates add up, an entry with g outside [0,B) or c outside [0,b) is skipped), any B, b >= 1,
+ * 1 <= n <= 12288: a pair adds 2w (x_g - y_c) to dx[g] [B,n] and 2w (y_c - x_g) to dy[c] [b,n]. dx or dy may be NULL (not both);
+ * every row of a non-NULL output is written, rows without a pair as zeros. A workgroup per output row and 256 columns scans the
+ * list and sums its row's pairs in list order: no atomics, bitwise reproducible, and a row that is the partner of every pair is
+ * one workgroup's P row reads. workspace: witw_sqdist_pairs_bwd_workspace_bytes(B, b, P) bytes (-1 for a bad shape; this form
+ * needs none and answers 0, workspace may then be NULL). */
+long long witw_sqdist_pairs_bwd_workspace_bytes(int B, int b, int P);
+int witw_sqdist_pairs_bwd(const float* x, const float* y, const int* pair_g, const int* pair_c, const float* pair_w, int P, float* dx,
+                          float* dy, int B, int b, int n, void* workspace, void* stream);
 
 /* ---- data path: Resize (:100-134), ImageNormalization (:137-149; semantic: cvig_semantic.py:167-176),
  *      PolarTransform (:156-209). NCHW fp32. mean/stdv: HOST arrays of C floats (NULL = resize only). */

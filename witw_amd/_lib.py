@@ -94,6 +94,10 @@ SIGNATURES = {
     'witw_exhaustive_loss_slab_sig': (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float, c_float] + [c_void_p] * 3),
     'witw_exhaustive_loss_slab_bwd': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_float, c_float, c_void_p]),
     'witw_sqdist_rect_bwd': (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
+    'witw_baseline_hard_slab_loss': (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float, c_float, c_void_p, c_void_p]),
+    'witw_baseline_hard_pairs': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_float, c_float] + [c_void_p] * 4),
+    'witw_sqdist_pairs_bwd_workspace_bytes': (c_longlong, [c_int] * 3),
+    'witw_sqdist_pairs_bwd': (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2),
     'witw_embed_normalize': (c_int, [c_void_p, c_int, c_int, c_void_p]),
     'witw_pairwise_sqdist': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'witw_row_sqnorm': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -457,6 +457,108 @@ def sharded_exhaustive_loss(surface_local, overhead_local, soft_margin=False, al
                                           _kernels or _slab_kernels())
 
 
+LOSSES = ('exhaustive', 'batch_hard')      # train(loss=...) / --loss
+
+
+def _hard_kernels():
+    from types import SimpleNamespace
+    from . import baseline_hard as bh
+    return SimpleNamespace(pairwise_sqdist=ops.pairwise_sqdist, batch_hard_slab_mine=ops.batch_hard_slab_mine,
+                           batch_hard_merge_rows=ops.batch_hard_merge_rows, hard_slab_loss=bh.hard_slab_loss, hard_pairs=bh.hard_pairs,
+                           sqdist_pairs_bwd=bh.sqdist_pairs_bwd)
+
+
+class _ShardedBatchHardLossFn(torch.autograd.Function):
+    """The batch-hard form of the loss over the GLOBAL batch on the column slabs of _ShardedExhaustiveLossFn: every anchor against
+    its hardest negative only (minimum of its row / column of T with the diagonal masked; the mined indices are constants for the
+    gradient). Exchanges: forward = all-gather of the overhead embeddings, of the diagonal (B floats) and of the per-rank row minima
+    ([w,B] values + global column indices, merged in rank order: the lowest index wins a tie), all-reduce of the loss partial (each
+    rank: the row terms of the anchors it owns + the column terms of its columns); backward = the at most 3b + B non-zeros of dL/dT in
+    this rank's columns as a pair list through the pair-list backward of the distances (no dense [B,b] gradient), then the
+    reduce-scatter of the overhead-embedding gradients. The surface gradients are complete locally. One rank runs the same kernels
+    on the one slab b = B, col0 = 0, without a collective.
+    Outputs: loss, and the mined (rv [B], ri [B]) of every overhead anchor and (cv [b], ci [b]) of this rank's surface anchors."""
+
+    @staticmethod
+    def forward(ctx, surface_local, overhead_local, soft_margin, alpha, margin, k, sharded):
+        from . import parallel
+        world, rank = (parallel.world(), parallel.rank()) if sharded else (1, 0)      # not sharded: one slab, whatever group there is
+        y = surface_local.contiguous()
+        b = y.shape[0]
+        if overhead_local.shape != y.shape or y.dim() != 2:
+            raise _lib.WitwError('sharded_batch_hard_loss: need [b, n] embeddings of one shape, got %s and %s'
+                                 % (tuple(surface_local.shape), tuple(overhead_local.shape)))
+        if world > 1:
+            with parallel.phase('batch_share_all_gather'):       # decided on gathered data: every rank raises, none is left waiting
+                shares = parallel._all_gather_cat(torch.tensor([b], dtype=torch.int64, device=y.device)).tolist()
+            if len(set(shares)) != 1:
+                raise _lib.WitwError('sharded_batch_hard_loss: unequal batch shares across the ranks %s -- every rank must bring the '
+                                     'same number of pairs (train with drop_last)' % (shares,))
+            with parallel.phase('overhead_all_gather'):
+                x = parallel._all_gather_cat(overhead_local.contiguous())
+        else:
+            x = overhead_local.contiguous()
+        col0 = rank * b
+        B = x.shape[0]
+        if B < 2:
+            raise _lib.WitwError('sharded_batch_hard_loss: batch %d < 2 (every anchor needs a negative)' % B)
+        with parallel.phase('slab_distances'):
+            T = k.pairwise_sqdist(x, y)
+        own = T[col0:col0 + b].diagonal().contiguous()
+        if world > 1:
+            with parallel.phase('diagonal_all_gather'):
+                diag = parallel._all_gather_cat(own)
+        else:
+            diag = own
+        with parallel.phase('row_minima_all_gather'):
+            rv, ri, cv, ci = k.batch_hard_slab_mine(T, col0)
+            if world > 1:
+                rv, ri = k.batch_hard_merge_rows(parallel._all_gather_cat(rv[None]), parallel._all_gather_cat(ri[None]))
+        with parallel.phase('loss_partial_all_reduce'):
+            part = k.hard_slab_loss(T, rv, cv, col0, soft_margin, alpha, margin)
+            if world > 1:
+                parallel.all_reduce_sum_(part)
+        ctx.save_for_backward(x, y, diag, rv, ri, cv, ci)
+        ctx.cfg = (col0, b, world, soft_margin, alpha, margin, k)
+        ctx.mark_non_differentiable(rv, ri, cv, ci)
+        ctx.set_materialize_grads(False)      # no zero gradients for the four non-differentiable outputs
+        return (part / (2. * B)).reshape(()), rv, ri, cv, ci
+
+    @staticmethod
+    def backward(ctx, g_loss, *_g):
+        from . import parallel
+        if g_loss is None:
+            return None, None, None, None, None, None, None
+        x, y, diag, rv, ri, cv, ci = ctx.saved_tensors
+        col0, b, world, soft_margin, alpha, margin, k = ctx.cfg
+        with parallel.phase('slab_backward'):
+            pg, pc, pw = k.hard_pairs(diag, rv, ri, cv, ci, g_loss.contiguous(), col0, soft_margin, alpha, margin)
+            dx, dy = k.sqdist_pairs_bwd(x, y, pg, pc, pw, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        if dx is not None and world > 1:
+            with parallel.phase('overhead_grad_reduce_scatter'):
+                dx = parallel.reduce_scatter_rows(dx, b)
+        return dy, dx, None, None, None, None, None
+
+
+def sharded_batch_hard_loss(surface_local, overhead_local, soft_margin=False, alpha=10., margin=1., mined=False, _kernels=None):
+    """The batch-hard triplet loss of the GLOBAL batch from this rank's b pairs (not in the reference; Hermans et al. 2017 on the
+    baseline's squared distances and its two margin forms): (sum_i l(d_i - min_{j != i} T_ij) + sum_j l(d_j - min_{i != j} T_ij)) / 2B
+    with the global B >= 2, l as in exhaustive_minibatch_triplet_loss. Every rank must call it with the same b (else a WitwError, on
+    every rank). Differentiable; identical on every rank. With no process group it is the same slab path at b = B. mined=True
+    appends the mined (rv [B], ri [B], cv [b], ci [b]) of the global rows and this rank's columns (global int64 indices; a NaN is
+    the minimum at the first NaN's index, else ties go to the lowest index). `_kernels` swaps the op set (CPU tests of the
+    collective algebra)."""
+    out = _ShardedBatchHardLossFn.apply(surface_local, overhead_local, bool(soft_margin), float(alpha), float(margin),
+                                        _kernels or _hard_kernels(), True)
+    return out if mined else out[0]
+
+
+def batch_hard_triplet_loss(embed1, embed2, soft_margin=False, alpha=10., margin=1.):
+    """exhaustive_minibatch_triplet_loss with every anchor against its hardest negative of the minibatch only, on one rank:
+    the kernels of sharded_batch_hard_loss on the one slab b = B, whatever process group there is. Differentiable in both arguments."""
+    return _ShardedBatchHardLossFn.apply(embed1, embed2, bool(soft_margin), float(alpha), float(margin), _hard_kernels(), False)[0]
+
+
 def ranks(overhead_embed, surface_embed):
     """model/cvig_baseline.py:454-460: Euclidean distances, rank = #{gallery : d <= d_true}."""
     D = ops.pairwise_sqdist(overhead_embed.contiguous(), surface_embed.contiguous(), take_sqrt=True)   # [gallery, query]
@@ -714,7 +816,7 @@ def _bn_modules(*encoders):
     return [getattr(e, 'bn%d' % i) for e in encoders for i in range(1, 8)]
 
 
-def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_epochs=999999, csv_path=None, seed=0):
+def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_epochs=999999, csv_path=None, seed=0, loss='exhaustive'):
     """model/cvig_baseline.py:318-404 on the HIP kernels: same flow, prints and checkpoint names; Adam with torch's
     defaults (lr 1e-3) over every encoder parameter.
     Under an initialised process group (N ranks, one per GPU) it is the reference's nn.DataParallel run (:339-343) with a rank in
@@ -724,10 +826,14 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
     statistics that count are rank 0's (parallel.broadcast_buffers before every validation phase and before saving). Validation
     embeds each global batch in contiguous shares and evaluates the dense loss on the gathered batch, so its numbers are those of
     the one-process loop on the same split. Rank 0 prints and saves. `seed` fixes the train / validation split, which every rank
-    must draw alike; it is not used on one rank."""
+    must draw alike; it is not used on one rank. loss='batch_hard' (not in the reference) trains on every anchor's hardest negative
+    of the global batch instead (batch_hard_triplet_loss / sharded_batch_hard_loss), and validation then evaluates that loss, so
+    that "best" is judged by the loss that is trained."""
     import pathlib
     import time
     from . import parallel
+    if loss not in LOSSES:
+        raise _lib.WitwError("train: loss must be 'exhaustive' or 'batch_hard', got %r" % (loss,))
     world, rank = parallel.world(), parallel.rank()
     if world > 1 and batch_size % world:
         raise _lib.WitwError('train: the global batch_size %d is not a multiple of the %d ranks' % (batch_size, world))
@@ -756,7 +862,9 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
     overhead_encoder = OverheadEncoder().to(device)
     encoders = [surface_encoder, overhead_encoder]
     parallel.broadcast_parameters(encoders)
-    loss_func = sharded_exhaustive_loss if world > 1 else exhaustive_minibatch_triplet_loss
+    dense_loss, sharded_loss = {'exhaustive': (exhaustive_minibatch_triplet_loss, sharded_exhaustive_loss),
+                                'batch_hard': (batch_hard_triplet_loss, sharded_batch_hard_loss)}[loss]
+    loss_func = sharded_loss if world > 1 else dense_loss
     optimizer = Adam(list(surface_encoder.parameters()) + list(overhead_encoder.parameters()))
     reducer = parallel.OverlappedGradReducer(encoders) if world > 1 else None      # SUM: the loss is normalised by the global batch
 
@@ -782,7 +890,7 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
                     su, ov = _embed_share(prep, surface_encoder, overhead_encoder, raw)
                     surface_embed, overhead_embed = parallel.all_gather_ragged(su), parallel.all_gather_ragged(ov)
                     with torch.no_grad():
-                        loss = exhaustive_minibatch_triplet_loss(surface_embed, overhead_embed)
+                        loss = dense_loss(surface_embed, overhead_embed)
                     count = surface_embed.size(0)
                 else:
                     data = prep(raw)
@@ -875,10 +983,13 @@ def main(argv=None):
                         help="Test mode: rank through evaluation_ranks -- 'direct' = the chunked difference-form pass, 'gemm' = the fp32 MFMA "
                              "distance GEMM with exact re-scoring (the same ranks), 'auto' = 'gemm' for large test sets. [Default = one dense "
                              "matrix, at most 65,535 pairs]")
+    parser.add_argument('--loss', default='exhaustive', choices=list(LOSSES),
+                        help='Train mode: exhaustive = every valid (anchor, positive, negative) of the global batch; batch_hard = every '
+                             'anchor against its hardest negative of the global batch only. [Default = exhaustive]')
     args = parser.parse_args(argv)
     _fov.init_distributed()       # under `python -m torch.distributed.run --nproc-per-node N`: one process per GPU; else nothing
     if args.mode == 'train':
-        train(dataset=args.dataset)
+        train(dataset=args.dataset, loss=args.loss)
     elif args.mode == 'test':
         test(dataset=args.dataset, match_method=args.match_method)
 
