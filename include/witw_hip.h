@@ -127,6 +127,11 @@ int witw_conv3x3_fwd_wino(const float* x, const float* wpk, const float* wpk_win
 /* 1 (default, or WITW_CONV_WINO in the environment): witw_conv3x3_fwd_wino takes the Winograd form where it can; 0: always the
  * direct form (A/B runs). enable < 0 only queries; returns the previous setting. */
 int witw_conv3x3_wino(int enable);
+/* 1 (default, or WITW_CONV_WINO_RUN in the environment): a Winograd launch starts at most one workgroup per CU, and each walks a
+ * run of tiles (every CU-count-th index of the workgroup -> tile map) with one continuous K loop; 0: one workgroup per tile. Same
+ * bits either way (A/B runs). WITW_CONV_WINO_WGS=n in the environment forces the workgroup count (test aid). enable < 0 only
+ * queries; returns the previous setting. */
+int witw_conv3x3_wino_run(int enable);
 /* backward of the fused MaxPool2d(2,2): pool_code (written by the forward when non-NULL: first arg-max position
  * dy*2+dx in torch's scan order) routes dy [B,Hp,Wp,C] into dx [B,H,W,C] (H>=2Hp, W>=2Wp). */
 int witw_maxpool2x2_bwd(const float* dy, const unsigned char* pool_code, float* dx, int B, int Hp, int Wp, int H, int W,

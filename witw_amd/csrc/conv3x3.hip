@@ -61,6 +61,9 @@ struct ConvArgs {
     // 64-channel tiles. Set by the launcher only for stride 1, no gate / dil_h / NCHW output / post affine, geometry 0.
     int wino;
     const float* wpk_wino;
+    // Winograd form only: the launch starts wino_wgs workgroups, and workgroup w walks the run w, w + wino_wgs, ... of the
+    // wino_items indices of the workgroup -> tile map (one index per workgroup when witw_conv3x3_wino_run is off)
+    int wino_items, wino_wgs;
 #ifdef WITW_STAMPS
     unsigned long long* stamps;   // diagnostic build only (tools/conv_stamps.cpp)
 #endif
@@ -89,55 +92,82 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
     constexpr int NWT = W_F4 / NTHREADS;
     static_assert(NWT * NTHREADS == W_F4, "the filter slab splits evenly over the workgroup");
 
-    const int tid = threadIdx.x;
+    // an opaque copy: nothing derived from it is shared with the direct form's code, whose registers would stay live over this form's
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int l31 = lane & 31;
     const int hq = lane >> 5;
 
-    int ntile, sp;          // block -> (n tile, image, spatial tile): as in the direct form
-    if (p.xcd_map) {
-        const int g = blockIdx.x >> 3;
-        ntile = g % p.n_tiles;
-        sp = (blockIdx.x & 7) * p.sp_per_xcd + g / p.n_tiles;
-        if (sp >= p.sp_total) return;
-    } else {
-        ntile = blockIdx.x / p.sp_total;
-        sp = blockIdx.x - ntile * p.sp_total;
-    }
+    // item -> (n tile, image, spatial tile): the map of the direct form, taken over an item index instead of blockIdx.x. Workgroup
+    // w walks items w, w + G, w + 2G, ... (G = p.wino_wgs, a multiple of 8 on the device: its run stays on one XCD's share of
+    // the spatial tiles, and the n tiles of a spatial tile still run at the same time on that XCD's L2); the holes of the padded
+    // XCD map (sp >= sp_total) are stepped over.
     const int tiles_img = p.tiles_x * p.tiles_y;
-    const int b = sp / tiles_img;
-    sp -= b * tiles_img;
-    const int ty = sp / p.tiles_x;
-    const int tx = sp - ty * p.tiles_x;
-    const int oy0 = ty * TH;
-    const int ox0 = tx * TW;
-    const int n0 = ntile * WTN;
+    auto item_sp = [&](int it, int& ntile) {
+        if (p.xcd_map) {
+            const int g = it >> 3;
+            ntile = g % p.n_tiles;
+            return (it & 7) * p.sp_per_xcd + g / p.n_tiles;
+        }
+        ntile = it / p.sp_total;
+        return it - ntile * p.sp_total;
+    };
+    auto step_item = [&](int it) { return p.wino_items - it > p.wino_wgs ? it + p.wino_wgs : p.wino_items; };      // no overflow
+    auto next_item = [&](int it) {      // first item of the run at or behind `it` that is a tile; p.wino_items when there is none
+        int nt;
+        while (it < p.wino_items && item_sp(it, nt) >= p.sp_total) it = step_item(it);
+        return it;
+    };
+    int it = next_item(blockIdx.x);
+    if (it >= p.wino_items) return;
     const int nkc = p.Cin >> 3;
 
     constexpr unsigned OOR = 0x80000000u;
     const size_t img_floats = (size_t)p.H * p.W * p.Cin;
-    __amdgpu_buffer_rsrc_t in_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b * img_floats), 0,
-                                                                     (unsigned)(img_floats * 4), 0x00020000);
-    __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<const f32x4*>(p.wpk_wino) + (size_t)ntile * nkc * W_F4), 0, (unsigned)nkc * W_F4 * 16u, 0x00020000);
+    // the tile being accumulated (the epilogue's), and the source of the staging instructions: the same tile up to its last chunk,
+    // whose "next chunk" is chunk 0 of the run's next item
+    int ntile, b, oy0, ox0;
+    __amdgpu_buffer_rsrc_t in_rs, w_rs;
     unsigned gin[NIN];
+    auto decode = [&](int item, int& nt_, int& b_, int& oy0_, int& ox0_) {
+        int sp = item_sp(item, nt_);
+        b_ = sp / tiles_img;
+        sp -= b_ * tiles_img;
+        const int ty = sp / p.tiles_x;
+        oy0_ = ty * TH;
+        ox0_ = (sp - ty * p.tiles_x) * TW;
+    };
+    // live = false: records of zero bytes, every staging load returns zeros without a memory access (behind a run's last item)
+    auto stage_from = [&](int nt_, int b_, int oy0_, int ox0_, bool live) {
+        in_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b_ * img_floats), 0, live ? (unsigned)(img_floats * 4) : 0u,
+                                                  0x00020000);
+        w_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const f32x4*>(p.wpk_wino) + (size_t)nt_ * nkc * W_F4), 0,
+                                                 live ? (unsigned)nkc * W_F4 * 16u : 0u, 0x00020000);
+        if (!live) return;
+        // the slot's (row, column) is worked out anew for every item: kept in registers over the K loop it would not fit
+        int t = tid;
+        asm volatile("" : "+v"(t));
 #pragma unroll
-    for (int i = 0; i < NIN; ++i) {
-        const int s = tid + i * NTHREADS;
-        const int pix = s >> 1, q = s & 1;
-        const int r = pix / IW, c = pix - r * IW;
-        const int gr = oy0 - 1 + r;
-        int gc = ox0 - 1 + c;
-        bool ok = (s < IN_F4) && gr >= 0 && gr < p.H;
-        if (p.circ) {
-            gc %= p.W;
-            if (gc < 0) gc += p.W;
-        } else {
-            ok = ok && gc >= 0 && gc < p.W;
+        for (int i = 0; i < NIN; ++i) {
+            const int s = t + i * NTHREADS;
+            const int pix = s >> 1, q = s & 1;
+            const int r = pix / IW, c = pix - r * IW;
+            const int gr = oy0_ - 1 + r;
+            int gc = ox0_ - 1 + c;
+            bool ok = (s < IN_F4) && gr >= 0 && gr < p.H;
+            if (p.circ) {
+                gc %= p.W;
+                if (gc < 0) gc += p.W;
+            } else {
+                ok = ok && gc >= 0 && gc < p.W;
+            }
+            gin[i] = ok ? (unsigned)((((size_t)gr * p.W + gc) * p.Cin + q * 4) * 4) : OOR;
         }
-        gin[i] = ok ? (unsigned)((((size_t)gr * p.W + gc) * p.Cin + q * 4) * 4) : OOR;
-    }
+    };
+    decode(it, ntile, b, oy0, ox0);
+    stage_from(ntile, b, oy0, ox0, true);
     const unsigned gwoff = (unsigned)tid * 16u;
     f32x4 rin[NIN], rw[NWT];
     // staging of a K chunk, one instruction at a time (i < NIN: input tile, then the filter slab): global -> registers -> LDS
@@ -234,9 +264,8 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
     // is a counted one. Step 4 has none to offer: there the chunk's barrier, whose drain is the loop's only full one, stands
     // between the reads (MFMAs 0..3) and the transform (MFMAs 8..15). It still separates the last read of this stage (step 4)
     // from its next overwrite (step 3 of the next chunk), and the writes of the next stage (step 3) from their first read (step 5).
-    for (int kc = 0; kc < nkc; ++kc) {
-        const int cur = kc & 1;
-        const int kn = (kc + 1 < nkc) ? kc + 1 : kc;   // last chunk restages itself (never read)
+    // One K chunk on stage `cur`, staging chunk kn of the staging source into the other stage.
+    auto chunk = [&](int cur, int kn) __attribute__((always_inline)) {
         const f32x4* in_s = smem + cur * STAGE_F4;
         const f32x4* w_s = in_s + IN_F4;
         const f32x4* in_n = smem + (cur ^ 1) * STAGE_F4;
@@ -266,78 +295,112 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
         }, false);
 #pragma unroll
         for (int t = 0; t < 4; ++t) fb[0][t] = fb[1][t];
-    }
-
-    // ---- epilogue: output transform, bias, dropout scale, ReLU, optional 2x2 max pool (the wave's own row pair), 16-byte stores
-    // through a wave-private 4 KB LDS slab (32 pixels x 32 channels; the staging buffers are dead behind the loop's last barrier)
-    f32x16 yv[2][2];       // [output row of the pair][column half]
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float m0 = acc[0][ct][r], m1 = acc[1][ct][r], m2 = acc[2][ct][r], m3 = acc[3][ct][r];
-            yv[0][ct][r] = (m0 + m1) + m2;
-            yv[1][ct][r] = (m1 - m2) - m3;
-        }
-    const int nb = n0 + wn * 32;
-    const int nch = nb + l31;
-    const float bv = p.bias[nch];
-    const float dm = (p.dropmask != nullptr && nch < p.Cout) ? p.dropmask[(size_t)b * p.Cout + nch] : 1.f;
-    const int act = p.relu;
-    auto fin = [&](float v) {
-        v = (v + bv) * dm;
-        if (act == 1) v = fmaxf(v, 0.f);
-        else if (act == 2) v = v > 0.f ? v : v * p.lrelu;
-        return v;
     };
+
+    // The run. The K loop is continuous over it: the stage parity carries on from item to item, and an item's last chunk stages
+    // chunk 0 of the next item (its own addresses and filter base, computed here between the loop and that chunk) and reads its
+    // first fragments in step 5, so only the run's first item pays the cold prologue above. Behind the run's last item the same
+    // instructions load zeros from empty records. Between two items stands the epilogue, serial, and the accumulators are cleared.
     const int Hy = POOL ? (p.Ho >> 1) : p.Ho;
     const int Wy = POOL ? (p.Wo >> 1) : p.Wo;
-    float* slab = reinterpret_cast<float*>(smem) + wave * (32 * 32);
+    // wave-private 4 KB epilogue slabs (32 pixels x 32 channels) behind the stages and their dummy slot: the other stage holds the
+    // next item's first chunk by then
+    float* slab = reinterpret_cast<float*>(smem + 2 * STAGE_F4 + 1) + wave * (32 * 32);
     const int prow = lane >> 3, pc4 = (lane & 7) * 4;     // read-back role: pixel in a group of 8, channel quad
-    if constexpr (!POOL) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) slab[((r & 3) + 8 * (r >> 2) + 4 * hq) * 32 + l31] = fin(yv[k][ct][r]);
-                const int yy = oy0 + 2 * wm + k;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int m = g * 8 + prow;
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(slab + m * 32 + pc4);
-                    const int xx = ox0 + 32 * ct + m;
-                    if (yy < Hy && xx < Wy && nb + pc4 < p.Cout)
-                        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.y + (((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nb + pc4));
-                }
-            }
-    } else {
-        const int yy = (oy0 + 2 * wm) >> 1;
+    int cur = 0;
+    for (;;) {
+        for (int kc = 1; kc < nkc; ++kc) {
+            chunk(cur, kc);
+            cur ^= 1;
+        }
+        const int it_n = next_item(step_item(it));
+        const bool more = it_n < p.wino_items;
+        int ntile_n = ntile, b_n = b, oy0_n = oy0, ox0_n = ox0;
+        if (more) decode(it_n, ntile_n, b_n, oy0_n, ox0_n);
+        stage_from(ntile_n, b_n, oy0_n, ox0_n, more);
+        chunk(cur, 0);
+        cur ^= 1;
+
+        // ---- epilogue: output transform, bias, dropout scale, ReLU, optional 2x2 max pool (the wave's own row pair), 16-byte stores
+        // through the wave's slab
+        const int n0 = ntile * WTN;
+        f32x16 yv[2][2];       // [output row of the pair][column half]
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
+            for (int r = 0; r < 16; ++r) {
+                const float m0 = acc[0][ct][r], m1 = acc[1][ct][r], m2 = acc[2][ct][r], m3 = acc[3][ct][r];
+                yv[0][ct][r] = (m0 + m1) + m2;
+                yv[1][ct][r] = (m1 - m2) - m3;
+            }
+        const int nb = n0 + wn * 32;
+        const int nch = nb + l31;
+        const float bv = p.bias[nch];
+        const float dm = (p.dropmask != nullptr && nch < p.Cout) ? p.dropmask[(size_t)b * p.Cout + nch] : 1.f;
+        const int act = p.relu;
+        auto fin = [&](float v) {
+            v = (v + bv) * dm;
+            if (act == 1) v = fmaxf(v, 0.f);
+            else if (act == 2) v = v > 0.f ? v : v * p.lrelu;
+            return v;
+        };
+        if constexpr (!POOL) {
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int r = 4 * g + 2 * e;
-                    const float a00 = yv[0][ct][r], a01 = yv[0][ct][r + 1], a10 = yv[1][ct][r], a11 = yv[1][ct][r + 1];
-                    const float m = fmaxf(fmaxf(a00, a01), fmaxf(a10, a11));
-                    const int pc = 16 * ct + 4 * g + 2 * hq + e;
-                    slab[pc * 32 + l31] = fin(m);
-                    const int xx = (ox0 >> 1) + pc;
-                    if (p.pool_code != nullptr && yy < Hy && xx < Wy && nch < p.Cout) {
-                        const int code = (a00 == m) ? 0 : (a01 == m) ? 1 : (a10 == m) ? 2 : 3;
-                        p.pool_code[(((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nch] = (unsigned char)code;
+            for (int k = 0; k < 2; ++k)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) slab[((r & 3) + 8 * (r >> 2) + 4 * hq) * 32 + l31] = fin(yv[k][ct][r]);
+                    const int yy = oy0 + 2 * wm + k;
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int m = g * 8 + prow;
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(slab + m * 32 + pc4);
+                        const int xx = ox0 + 32 * ct + m;
+                        if (yy < Hy && xx < Wy && nb + pc4 < p.Cout)
+                            __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.y + (((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nb + pc4));
                     }
                 }
+        } else {
+            const int yy = (oy0 + 2 * wm) >> 1;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int pc = g * 8 + prow;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(slab + pc * 32 + pc4);
-            const int xx = (ox0 >> 1) + pc;
-            if (yy < Hy && xx < Wy && nb + pc4 < p.Cout)
-                __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.y + (((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nb + pc4));
+            for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int r = 4 * g + 2 * e;
+                        const float a00 = yv[0][ct][r], a01 = yv[0][ct][r + 1], a10 = yv[1][ct][r], a11 = yv[1][ct][r + 1];
+                        const float m = fmaxf(fmaxf(a00, a01), fmaxf(a10, a11));
+                        const int pc = 16 * ct + 4 * g + 2 * hq + e;
+                        slab[pc * 32 + l31] = fin(m);
+                        const int xx = (ox0 >> 1) + pc;
+                        if (p.pool_code != nullptr && yy < Hy && xx < Wy && nch < p.Cout) {
+                            const int code = (a00 == m) ? 0 : (a01 == m) ? 1 : (a10 == m) ? 2 : 3;
+                            p.pool_code[(((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nch] = (unsigned char)code;
+                        }
+                    }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int pc = g * 8 + prow;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(slab + pc * 32 + pc4);
+                const int xx = (ox0 >> 1) + pc;
+                if (yy < Hy && xx < Wy && nb + pc4 < p.Cout)
+                    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.y + (((size_t)b * Hy + yy) * Wy + xx) * p.Cout + nb + pc4));
+            }
         }
+        if (!more) break;
+        it = it_n;
+        ntile = ntile_n;
+        b = b_n;
+        oy0 = oy0_n;
+        ox0 = ox0_n;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][ct][r] = 0.f;
     }
 }
 
@@ -379,13 +442,16 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_f32_kernel(ConvArgs p) {
     // with 4 taps and TN = 64 two stages are smaller than 8 slabs (58.6 KB < 64 KB), so the array is sized for both uses.
     // WINO: the classes that also run the Winograd F(2,3)-along-H form (conv_wino_h2) when the launcher sets p.wino
     constexpr bool WINO = SH == 1 && TAPS == 9 && GEO == 0 && (TN == 128 || POOL);
-    constexpr int WINO_F4 = WINO ? 2 * (2 * (NW + 2) * IW + 12 * 2 * 64) + 1 : 0;
+    // its two stages, the dummy slot and, behind them, a 4 KB epilogue slab per wave (both stages are live between two items of a run)
+    constexpr int WINO_F4 = WINO ? 2 * (2 * (NW + 2) * IW + 12 * 2 * 64) + 1 + NW * 256 : 0;
     constexpr int DIRECT_F4 = (2 * STAGE_F4 + 1 > NW * 512) ? 2 * STAGE_F4 + 1 : NW * 512;
     constexpr int SMEM_F4 = DIRECT_F4 > WINO_F4 ? DIRECT_F4 : WINO_F4;
     __shared__ f32x4 smem[SMEM_F4];
     static_assert(SMEM_F4 * 16 >= NW * 32 * 64 * 4, "the buffer must hold one epilogue slab per wave");
     if constexpr (WINO) {
-        if (p.wino) {
+        // weighted as the unlikely side: the run loop around the K loop otherwise outweighs the direct form's blocks in the register
+        // allocator's spill costs, and the direct epilogue spills (72 VGPRs in <128,1,false,8,0,9>)
+        if (__builtin_expect(p.wino != 0, 0)) {
             conv_wino_h2<NW, POOL>(p, smem);
             return;
         }
@@ -964,6 +1030,9 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restri
     y[idx] = (c < C) ? x[(b * C + c) * hw + r] : 0.f;
 }
 
+int env_int(const char* name, int dflt);
+int wino_run();
+
 template <int TN, int SH, bool POOL, int NW, int GEO, int TAPS = 9>
 int launch_conv_nw(ConvArgs a, hipStream_t st) {
     a.tiles_y = cdiv(a.Ho, GEO == 1 ? 4 * NW : NW);
@@ -981,7 +1050,15 @@ int launch_conv_nw(ConvArgs a, hipStream_t st) {
     }
     a.sp_total = (int)sp_total;
     const unsigned gy = (TAPS == 4 && a.ksplit > 1) ? (unsigned)a.ksplit : 1u;
-    hipLaunchKernelGGL((conv3x3_nhwc_f32_kernel<TN, SH, POOL, NW, GEO, TAPS>), dim3((unsigned)grid, gy), dim3(64 * NW), 0, st, a);
+    // the Winograd form: at most one workgroup per CU, each walking a run of the map's indices (wino_run() off: one index each)
+    a.wino_items = (int)grid;
+    a.wino_wgs = (int)grid;
+    if (a.wino && wino_run()) {
+        const int forced = env_int("WITW_CONV_WINO_WGS", 0);      // test aid: runs of more than one item on small shapes
+        a.wino_wgs = (int)std::min<long long>(grid, forced > 0 ? forced : witw_cu_count());
+    }
+    hipLaunchKernelGGL((conv3x3_nhwc_f32_kernel<TN, SH, POOL, NW, GEO, TAPS>), dim3(a.wino ? (unsigned)a.wino_wgs : (unsigned)grid, gy),
+                       dim3(64 * NW), 0, st, a);
     WITW_CHECK_LAUNCH("conv3x3_nhwc_f32");
     witw_note_variant("conv3x3_nhwc_f32_kernel<%d,%d,%s,%d,%d,%d>", TN, SH, POOL ? "true" : "false", NW, GEO, TAPS);
     if (a.wino) witw_note_conv_form("wino_h2");
@@ -1024,6 +1101,17 @@ int wino_on() {
         g_wino = e ? (atoi(e) != 0) : 1;
     }
     return g_wino;
+}
+
+// 1 (default): a Winograd launch starts one workgroup per CU and each walks a run of tiles with one continuous K loop; 0: one
+// workgroup per tile (WITW_CONV_WINO_RUN=0 / witw_conv3x3_wino_run(0): A/B runs, the bitwise tests)
+int g_wino_run = -1;
+int wino_run() {
+    if (g_wino_run < 0) {
+        const char* e = getenv("WITW_CONV_WINO_RUN");
+        g_wino_run = e ? (atoi(e) != 0) : 1;
+    }
+    return g_wino_run;
 }
 
 template <int TN, int SH, bool POOL>
@@ -1305,6 +1393,14 @@ int witw_conv3x3_fwd_wino(const float* x, const float* wpk, const float* wpk_win
 int witw_conv3x3_wino(int enable) {
     const int prev = wino_on();
     if (enable >= 0) g_wino = enable != 0;
+    return prev;
+}
+
+// 1 (default): a Winograd launch runs one workgroup per CU over runs of tiles; 0: one workgroup per tile (same bits). enable < 0
+// only queries. Returns the previous setting.
+int witw_conv3x3_wino_run(int enable) {
+    const int prev = wino_run();
+    if (enable >= 0) g_wino_run = enable != 0;
     return prev;
 }
 

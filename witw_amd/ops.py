@@ -1455,6 +1455,12 @@ def conv_wino(enable=None):
     return bool(_lib.load().witw_conv3x3_wino(-1 if enable is None else int(bool(enable))))
 
 
+def conv_wino_run(enable=None):
+    """Query (enable=None) or set whether a Winograd launch walks runs of tiles, one workgroup per CU (witw_conv3x3_wino_run);
+    returns the previous setting."""
+    return bool(_lib.load().witw_conv3x3_wino_run(-1 if enable is None else int(bool(enable))))
+
+
 def last_kernel_variant():
     """Name of the conv kernel instantiation the calling thread's last conv launcher picked (witw_last_kernel_variant), spelled
     as in rocprof kernel names."""
