@@ -86,6 +86,11 @@ int witw_conv_first2_bf16_fwd_train(const float* x, const void* wf0, const float
 int witw_conv3x3_bf16_gatebits_ok(int B, int H, int W, int Cin, int Cout);
 int witw_conv3x3_bf16_fwd_gatebits(const void* x_bf16, const void* wpk_bf16, const float* bias, const void* gate_bits, void* y, int B, int H,
                                    int W, int Cin, int Cout, int pad_circular, int relu, void* stream);
+/* The first layer itself (described above witw_conv3x3_first_pack). Finite images only: the kernels multiply filter slots that hold
+ * zero (a tap that does not exist, a channel >= C, a zero weight) with the pixel they meet, so a non-finite pixel makes the outputs
+ * whose 3x3 window contains it unspecified among NaN and +-inf -- 0 * inf = NaN where the convolution in the reals gives +-inf -- and,
+ * with relu, +0.0 (the ReLU of a NaN or of -inf). Every other output is unaffected. On finite data each form is tested bit for bit
+ * against float64: tests/test_first_layer_gpu.py. */
 int witw_conv3x3_first_fwd(const float* x, const float* wf, const float* bias, void* y, int B, int C, int H, int W,
                            int pad_circular, int relu, int out_bf16, void* stream);
 
