@@ -488,6 +488,27 @@ int witw_conv3x3_wgrad_taps4(const float* x, const float* dz, float* dw, float* 
  * witw_conv3x3_fwd_taps4_ex(s2d = 1) for that block. */
 int witw_conv4x4s2_first_fwd(const float* x, const float* w, const float* bias, const float* scale, const float* shift, float* y,
                              int B, int C, int H, int W, int normalize, float lrelu_slope, void* stream);
+/* ---- cvig_baseline inference with bf16 operands on v_mfma_f32_16x16x32_bf16 (blocks 1-4 of the encoder, model/cvig_baseline.py:
+ * 236-249, 265-275; blocks 5-7, the pooling and the normalisation stay on the fp32 entries).
+ * witw_conv4x4s2_first_fwd_bf16: witw_conv4x4s2_first_fwd with y bf16 [B, ceil(vh/2), ceil(vw/2), 256]: the same fp32 arithmetic in
+ * the same order, each output rounded once to nearest-even. */
+int witw_conv4x4s2_first_fwd_bf16(const float* x, const float* w, const float* bias, const float* scale, const float* shift, void* y_bf16,
+                                  int B, int C, int H, int W, int normalize, float lrelu_slope, void* stream);
+/* The 2x2-tap convolution of blocks 2-4 (model/cvig_baseline.py:241-249, 267-275: Conv2d(k=4, s=2) -> LeakyReLU -> BatchNorm2d in
+ * eval mode) on bf16 operands with fp32 accumulation. pack: taps {1,2}^2 of w [cout][cin][3][3] fp32 (what witw_conv4x4_to_k3
+ * writes), rounded once to bf16 (nearest-even), into wpk of witw_conv3x3_bf16_packed_elems_taps4(cout, cin) bf16 elements (cin
+ * padded to 16 with zeros); forward filters only. fwd: x NHWC bf16 [B,H,W,Cin] (Cin % 16 == 0, H, W >= 2), bias fp32 [Cout],
+ * post_scale / post_shift fp32 [Cout] or both NULL ->
+ *   y[b, r/2, c/2, ((r&1)*2 + (c&1))*Cout + n] = lrelu(sum_{ty,tx,ci} x[b,r+ty,c+tx,ci] * w[n,ci,1+ty,1+tx] + bias[n]) * post_scale[n]
+ *                                                 + post_shift[n]      for r < valid_h, c < valid_w, +0.0 elsewhere
+ * (x zero past H / W; 1 <= valid_h <= H, 1 <= valid_w <= W), y [B, ceil(valid_h/2), ceil(valid_w/2), 4*Cout]: the layout of
+ * witw_conv3x3_fwd_taps4_ex with s2d != 0. The epilogue runs in fp32 in that entry's order; y is bf16 with ONE nearest-even
+ * rounding per output (out_f32 == 0) or fp32 without any (out_f32 != 0). Any Cout >= 1 (a slower store unless Cout % 8 == 0). */
+long long witw_conv3x3_bf16_packed_elems_taps4(int cout, int cin);
+int witw_conv3x3_bf16_pack_weights_taps4(const float* w_kcrs, void* wpk_bf16, int cout, int cin, void* stream);
+int witw_conv3x3_bf16_fwd_taps4(const void* x_bf16, const void* wpk_bf16, const float* bias, const float* post_scale,
+                                const float* post_shift, void* y, int B, int H, int W, int Cin, int Cout, float lrelu_slope,
+                                int valid_h, int valid_w, int out_f32, void* stream);
 int witw_space_to_depth2(const float* x, float* y, int B, int Hp, int Wp, int H, int W, int C, int Cpad, int in_nchw,
                          int normalize, const float* scale, const float* shift, void* stream);
 /* Mosaic space-to-depth: x NHWC [B,H,W,C] (C % 4 == 0) -> y [ceil(B/g^2), g*ceil(H/2), g*ceil(W/2), 4C]: image b is cell b % g^2

@@ -28,15 +28,18 @@ struct First4Args {
     const float* bias;       // [64]
     const float* scale;      // [64] or null: y = lrelu(conv + bias) * scale + shift
     const float* shift;
-    float* y;                // [B, H2, W2, 256]
+    void* y;                 // [B, H2, W2, 256] fp32, or bf16 (conv4x4s2_first_kernel<C, true>)
     int B, C, H, W, vh, vw, H2, W2;
     int tiles_x, tiles_y, n_tiles;
     int normalize;
     float slope;
 };
 
-template <int C>
+// BF16: the same fp32 arithmetic in the same order, each output rounded once (nearest-even) to bf16 at the store -- what the bf16
+// second block reads (conv_taps4_bf16.hip). ES = bytes per output element; the fp32 instantiation's code is what it was without the flag.
+template <int C, bool BF16>
 __global__ __launch_bounds__(FT) void conv4x4s2_first_kernel(First4Args p) {
+    constexpr unsigned ES = BF16 ? 2u : 4u;
     __shared__ float raw_s[C * FRH * FRP];
     __shared__ float w_s[64 * (16 * C + 1)];
     constexpr int NSTEP = 8 * C;             // K = 16 C in steps of 2
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(FT) void conv4x4s2_first_kernel(First4Args p) {
     // the picture and tiles past the end read zeros (out-of-range offset / empty descriptor: straight-line code)
     const size_t plane = (size_t)p.H * p.W;
     const unsigned img_bytes = (unsigned)(C * plane * 4);      // < 2^31 (checked by the launcher)
-    const unsigned out_bytes = (unsigned)p.H2 * (unsigned)p.W2 * 1024u;      // one image's output, < 2^31 as well
+    const unsigned out_bytes = (unsigned)p.H2 * (unsigned)p.W2 * (256u * ES);      // one image's output, < 2^31 as well
     constexpr int NPIX = FRH * FRW, NIT = (NPIX + FT - 1) / FT;
     const int tiles_img = p.tiles_x * p.tiles_y;
     float rv[NIT][C];
@@ -157,8 +160,9 @@ __global__ __launch_bounds__(FT) void conv4x4s2_first_kernel(First4Args p) {
             // Buffer stores over image b's output: a pixel outside the padded grid is an out-of-range offset (dropped) -- no branch
             // around the stores, so the compiler can COUNT them in the wait of consume() above
             const int oy = oy0 + orow;
-            __amdgpu_buffer_rsrc_t ys = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (size_t)b * p.H2 * p.W2 * 256), 0, out_bytes, 0x00020000);
-            const unsigned row_off = ((unsigned)(oy >> 1) * (unsigned)p.W2 * 256u + (unsigned)(oy & 1) * 128u + (unsigned)l31) * 4u;
+            __amdgpu_buffer_rsrc_t ys =
+                __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.y + (size_t)b * p.H2 * p.W2 * (256 * ES)), 0, out_bytes, 0x00020000);
+            const unsigned row_off = ((unsigned)(oy >> 1) * (unsigned)p.W2 * 256u + (unsigned)(oy & 1) * 128u + (unsigned)l31) * ES;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ox = ox0 + (r & 3) + 8 * (r >> 2) + 4 * hq;
@@ -168,9 +172,14 @@ __global__ __launch_bounds__(FT) void conv4x4s2_first_kernel(First4Args p) {
                 v1 = v1 > 0.f ? v1 : v1 * p.slope;
                 v0 = v0 * sc0 + sh0;
                 v1 = v1 * sc1 + sh1;
-                const unsigned off = (oy < 2 * p.H2 && ox < 2 * p.W2) ? row_off + ((unsigned)(ox >> 1) * 256u + (unsigned)(ox & 1) * 64u) * 4u : 0xfffffff0u;
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, valid ? v0 : 0.f), ys, off, 0, 2);        // aux 2: nt
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, valid ? v1 : 0.f), ys, off, 128, 2);
+                const unsigned off = (oy < 2 * p.H2 && ox < 2 * p.W2) ? row_off + ((unsigned)(ox >> 1) * 256u + (unsigned)(ox & 1) * 64u) * ES : 0xfffffff0u;
+                if constexpr (BF16) {
+                    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, (__bf16)(valid ? v0 : 0.f)), ys, off, 0, 2);
+                    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, (__bf16)(valid ? v1 : 0.f)), ys, off, 64, 2);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, valid ? v0 : 0.f), ys, off, 0, 2);        // aux 2: nt
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, valid ? v1 : 0.f), ys, off, 128, 2);
+                }
             }
         }
         __syncthreads();                             // every wave has read its rows of the raw tile
@@ -179,15 +188,9 @@ __global__ __launch_bounds__(FT) void conv4x4s2_first_kernel(First4Args p) {
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-// x NCHW fp32 [B,C,H,W] (C <= 5, H, W >= 4) -> y [B, ceil(vh/2), ceil(vw/2), 256] with vh = (H-4)/2+1, vw = (W-4)/2+1:
-// y[b, oy/2, ox/2, ((oy&1)*2 + (ox&1))*64 + n] = lrelu(conv4x4s2(f(x))[b,n,oy,ox] + bias[n]) * scale[n] + shift[n] for oy < vh,
-// ox < vw, 0 elsewhere; f = (x/255)*2 - 1 when normalize != 0. w: torch layout [64][C][4][4]. scale / shift may both be NULL.
-int witw_conv4x4s2_first_fwd(const float* x, const float* w, const float* bias, const float* scale, const float* shift, float* y,
-                             int B, int C, int H, int W, int normalize, float lrelu_slope, void* stream) {
+template <bool BF16>
+int first4_launch(const float* x, const float* w, const float* bias, const float* scale, const float* shift, void* y, int B, int C, int H,
+                  int W, int normalize, float lrelu_slope, void* stream) {
     WITW_CHECK_ARG(x && w && bias && y, "conv4x4s2_first: null pointer");
     WITW_CHECK_ARG((scale == nullptr) == (shift == nullptr), "conv4x4s2_first: scale and shift come together");
     WITW_CHECK_ARG(B > 0 && C >= 1 && C <= FC_MAX && H >= 4 && W >= 4, "conv4x4s2_first: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
@@ -207,15 +210,34 @@ int witw_conv4x4s2_first_fwd(const float* x, const float* w, const float* bias, 
     const long long grid = n_tiles < 4LL * n_cu ? n_tiles : 4LL * n_cu;
     hipStream_t st = (hipStream_t)stream;
     switch (C) {
-    case 1: hipLaunchKernelGGL(conv4x4s2_first_kernel<1>, dim3((unsigned)grid), dim3(FT), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(conv4x4s2_first_kernel<2>, dim3((unsigned)grid), dim3(FT), 0, st, a); break;
-    case 3: hipLaunchKernelGGL(conv4x4s2_first_kernel<3>, dim3((unsigned)grid), dim3(FT), 0, st, a); break;
-    case 4: hipLaunchKernelGGL(conv4x4s2_first_kernel<4>, dim3((unsigned)grid), dim3(FT), 0, st, a); break;
-    default: hipLaunchKernelGGL(conv4x4s2_first_kernel<5>, dim3((unsigned)grid), dim3(FT), 0, st, a); break;
+    case 1: hipLaunchKernelGGL((conv4x4s2_first_kernel<1, BF16>), dim3((unsigned)grid), dim3(FT), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((conv4x4s2_first_kernel<2, BF16>), dim3((unsigned)grid), dim3(FT), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((conv4x4s2_first_kernel<3, BF16>), dim3((unsigned)grid), dim3(FT), 0, st, a); break;
+    case 4: hipLaunchKernelGGL((conv4x4s2_first_kernel<4, BF16>), dim3((unsigned)grid), dim3(FT), 0, st, a); break;
+    default: hipLaunchKernelGGL((conv4x4s2_first_kernel<5, BF16>), dim3((unsigned)grid), dim3(FT), 0, st, a); break;
     }
     WITW_CHECK_LAUNCH("conv4x4s2_first");
-    witw_note_variant("conv4x4s2_first_kernel<%d>", C);
+    if (BF16) witw_note_variant("conv4x4s2_first_kernel<%d,true>", C);
+    else witw_note_variant("conv4x4s2_first_kernel<%d>", C);
     return WITW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// x NCHW fp32 [B,C,H,W] (C <= 5, H, W >= 4) -> y [B, ceil(vh/2), ceil(vw/2), 256] with vh = (H-4)/2+1, vw = (W-4)/2+1:
+// y[b, oy/2, ox/2, ((oy&1)*2 + (ox&1))*64 + n] = lrelu(conv4x4s2(f(x))[b,n,oy,ox] + bias[n]) * scale[n] + shift[n] for oy < vh,
+// ox < vw, 0 elsewhere; f = (x/255)*2 - 1 when normalize != 0. w: torch layout [64][C][4][4]. scale / shift may both be NULL.
+int witw_conv4x4s2_first_fwd(const float* x, const float* w, const float* bias, const float* scale, const float* shift, float* y,
+                             int B, int C, int H, int W, int normalize, float lrelu_slope, void* stream) {
+    return first4_launch<false>(x, w, bias, scale, shift, y, B, C, H, W, normalize, lrelu_slope, stream);
+}
+
+// The same with y bf16 [B, ceil(vh/2), ceil(vw/2), 256]: the fp32 result above, rounded once to nearest-even.
+int witw_conv4x4s2_first_fwd_bf16(const float* x, const float* w, const float* bias, const float* scale, const float* shift, void* y_bf16,
+                                  int B, int C, int H, int W, int normalize, float lrelu_slope, void* stream) {
+    return first4_launch<true>(x, w, bias, scale, shift, y_bf16, B, C, H, W, normalize, lrelu_slope, stream);
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, baseline_bf16, ops
 from . import cvig_fov as _fov
 from .cvig_fov import Adam, recall_table  # noqa: F401  (same table, model/cvig_baseline.py:461-466)
 
@@ -29,6 +29,10 @@ class Globals:
         'cvusa': {'path_columns': [0, 1], 'path_names': ['overhead', 'surface'], 'header': None, 'panorama': True},
         'witw': {'path_columns': [15, 16], 'path_names': ['surface', 'overhead'], 'header': 0, 'panorama': False},
     }
+    precision = 'fp32'       # arithmetic of the encoders' eval forward: 'fp32', or 'bf16' (blocks 1-4 on the bf16 MFMA; inference only)
+
+
+PRECISIONS = ('fp32', 'bf16')
 
 
 # how many units make one full turn of the panorama, per first letter of the unit name; None: the shift already is in pixels
@@ -146,8 +150,14 @@ class SurfaceEncoder(nn.Module):
     """model/cvig_baseline.py:228-279; parameters live in nn.Conv2d / nn.BatchNorm2d children named
     conv1..7 / bn1..7 (same state-dict keys), the forward runs on the HIP kernels."""
 
-    def __init__(self, orientation=False, bands=3, p=3.):
+    def __init__(self, orientation=False, bands=3, p=3., precision=None):
+        """precision: None = Globals.precision; 'fp32', or 'bf16' = the eval forward runs blocks 1-4 with bf16 operands and fp32
+        accumulation (bf16 activations between them, fp32 into block 5; the filters are rounded from the fp32 master weights, the
+        BatchNorm fold, blocks 5-7, pooling and normalisation stay fp32). Training is fp32 only."""
         super().__init__()
+        self.precision = Globals.precision if precision is None else precision
+        if self.precision not in PRECISIONS:
+            raise _lib.WitwError("cvig_baseline encoder: precision must be 'fp32' or 'bf16', got %r" % (self.precision,))
         self.orientation, self.bands, self.p = orientation, bands, p
         self.inputs = self.bands + 2 * self.orientation
         widths = [self.inputs, 64, 128, 256, 512, 512, 512, 512]
@@ -163,9 +173,10 @@ class SurfaceEncoder(nn.Module):
         self._packed = {}
         self.fused_first = True       # eval forward: block 1 by witw_conv4x4s2_first_fwd (False: space-to-depth pass + 2x2-tap conv)
 
-    def _layer(self, i, fold=True):
+    def _layer(self, i, fold=True, pack=True):
         """-> (packed 2x2-tap filter, eval-mode BatchNorm scale, shift, padded input channels). fold=False (the training forward:
-        batch statistics) skips the scale / shift of the running statistics."""
+        batch statistics) skips the scale / shift of the running statistics. pack=False (blocks 1-4 of the bf16 forward, which never
+        launch the fp32 image) skips the fp32 packing: the first element is then whatever image there is, possibly None."""
         conv, bn = getattr(self, 'conv%d' % i), getattr(self, 'bn%d' % i)
         # torch's version counters see in-place torch ops; the C-ABI Adam bumps _witw_version instead
         wkey = tuple(t._version for t in (conv.weight, conv.bias)) + tuple(getattr(t, '_witw_version', 0) for t in (conv.weight, conv.bias)) + \
@@ -178,9 +189,12 @@ class SurfaceEncoder(nn.Module):
                 # 4x4/s2 filter -> 3x3 filter over space-to-depth channels (dy*2+dx)*ci+c; tap (kh,kw) in {1,2}^2 holds
                 # W[:, :, 2(kh-1)+dy, 2(kw-1)+dx], row / column 0 of the taps stay zero (witw_conv4x4_to_k3: one launch)
                 k3 = ops.conv4x4_to_k3(conv.weight, cpad)
-                packed = ops.PackedConv(k3, conv.bias, taps4=True, reuse=hit[1] if hit else None)      # only the 2x2 live taps
-            hit = [wkey, packed, cpad, k3, None]
+            hit = [wkey, None, cpad, k3, None, (hit[1] or hit[5]) if hit else None]      # [5]: a stale fp32 image to overwrite in place
             self._packed[i] = hit
+        if pack and hit[1] is None:
+            with torch.no_grad():
+                hit[1] = ops.PackedConv(hit[3], conv.bias, taps4=True, reuse=hit[5])      # only the 2x2 live taps
+            hit[5] = None
         if not fold:
             return hit[1], None, None, hit[2]
         bkey = tuple(t._version for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)) + \
@@ -191,6 +205,17 @@ class SurfaceEncoder(nn.Module):
                 shift = bn.bias - bn.running_mean * scale
             hit[4] = (bkey, scale.contiguous(), shift.contiguous())
         return hit[1], hit[4][1], hit[4][2], hit[2]
+
+    def _layer_bf16(self, i):
+        """the bf16 2x2-tap filter of block i, re-packed in place when the weights have changed (the key of _layer)"""
+        self._layer(i, fold=False, pack=False)
+        wkey, k3 = self._packed[i][0], self._packed[i][3]
+        hit = self._packed.get(('bf16', i))
+        if hit is None or hit[0] != wkey:
+            conv = getattr(self, 'conv%d' % i)
+            hit = (wkey, baseline_bf16.PackedConvBf16Taps4(k3, conv.bias, reuse=hit[1] if hit else None))
+            self._packed[('bf16', i)] = hit
+        return hit[1]
 
     def _layer_k3(self, i):
         self._layer(i, fold=False)
@@ -223,6 +248,12 @@ class SurfaceEncoder(nn.Module):
         B, _c, H, W = x.shape
         if min(H, W) < 382:
             raise _lib.WitwError('cvig_baseline encoder needs sides >= 382 px, got %dx%d' % (H, W))
+        bf16 = self.precision == 'bf16'
+        if bf16 and self.training:
+            raise _lib.WitwError("cvig_baseline encoder: precision='bf16' is inference only -- fp32 is the only training arithmetic")
+        if bf16 and self.inputs > 5:
+            raise _lib.WitwError("cvig_baseline encoder: precision='bf16' needs the fused first block (at most 5 input channels, got %d)"
+                                 % self.inputs)
         if self.training:
             self._bwd_override = {} if lrelu_acts is None else lrelu_acts
             return _BaselineEncoderFn.apply(x, self, *self.train_params())
@@ -232,13 +263,19 @@ class SurfaceEncoder(nn.Module):
             g = 1                  # images per mosaic side of the current layer input h
             # block 1 straight from the raw image (normalisation :265-266, conv1, LeakyReLU, bn1 in one launch) when the second
             # block reads exactly its 4 x 64 space-to-depth channels; otherwise the re-layout pass + the generic 2x2-tap form
-            fused_first = self.fused_first and self._layer(2)[3] == 256 and self.inputs <= 5
+            fused_first = bf16 or (self.fused_first and self._layer(2)[3] == 256 and self.inputs <= 5)
             h = None if fused_first else ops.space_to_depth2(x.contiguous(), in_nchw=True, normalize=True, cpad=self._layer(1)[3])
             for i in range(1, 8):
-                packed, scale, shift, _cp = self._layer(i)
+                packed, scale, shift, _cp = self._layer(i, pack=not (bf16 and i < 5))
                 vh, vw = (vh - 4) // 2 + 1, (vw - 4) // 2 + 1
                 if i == 1 and fused_first:
-                    h = ops.conv4x4s2_first(x.contiguous(), self.conv1.weight, self.conv1.bias, scale, shift, normalize=True, lrelu_slope=0.2)
+                    h = ops.conv4x4s2_first(x.contiguous(), self.conv1.weight, self.conv1.bias, scale, shift, normalize=True, lrelu_slope=0.2,
+                                            out_bf16=bf16)
+                    continue
+                if bf16 and i < 5:
+                    # blocks 2-4 on the bf16 MFMA: bf16 activations between them, block 4 hands fp32 to the split-K blocks
+                    h = baseline_bf16.conv_taps4_s2d_bf16(h, self._layer_bf16(i), (vh, vw), lrelu_slope=0.2, post_scale=scale, post_shift=shift,
+                                                out_f32=(i == 4))
                     continue
                 if i < 5 and 4 * packed.cout == self._layer(i + 1)[3]:
                     # blocks 1-4: the epilogue writes the next block's space-to-depth input directly
@@ -921,11 +958,12 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
     return best_loss
 
 
-def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_method=None):
+def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_method=None, precision=None):
     """model/cvig_baseline.py:405-475: embed the test set (SyncedRotation stays on, as in the reference :410-414),
     rank every query against the whole gallery on the GPU, print the recall table. match_method: None = ranks() (one dense
     matrix, at most 65,535 pairs); 'direct', 'gemm' or 'auto' = evaluation_ranks(method=...): the same ranks from the chunked
-    pass, 'gemm' at GEMM cost with exact re-scoring (retrieve).
+    pass, 'gemm' at GEMM cost with exact re-scoring (retrieve). precision: the encoders' arithmetic ('fp32' or 'bf16'; None =
+    Globals.precision), see SurfaceEncoder.
     Under an initialised process group every rank embeds a contiguous share of the test set and keeps its gallery rows; the
     queries are gathered and the rank counts summed inside evaluation_ranks, rank 0 prints. None then means 'auto': the dense
     ranks() cannot be sharded."""
@@ -940,8 +978,8 @@ def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_met
     shard = torch.utils.data.Subset(test_set, range(shard_begin, shard_end)) if world > 1 else test_set
     test_loader = torch.utils.data.DataLoader(shard, batch_size=batch_size, shuffle=False, drop_last=False,
                                               num_workers=num_workers, collate_fn=_fov.collate_raw)
-    surface_encoder = SurfaceEncoder().to(device)
-    overhead_encoder = OverheadEncoder().to(device)
+    surface_encoder = SurfaceEncoder(precision=precision).to(device)
+    overhead_encoder = OverheadEncoder(precision=precision).to(device)
     surface_encoder.load_state_dict(torch.load('./weights/surface_best.pth', map_location='cpu'))
     overhead_encoder.load_state_dict(torch.load('./weights/overhead_best.pth', map_location='cpu'))
     surface_encoder.eval()
@@ -986,12 +1024,18 @@ def main(argv=None):
     parser.add_argument('--loss', default='exhaustive', choices=list(LOSSES),
                         help='Train mode: exhaustive = every valid (anchor, positive, negative) of the global batch; batch_hard = every '
                              'anchor against its hardest negative of the global batch only. [Default = exhaustive]')
+    parser.add_argument('--precision', default='fp32', choices=list(PRECISIONS),
+                        help='Test mode: arithmetic of the encoders. fp32 = fp32 MFMA throughout (within 2e-5 of fp64); bf16 = blocks 1-4 '
+                             '(86 %% of the multiply-adds) with bf16 operands and fp32 accumulation on the bf16 MFMA, blocks 5-7 and the '
+                             'head in fp32 (embedding within 1e-2 of fp64, relative to its norm). Training is fp32 only. [Default = fp32]')
     args = parser.parse_args(argv)
+    if args.mode == 'train' and args.precision != 'fp32':
+        parser.error("--precision %s is inference only: --mode train runs in fp32 (use it with --mode test)" % args.precision)
     _fov.init_distributed()       # under `python -m torch.distributed.run --nproc-per-node N`: one process per GPU; else nothing
     if args.mode == 'train':
         train(dataset=args.dataset, loss=args.loss)
     elif args.mode == 'test':
-        test(dataset=args.dataset, match_method=args.match_method)
+        test(dataset=args.dataset, match_method=args.match_method, precision=args.precision)
 
 
 if __name__ == '__main__':

@@ -361,10 +361,11 @@ def conv_taps4_s2d(x_nhwc, packed, valid_hw, lrelu_slope=None, post_scale=None, 
     return y
 
 
-def conv4x4s2_first(x_nchw, weight, bias, post_scale=None, post_shift=None, normalize=True, lrelu_slope=0.2):
+def conv4x4s2_first(x_nchw, weight, bias, post_scale=None, post_shift=None, normalize=True, lrelu_slope=0.2, out_bf16=False):
     """First block of a cvig_baseline encoder in one launch: x NCHW fp32 [B,C,H,W] (raw 0..255 values when normalize) ->
     [B, ceil(vh/2), ceil(vw/2), 256], the space-to-depth(2) input of the second block (model/cvig_baseline.py:236-240, 265-268).
-    weight [64,C,4,4] (torch layout), bias / post_scale / post_shift [64]."""
+    weight [64,C,4,4] (torch layout), bias / post_scale / post_shift [64]. out_bf16: the same fp32 values rounded once to bf16
+    (nearest-even), the input of baseline_bf16.conv_taps4_s2d_bf16."""
     lib = _lib.load()
     x = _dev_f32(x_nchw, 'x')
     w, b = _dev_f32(weight.detach(), 'weight'), _dev_f32(bias.detach(), 'bias')
@@ -376,10 +377,12 @@ def conv4x4s2_first(x_nchw, weight, bias, post_scale=None, post_shift=None, norm
     if post_scale is not None:
         post_scale, post_shift = _dev_f32(post_scale, 'post_scale'), _dev_f32(post_shift, 'post_shift')
     vh, vw = (H - 4) // 2 + 1, (W - 4) // 2 + 1
-    y = torch.empty((B, (vh + 1) // 2, (vw + 1) // 2, 256), dtype=torch.float32, device=x.device)
+    y = torch.empty((B, (vh + 1) // 2, (vw + 1) // 2, 256), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device)
     prof = _prof_begin()
-    _lib.check(lib.witw_conv4x4s2_first_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), _p(post_scale), _p(post_shift), y.data_ptr(),
-                                            B, C, H, W, int(bool(normalize)), float(lrelu_slope), _stream()), 'witw_conv4x4s2_first_fwd')
+    entry, what = (lib.witw_conv4x4s2_first_fwd_bf16, 'witw_conv4x4s2_first_fwd_bf16') if out_bf16 else \
+        (lib.witw_conv4x4s2_first_fwd, 'witw_conv4x4s2_first_fwd')
+    _lib.check(entry(x.data_ptr(), w.data_ptr(), b.data_ptr(), _p(post_scale), _p(post_shift), y.data_ptr(),
+                     B, C, H, W, int(bool(normalize)), float(lrelu_slope), _stream()), what)
     if prof is not None:
         _prof_end(prof, ('first4x4', 64, 2, False), 2.0 * C * 64 * 16 * vh * vw * B)
     return y
