@@ -509,6 +509,21 @@ int witw_conv3x3_bf16_pack_weights_taps4(const float* w_kcrs, void* wpk_bf16, in
 int witw_conv3x3_bf16_fwd_taps4(const void* x_bf16, const void* wpk_bf16, const float* bias, const float* post_scale,
                                 const float* post_shift, void* y, int B, int H, int W, int Cin, int Cout, float lrelu_slope,
                                 int valid_h, int valid_w, int out_f32, void* stream);
+/* Blocks 5-7 of the same encoders on bf16 operands (SurfaceEncoder(precision='bf16_all')): the split-K form of the convolution above
+ * over a g x g mosaic. x NHWC bf16 [Bm,H,W,Cin] (Cin % 16 == 0; the layout witw_space_to_depth2_mosaic_bf16 writes, or the plain batch),
+ * wpk from witw_conv3x3_bf16_pack_weights_taps4 (unchanged), 1 <= ksplit <= Cin/16, Cout % 4 == 0 ->
+ *   ws[s, b, r, c, n] = sum_{ty,tx} sum_{ci in slice s} x[b,r+ty,c+tx,ci] * w[n,ci,1+ty,1+tx]        for every r < H, c < W, n < Cout
+ * (x zero past H / W), ws fp32 [ksplit][Bm,H,W,Cout]: RAW partial sums in fp32, no bias, no activation, no affine, and no element of
+ * ws left unwritten. Slice s is a contiguous run of the Cin/16 chunks of 16 channels, the first (Cin/16) % ksplit slices one chunk
+ * longer than the rest. witw_taps4_splitk_finish adds the slices in slice order (deterministic for a given ksplit), applies the
+ * epilogue and gathers the valid outputs. witw_conv3x3_bf16_taps4_ksplit returns the factor the library would pick for the shape
+ * (WITW_CONV_KSPLIT forces it), -1 on a bad shape. */
+int witw_conv3x3_bf16_taps4_ksplit(int Bm, int H, int W, int Cin, int Cout);
+int witw_conv3x3_bf16_fwd_taps4_splitk(const void* x_bf16, const void* wpk_bf16, float* ws, int Bm, int H, int W, int Cin, int Cout,
+                                       int ksplit, void* stream);
+/* witw_space_to_depth2_mosaic (below) with a bf16 output: x fp32 NHWC [B,H,W,C] (C % 4 == 0) -> y bf16 [ceil(B/g^2), g*ceil(H/2),
+ * g*ceil(W/2), 4C], ONE nearest-even rounding per element, +0.0 where no source exists (16-byte stores where C % 8 == 0). */
+int witw_space_to_depth2_mosaic_bf16(const float* x, void* y_bf16, int B, int H, int W, int C, int g, void* stream);
 int witw_space_to_depth2(const float* x, float* y, int B, int Hp, int Wp, int H, int W, int C, int Cpad, int in_nchw,
                          int normalize, const float* scale, const float* shift, void* stream);
 /* Mosaic space-to-depth: x NHWC [B,H,W,C] (C % 4 == 0) -> y [ceil(B/g^2), g*ceil(H/2), g*ceil(W/2), 4C]: image b is cell b % g^2

@@ -23,6 +23,7 @@ from witw_amd import cvig_baseline as cb  # noqa: E402
 from witw_amd import ops, synth  # noqa: E402
 
 PEAK_TFLOPS = 2500.0
+PRECISIONS = ('fp32', 'bf16')      # the third value, 'bf16_all', has tools/bench_baseline_bf16_all.py
 
 
 def _event_ms(run):
@@ -50,7 +51,7 @@ def main():
     su = torch.from_numpy(synth.images_u8(90, 0, (args.pairs, 3, 500, 500))).to(dev)
     ov = torch.from_numpy(synth.images_u8(90, 1, (args.pairs, 3, 512, 512))).to(dev)
     enc = {}
-    for prec in cb.PRECISIONS:
+    for prec in PRECISIONS:
         torch.manual_seed(1)
         enc[prec] = (cb.SurfaceEncoder(precision=prec).to(dev).eval(), cb.OverheadEncoder(precision=prec).to(dev).eval())
 
@@ -59,12 +60,12 @@ def main():
         return s(su), o(ov)
 
     for _ in range(args.warmup):
-        for prec in cb.PRECISIONS:
+        for prec in PRECISIONS:
             step(prec)
     torch.cuda.synchronize()
-    times = {prec: [] for prec in cb.PRECISIONS}
+    times = {prec: [] for prec in PRECISIONS}
     for _ in range(args.rounds):
-        for prec in cb.PRECISIONS:
+        for prec in PRECISIONS:
             times[prec].append(_event_ms(lambda: step(prec)))
     out = {'pairs': args.pairs, 'rounds': args.rounds, 'device': torch.cuda.get_device_name(0), 'step_ms': {p: _row(v) for p, v in times.items()}}
     f32, b16 = out['step_ms']['fp32'], out['step_ms']['bf16']

@@ -29,10 +29,10 @@ class Globals:
         'cvusa': {'path_columns': [0, 1], 'path_names': ['overhead', 'surface'], 'header': None, 'panorama': True},
         'witw': {'path_columns': [15, 16], 'path_names': ['surface', 'overhead'], 'header': 0, 'panorama': False},
     }
-    precision = 'fp32'       # arithmetic of the encoders' eval forward: 'fp32', or 'bf16' (blocks 1-4 on the bf16 MFMA; inference only)
+    precision = 'fp32'       # arithmetic of the encoders' eval forward: 'fp32', 'bf16' (blocks 1-4 on the bf16 MFMA) or 'bf16_all' (all seven); bf16 is inference only
 
 
-PRECISIONS = ('fp32', 'bf16')
+PRECISIONS = ('fp32', 'bf16', 'bf16_all')
 
 
 # how many units make one full turn of the panorama, per first letter of the unit name; None: the shift already is in pixels
@@ -153,11 +153,13 @@ class SurfaceEncoder(nn.Module):
     def __init__(self, orientation=False, bands=3, p=3., precision=None):
         """precision: None = Globals.precision; 'fp32', or 'bf16' = the eval forward runs blocks 1-4 with bf16 operands and fp32
         accumulation (bf16 activations between them, fp32 into block 5; the filters are rounded from the fp32 master weights, the
-        BatchNorm fold, blocks 5-7, pooling and normalisation stay fp32). Training is fp32 only."""
+        BatchNorm fold, blocks 5-7, pooling and normalisation stay fp32); 'bf16_all' = blocks 5-7 as well: block 4 stores bf16, blocks
+        5-7 run the bf16 split-K convolution over bf16 mosaics (baseline_bf16.conv_taps4_splitk_bf16), their fp32 outputs are pooled
+        unrounded and rounded once on the way into the next block. Training is fp32 only."""
         super().__init__()
         self.precision = Globals.precision if precision is None else precision
         if self.precision not in PRECISIONS:
-            raise _lib.WitwError("cvig_baseline encoder: precision must be 'fp32' or 'bf16', got %r" % (self.precision,))
+            raise _lib.WitwError("cvig_baseline encoder: precision must be 'fp32', 'bf16' or 'bf16_all', got %r" % (self.precision,))
         self.orientation, self.bands, self.p = orientation, bands, p
         self.inputs = self.bands + 2 * self.orientation
         widths = [self.inputs, 64, 128, 256, 512, 512, 512, 512]
@@ -175,7 +177,7 @@ class SurfaceEncoder(nn.Module):
 
     def _layer(self, i, fold=True, pack=True):
         """-> (packed 2x2-tap filter, eval-mode BatchNorm scale, shift, padded input channels). fold=False (the training forward:
-        batch statistics) skips the scale / shift of the running statistics. pack=False (blocks 1-4 of the bf16 forward, which never
+        batch statistics) skips the scale / shift of the running statistics. pack=False (blocks 1-4 of the 'bf16' forward and every block of the 'bf16_all' one, which never
         launch the fp32 image) skips the fp32 packing: the first element is then whatever image there is, possibly None."""
         conv, bn = getattr(self, 'conv%d' % i), getattr(self, 'bn%d' % i)
         # torch's version counters see in-place torch ops; the C-ABI Adam bumps _witw_version instead
@@ -248,12 +250,13 @@ class SurfaceEncoder(nn.Module):
         B, _c, H, W = x.shape
         if min(H, W) < 382:
             raise _lib.WitwError('cvig_baseline encoder needs sides >= 382 px, got %dx%d' % (H, W))
-        bf16 = self.precision == 'bf16'
+        bf16 = self.precision in ('bf16', 'bf16_all')
+        bf16_all = self.precision == 'bf16_all'
         if bf16 and self.training:
-            raise _lib.WitwError("cvig_baseline encoder: precision='bf16' is inference only -- fp32 is the only training arithmetic")
+            raise _lib.WitwError("cvig_baseline encoder: precision='%s' is inference only -- fp32 is the only training arithmetic" % self.precision)
         if bf16 and self.inputs > 5:
-            raise _lib.WitwError("cvig_baseline encoder: precision='bf16' needs the fused first block (at most 5 input channels, got %d)"
-                                 % self.inputs)
+            raise _lib.WitwError("cvig_baseline encoder: precision='%s' needs the fused first block (at most 5 input channels, got %d)"
+                                 % (self.precision, self.inputs))
         if self.training:
             self._bwd_override = {} if lrelu_acts is None else lrelu_acts
             return _BaselineEncoderFn.apply(x, self, *self.train_params())
@@ -266,16 +269,27 @@ class SurfaceEncoder(nn.Module):
             fused_first = bf16 or (self.fused_first and self._layer(2)[3] == 256 and self.inputs <= 5)
             h = None if fused_first else ops.space_to_depth2(x.contiguous(), in_nchw=True, normalize=True, cpad=self._layer(1)[3])
             for i in range(1, 8):
-                packed, scale, shift, _cp = self._layer(i, pack=not (bf16 and i < 5))
+                packed, scale, shift, _cp = self._layer(i, pack=not (bf16_all or (bf16 and i < 5)))
                 vh, vw = (vh - 4) // 2 + 1, (vw - 4) // 2 + 1
                 if i == 1 and fused_first:
                     h = ops.conv4x4s2_first(x.contiguous(), self.conv1.weight, self.conv1.bias, scale, shift, normalize=True, lrelu_slope=0.2,
                                             out_bf16=bf16)
                     continue
                 if bf16 and i < 5:
-                    # blocks 2-4 on the bf16 MFMA: bf16 activations between them, block 4 hands fp32 to the split-K blocks
+                    # blocks 2-4 on the bf16 MFMA: bf16 activations between them, block 4 hands fp32 to the fp32 split-K blocks
+                    # ('bf16') or bf16 to the bf16 ones ('bf16_all')
                     h = baseline_bf16.conv_taps4_s2d_bf16(h, self._layer_bf16(i), (vh, vw), lrelu_slope=0.2, post_scale=scale, post_shift=shift,
-                                                out_f32=(i == 4))
+                                                out_f32=(i == 4 and not bf16_all))
+                    continue
+                if bf16_all:
+                    # blocks 5-7 on the bf16 MFMA: split-K over a bf16 mosaic, fp32 out: pooled unrounded, rounded once into the next block
+                    y = baseline_bf16.conv_taps4_splitk_bf16(h, self._layer_bf16(i), B, g, (vh, vw), lrelu_slope=0.2, post_scale=scale,
+                                                             post_shift=shift)
+                    ops.gem_pool(y, (vh, vw), f, 512 * (i - 5), self.p)
+                    if i < 7:
+                        nh, nw = (vh + 1) // 2, (vw + 1) // 2
+                        g = max(1, min(16 // nh, 16 // nw))
+                        h = baseline_bf16.space_to_depth2_mosaic_bf16(y, g)
                     continue
                 if i < 5 and 4 * packed.cout == self._layer(i + 1)[3]:
                     # blocks 1-4: the epilogue writes the next block's space-to-depth input directly
@@ -962,7 +976,7 @@ def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_met
     """model/cvig_baseline.py:405-475: embed the test set (SyncedRotation stays on, as in the reference :410-414),
     rank every query against the whole gallery on the GPU, print the recall table. match_method: None = ranks() (one dense
     matrix, at most 65,535 pairs); 'direct', 'gemm' or 'auto' = evaluation_ranks(method=...): the same ranks from the chunked
-    pass, 'gemm' at GEMM cost with exact re-scoring (retrieve). precision: the encoders' arithmetic ('fp32' or 'bf16'; None =
+    pass, 'gemm' at GEMM cost with exact re-scoring (retrieve). precision: the encoders' arithmetic ('fp32', 'bf16' or 'bf16_all'; None =
     Globals.precision), see SurfaceEncoder.
     Under an initialised process group every rank embeds a contiguous share of the test set and keeps its gallery rows; the
     queries are gathered and the rank counts summed inside evaluation_ranks, rank 0 prints. None then means 'auto': the dense
@@ -1027,7 +1041,8 @@ def main(argv=None):
     parser.add_argument('--precision', default='fp32', choices=list(PRECISIONS),
                         help='Test mode: arithmetic of the encoders. fp32 = fp32 MFMA throughout (within 2e-5 of fp64); bf16 = blocks 1-4 '
                              '(86 %% of the multiply-adds) with bf16 operands and fp32 accumulation on the bf16 MFMA, blocks 5-7 and the '
-                             'head in fp32 (embedding within 1e-2 of fp64, relative to its norm). Training is fp32 only. [Default = fp32]')
+                             'head in fp32 (embedding within 1e-2 of fp64, relative to its norm); bf16_all = the convolutions of blocks 5-7 on the '
+                             'bf16 MFMA as well (split-K, fp32 sums; same bound). Training is fp32 only. [Default = fp32]')
     args = parser.parse_args(argv)
     if args.mode == 'train' and args.precision != 'fp32':
         parser.error("--precision %s is inference only: --mode train runs in fp32 (use it with --mode test)" % args.precision)
