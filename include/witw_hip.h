@@ -147,7 +147,7 @@ int witw_nchw_to_nhwc(const float* x, float* y, int B, int C, int H, int W, int 
  * [B,Ho,W,Cout] NHWC (ReLU / dropout gates already applied). dw: torch layout [Cout][cin_real][3][3];
  * db: [Cout] or NULL; accumulate != 0 adds into dw/db. workspace: witw_conv3x3_wgrad_workspace_floats().
  *
- * Contract of every weight-gradient entry (witw_conv3x3_wgrad, _wgrad_taps4, _wgrad_bf16, _wgrad_bf16_nhwc, _wgrad_f16x3), as
+ * Contract of every weight-gradient entry (witw_conv3x3_wgrad, _wgrad_taps4, _wgrad_bf16, _wgrad_bf16_nhwc, _wgrad_bf16_taps4, _wgrad_f16x3), as
  * tested by tests/test_wgrad_edges_gpu.py:
  *   accumulate: with accumulate != 0 each element of dw [Cout][cin_real][3][3] and of db (when not NULL) becomes
  *     old value + (the value accumulate == 0 would have stored): ONE fp32 add per element, bit for bit, no other arithmetic on
@@ -524,6 +524,35 @@ int witw_conv3x3_bf16_fwd_taps4_splitk(const void* x_bf16, const void* wpk_bf16,
 /* witw_space_to_depth2_mosaic (below) with a bf16 output: x fp32 NHWC [B,H,W,C] (C % 4 == 0) -> y bf16 [ceil(B/g^2), g*ceil(H/2),
  * g*ceil(W/2), 4C], ONE nearest-even rounding per element, +0.0 where no source exists (16-byte stores where C % 8 == 0). */
 int witw_space_to_depth2_mosaic_bf16(const float* x, void* y_bf16, int B, int H, int W, int C, int g, void* stream);
+/* ---- cvig_baseline TRAINING with bf16 operands (blocks 2-4 under train_precision='bf16': forward, data gradient and weight gradient
+ * of model/cvig_baseline.py:241-249, 267-275 on the bf16 MFMA with fp32 accumulation; BatchNorm, LeakyReLU gates, pooling, blocks 1 and
+ * 5-7, the loss and Adam stay on the fp32 entries). Rounded (nearest-even, once): the filter, a block's input, a block's output gradient.
+ * pack_weights_taps4_ex: witw_conv3x3_bf16_pack_weights_taps4 with transpose_flip as in witw_conv3x3_pack_weights_taps4: != 0 packs taps
+ *   {0,1}^2 of the data-gradient filter, (cout, cin) describe the PACKED filter, the source is [cin][cout][3][3]:
+ *   packed tap (ty, tx) of (co, ci) = bf16(w[ci][co][2-ty][2-tx]). transpose_flip == 0 is the entry without _ex.
+ * fwd_taps4_plain: x NHWC bf16 [B,H,W,Cin] (Cin % 16 == 0), bias fp32 [Cout] or NULL, off = 1 - tap_base ->
+ *   y[b,r,c,n] = act(sum_{ty,tx in {0,1}} sum_ci x[b,r+ty-off,c+tx-off,ci] * wpk[n,ci,tap (ty,tx)] + bias[n])   for r < valid_h, c < valid_w,
+ *   +0.0 elsewhere (x zero outside [0,H) x [0,W)); act = LeakyReLU(lrelu_slope) when lrelu != 0, else none; y fp32 [B,H,W,Cout], every
+ *   element written, never rounded: the layout witw_conv3x3_fwd_taps4 gives and witw_bn_train_stats / witw_bn_lrelu_bwd_ex read. tap_base = 1
+ *   with a forward-packed filter is the block's forward, tap_base = 0 with a transpose_flip-packed one its data gradient. Any Cout >= 1.
+ * space_to_depth2_bf16: witw_space_to_depth2 for an NHWC source with C % 4 == 0 and Cpad == 4C, bf16 out: y[b,h2,w2,(dy*2+dx)*C+c] =
+ *   bf16(x[b,2h2+dy,2w2+dx,c] * scale[c] + shift[c]) inside the H x W valid region (fp32 multiply, then add, one rounding), +0.0 outside
+ *   it whatever the shift; scale / shift both NULL: no affine. 16-byte stores where C % 8 == 0.
+ * f32_to_bf16: y[i] = bf16(x[i]), i < n.
+ * wgrad_bf16_taps4: x [B,H,W,Cin] (Cin % 8 == 0), dz [B,H,W,Cout] (Cout % 4 == 0), both NHWC bf16 ->
+ *   dw[n, ci, 1+ty, 1+tx] (+)= sum_{b,r,c} dz[b,r,c,n] * x[b,r+ty,c+tx,ci]   (x zero past H / W; ci < cin_real; fp32 sums),
+ *   db[n] (+)= sum_{b,r,c} dz[b,r,c,n] (db may be NULL); dw [Cout][cin_real][3][3] fp32, the five taps outside {1,2}^2 +0 (accumulate == 0)
+ *   or untouched. The weight-gradient contract above holds (workspace of witw_conv3x3_wgrad_bf16_taps4_workspace_floats floats, fixed
+ *   split order: bitwise reproducible). */
+int witw_conv3x3_bf16_pack_weights_taps4_ex(const float* w_kcrs, void* wpk_bf16, int cout, int cin, int transpose_flip, void* stream);
+int witw_conv3x3_bf16_fwd_taps4_plain(const void* x_bf16, const void* wpk_bf16, const float* bias, float* y, int B, int H, int W, int Cin,
+                                      int Cout, int lrelu, float lrelu_slope, int tap_base, int valid_h, int valid_w, void* stream);
+int witw_space_to_depth2_bf16(const float* x, void* y_bf16, int B, int Hp, int Wp, int H, int W, int C, const float* scale,
+                              const float* shift, void* stream);
+int witw_f32_to_bf16(const float* x, void* y_bf16, long long n, void* stream);
+long long witw_conv3x3_wgrad_bf16_taps4_workspace_floats(int B, int H, int W, int Cin, int Cout);
+int witw_conv3x3_wgrad_bf16_taps4(const void* x_nhwc, const void* dz_nhwc, float* dw, float* db, float* workspace, int B, int H, int W,
+                                  int Cin, int cin_real, int Cout, int accumulate, void* stream);
 int witw_space_to_depth2(const float* x, float* y, int B, int Hp, int Wp, int H, int W, int C, int Cpad, int in_nchw,
                          int normalize, const float* scale, const float* shift, void* stream);
 /* Mosaic space-to-depth: x NHWC [B,H,W,C] (C % 4 == 0) -> y [ceil(B/g^2), g*ceil(H/2), g*ceil(W/2), 4C]: image b is cell b % g^2

@@ -86,6 +86,12 @@ SIGNATURES = {
     'witw_conv3x3_bf16_taps4_ksplit': (c_int, [c_int] * 5),
     'witw_conv3x3_bf16_fwd_taps4_splitk': (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p]),
     'witw_space_to_depth2_mosaic_bf16': (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
+    'witw_conv3x3_bf16_pack_weights_taps4_ex': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'witw_conv3x3_bf16_fwd_taps4_plain': (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_float] + [c_int] * 3 + [c_void_p]),
+    'witw_space_to_depth2_bf16': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 3),
+    'witw_f32_to_bf16': (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
+    'witw_conv3x3_wgrad_bf16_taps4_workspace_floats': (c_longlong, [c_int] * 5),
+    'witw_conv3x3_wgrad_bf16_taps4': (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
     'witw_space_to_depth2': (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_void_p]),
     'witw_space_to_depth2_mosaic': (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     'witw_taps4_splitk_finish': (c_int, [c_void_p, c_int, c_void_p, c_int, c_float] + [c_void_p] * 3 + [c_int] * 7 + [c_void_p]),

@@ -2,27 +2,37 @@
 encoders at inference (SurfaceEncoder(precision='bf16')). With ops.conv4x4s2_first(out_bf16=True) they are the bf16 part of that
 forward and live here, not in ops.py; their memory-contract cases are in tests/test_baseline_bf16_gpu.py. No CPU fallback.
 precision='bf16_all' adds the wrappers of csrc/conv_taps4_splitk_bf16.hip for blocks 5-7: conv_taps4_splitk_bf16 and
-space_to_depth2_mosaic_bf16 (memory-contract cases in tests/test_baseline_bf16_all_gpu.py)."""
+space_to_depth2_mosaic_bf16 (memory-contract cases in tests/test_baseline_bf16_all_gpu.py).
+train_precision='bf16' (training: forward, data gradient and weight gradient of blocks 2-4) adds the transpose_flip packing,
+conv_taps4_plain_bf16, space_to_depth2_bf16, to_bf16 and conv3x3_wgrad_bf16_taps4 (tests/test_baseline_bf16_train_gpu.py)."""
 import torch
 
 from . import _lib
-from .ops import _Packed, _dev_f32, _p, _prof_begin, _prof_end, _stream
+from .ops import _Packed, _dev_f32, _p, _prof_begin, _prof_end, _stream, _wgrad_setup
 
 
 class PackedConvBf16Taps4(_Packed):
     """bf16 packing of the taps {1,2}^2 of one [cout][cin][3][3] filter (ops.conv4x4_to_k3 of a Conv2d(k=4, s=2)) for conv_taps4_s2d_bf16
-    + the fp32 bias. Forward filters only: cvig_baseline's bf16 arithmetic is inference."""
+    + the fp32 bias. transpose_flip (training only, conv_taps4_plain_bf16 with tap_base = 0): the taps {0,1}^2 of the data-gradient filter
+    w_t[ci][co][kh][kw] = w[co][ci][2-kh][2-kw] instead, no bias."""
     CPAD, DTYPE = 16, torch.bfloat16
     taps4 = True
 
-    def __init__(self, weight, bias, reuse=None):
+    def __init__(self, weight, bias, reuse=None, transpose_flip=False):
         lib = _lib.load()
-        w, reuse = self._filter_buffer(weight, False, reuse, lib.witw_conv3x3_bf16_packed_elems_taps4)
+        self.tap_base = 0 if transpose_flip else 1
+        if reuse is not None and getattr(reuse, 'tap_base', 1) != self.tap_base:
+            reuse = None
+        w, reuse = self._filter_buffer(weight, bool(transpose_flip), reuse, lib.witw_conv3x3_bf16_packed_elems_taps4)
         if tuple(w.shape[2:]) != (3, 3):
             raise _lib.WitwError('PackedConvBf16Taps4: expects a [cout, cin, 3, 3] filter, got %s' % (tuple(w.shape),))
-        _lib.check(lib.witw_conv3x3_bf16_pack_weights_taps4(w.data_ptr(), self.wpk.data_ptr(), self.cout, self.cin, _stream()),
-                   'witw_conv3x3_bf16_pack_weights_taps4')
-        self._bias_buffer(reuse, bias)
+        if transpose_flip:
+            _lib.check(lib.witw_conv3x3_bf16_pack_weights_taps4_ex(w.data_ptr(), self.wpk.data_ptr(), self.cout, self.cin, 1, _stream()),
+                       'witw_conv3x3_bf16_pack_weights_taps4_ex')
+        else:
+            _lib.check(lib.witw_conv3x3_bf16_pack_weights_taps4(w.data_ptr(), self.wpk.data_ptr(), self.cout, self.cin, _stream()),
+                       'witw_conv3x3_bf16_pack_weights_taps4')
+        self._bias_buffer(reuse, None if transpose_flip else bias)
 
 
 def conv_taps4_s2d_bf16(x_nhwc, packed, valid_hw, lrelu_slope=0.2, post_scale=None, post_shift=None, out_f32=False):
@@ -32,8 +42,8 @@ def conv_taps4_s2d_bf16(x_nhwc, packed, valid_hw, lrelu_slope=0.2, post_scale=No
     lib = _lib.load()
     if not (isinstance(x_nhwc, torch.Tensor) and x_nhwc.is_cuda and x_nhwc.dtype == torch.bfloat16 and x_nhwc.is_contiguous() and x_nhwc.dim() == 4):
         raise _lib.WitwError('conv_taps4_s2d_bf16: x must be a contiguous bfloat16 NHWC GPU tensor (no CPU fallback)')
-    if not isinstance(packed, PackedConvBf16Taps4):
-        raise _lib.WitwError('conv_taps4_s2d_bf16: a PackedConvBf16Taps4 filter is required')
+    if not isinstance(packed, PackedConvBf16Taps4) or packed.tap_base != 1:
+        raise _lib.WitwError('conv_taps4_s2d_bf16: a forward-packed PackedConvBf16Taps4 filter is required')
     B, H, W, C = x_nhwc.shape
     if C != packed.cin_pad:
         raise _lib.WitwError('conv_taps4_s2d_bf16: input has %d channels, packed weights expect %d' % (C, packed.cin_pad))
@@ -65,8 +75,8 @@ def conv_taps4_splitk_bf16(x_mosaic_bf16, packed, n_images, g, valid_hw, lrelu_s
     x = x_mosaic_bf16
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 4):
         raise _lib.WitwError('conv_taps4_splitk_bf16: x must be a contiguous bfloat16 NHWC GPU tensor (no CPU fallback)')
-    if not isinstance(packed, PackedConvBf16Taps4):
-        raise _lib.WitwError('conv_taps4_splitk_bf16: a PackedConvBf16Taps4 filter is required')
+    if not isinstance(packed, PackedConvBf16Taps4) or packed.tap_base != 1:
+        raise _lib.WitwError('conv_taps4_splitk_bf16: a forward-packed PackedConvBf16Taps4 filter is required')
     Bm, H, W, C = x.shape
     n_images, g = int(n_images), int(g)
     if g < 1 or n_images < 1 or H % g or W % g or Bm != (n_images + g * g - 1) // (g * g):
@@ -116,3 +126,92 @@ def space_to_depth2_mosaic_bf16(y_f32, g=1):
     out = torch.empty(((B + g * g - 1) // (g * g), g * ((H + 1) // 2), g * ((W + 1) // 2), 4 * C), dtype=torch.bfloat16, device=y.device)
     _lib.check(lib.witw_space_to_depth2_mosaic_bf16(y.data_ptr(), out.data_ptr(), B, H, W, C, g, _stream()), 'witw_space_to_depth2_mosaic_bf16')
     return out
+
+
+# ----------------------------------------------------------------------------- training (train_precision='bf16')
+def _bf16_nhwc(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and t.dim() == 4):
+        raise _lib.WitwError('%s must be a contiguous bfloat16 NHWC GPU tensor (no CPU fallback)' % name)
+    return t
+
+
+def conv_taps4_plain_bf16(x_nhwc, packed, valid_hw=None, lrelu_slope=None):
+    """ops.conv3x3_fwd with a taps4 filter on bf16 operands with fp32 accumulation (witw_conv3x3_bf16_fwd_taps4_plain): x bf16
+    [B,H,W,Cin_pad], packed a PackedConvBf16Taps4 -> fp32 [B,H,W,Cout] in the plain layout, never rounded, +0.0 outside the (vh, vw)
+    valid outputs (None: all of H x W). A forward-packed filter (tap_base 1) adds its bias, then LeakyReLU when lrelu_slope is given:
+    a block's forward; a transpose_flip-packed one (tap_base 0) has neither: the block's data gradient."""
+    lib = _lib.load()
+    x = _bf16_nhwc(x_nhwc, 'conv_taps4_plain_bf16: x')
+    if not isinstance(packed, PackedConvBf16Taps4):
+        raise _lib.WitwError('conv_taps4_plain_bf16: a PackedConvBf16Taps4 filter is required')
+    B, H, W, C = x.shape
+    if C != packed.cin_pad:
+        raise _lib.WitwError('conv_taps4_plain_bf16: input has %d channels, packed weights expect %d' % (C, packed.cin_pad))
+    if packed.tap_base == 0 and lrelu_slope is not None:
+        raise _lib.WitwError('conv_taps4_plain_bf16: a data-gradient filter takes no activation')
+    vh, vw = (H, W) if valid_hw is None else (int(v) for v in valid_hw)
+    if not (1 <= vh <= H and 1 <= vw <= W):
+        raise _lib.WitwError('conv_taps4_plain_bf16: valid region %dx%d outside the %dx%d map' % (vh, vw, H, W))
+    y = torch.empty((B, H, W, packed.cout), dtype=torch.float32, device=x.device)
+    prof = _prof_begin()
+    _lib.check(lib.witw_conv3x3_bf16_fwd_taps4_plain(x.data_ptr(), packed.wpk.data_ptr(), packed.bias.data_ptr() if packed.tap_base else None,
+                                                     y.data_ptr(), B, H, W, C, packed.cout, int(lrelu_slope is not None),
+                                                     float(lrelu_slope or 0.), packed.tap_base, vh, vw, _stream()),
+               'witw_conv3x3_bf16_fwd_taps4_plain')
+    if prof is not None:
+        _prof_end(prof, ('bf16_taps4_plain', 128, 1, False), 2.0 * packed.cin * packed.cout * 4 * vh * vw * B, kernel=True)
+    return y
+
+
+def space_to_depth2_bf16(x_nhwc, valid_hw=None, scale=None, shift=None):
+    """ops.space_to_depth2 of an NHWC activation with one nearest-even rounding at a bf16 store: x fp32 [B,Hp,Wp,C] (C % 4 == 0) -> bf16
+    [B, ceil(vh/2), ceil(vw/2), 4C], the train-mode BatchNorm affine (scale, shift: [C]) applied on the fly, +0.0 outside the valid region."""
+    lib = _lib.load()
+    x = _dev_f32(x_nhwc, 'x')
+    if x.dim() != 4 or x.shape[3] % 4:
+        raise _lib.WitwError('space_to_depth2_bf16: x must be NHWC with C %% 4 == 0, got %s' % (tuple(x.shape),))
+    B, Hp, Wp, C = x.shape
+    H, W = (Hp, Wp) if valid_hw is None else (int(v) for v in valid_hw)
+    if not (1 <= H <= Hp and 1 <= W <= Wp):
+        raise _lib.WitwError('space_to_depth2_bf16: valid region %dx%d outside the %dx%d map' % (H, W, Hp, Wp))
+    if (scale is None) != (shift is None):
+        raise _lib.WitwError('space_to_depth2_bf16: scale and shift come together')
+    if scale is not None:
+        scale, shift = _dev_f32(scale, 'scale'), _dev_f32(shift, 'shift')
+        if scale.numel() != C or shift.numel() != C:
+            raise _lib.WitwError('space_to_depth2_bf16: scale / shift must have C entries')
+    y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, 4 * C), dtype=torch.bfloat16, device=x.device)
+    _lib.check(lib.witw_space_to_depth2_bf16(x.data_ptr(), y.data_ptr(), B, Hp, Wp, H, W, C, _p(scale), _p(shift), _stream()),
+               'witw_space_to_depth2_bf16')
+    return y
+
+
+def to_bf16(x):
+    """fp32 -> bf16 of the same shape, one nearest-even rounding per element (witw_f32_to_bf16): a block's output gradient dz."""
+    lib = _lib.load()
+    x = _dev_f32(x, 'x')
+    y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    if x.numel():
+        _lib.check(lib.witw_f32_to_bf16(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), 'witw_f32_to_bf16')
+    return y
+
+
+def conv3x3_wgrad_bf16_taps4(x_nhwc, dz_nhwc, cin_real, want_bias=True, out=None, accumulate=False):
+    """ops.conv3x3_wgrad(taps4=True) on bf16 operands with fp32 accumulation (witw_conv3x3_wgrad_bf16_taps4): x bf16 [B,H,W,Cin], dz bf16
+    [B,H,W,Cout] -> (dW [Cout,cin_real,3,3] fp32 with taps {1,2}^2 computed and exact zeros elsewhere, db [Cout] fp32 or None).
+    out = (dW, db): write into (accumulate: add to) these contiguous fp32 tensors."""
+    lib = _lib.load()
+    x, dz = _bf16_nhwc(x_nhwc, 'conv3x3_wgrad_bf16_taps4: x'), _bf16_nhwc(dz_nhwc, 'conv3x3_wgrad_bf16_taps4: dz')
+    B, H, W, Cin = x.shape
+    Cout = dz.shape[3]
+    if accumulate and out is None:
+        raise _lib.WitwError('conv3x3_wgrad_bf16_taps4: accumulate needs out')
+    _, dw, db = _wgrad_setup('conv3x3_wgrad_bf16_taps4', B, H, W, Cout, cin_real, 1, dz.shape[:3], x.device, want_bias, out)
+    n_ws = lib.witw_conv3x3_wgrad_bf16_taps4_workspace_floats(B, H, W, Cin, Cout)
+    ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
+    prof = _prof_begin()
+    _lib.check(lib.witw_conv3x3_wgrad_bf16_taps4(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), _p(db), ws.data_ptr(), B, H, W, Cin, cin_real,
+                                                 Cout, int(bool(accumulate)), _stream()), 'witw_conv3x3_wgrad_bf16_taps4')
+    if prof is not None:
+        _prof_end(prof, ('wgrad_bf16_taps4', 1), 2.0 * cin_real * Cout * 4 * H * W * B, kernel=True)
+    return dw, db

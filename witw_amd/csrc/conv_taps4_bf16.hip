@@ -14,6 +14,11 @@
 // Staging as in conv3x3_bf16.hip: the 9 x 33 halo tile goes global -> VGPR -> LDS (two planes of 8 channels, plane pitch a multiple
 // of 16 slots: the conflict-free pitch of the s16 kernel), the 16 KB weight slab by LDS-DMA (the packed image is the LDS image), two
 // stages, one barrier per chunk. The fragment reads are left to the compiler (DESIGN.md 4.11 says what that leaves).
+//
+// PLAIN form (training, blocks 2-4 under train_precision='bf16'): the same tile, staging and K loop, another store: fp32 [B,H,W,Cout] in
+// the plain NHWC layout the BatchNorm kernels read, +0.0 outside the valid region, bias / LeakyReLU optional, and a tap base:
+//   out[b, oy, ox, n] = sum_{ty,tx in {0,1}} sum_c x[b, oy+ty-off, ox+tx-off, c] * wpk[n, c, tap ty*2+tx]      off = 1 - tap_base
+// tap_base = 1 is the forward above; tap_base = 0 with a transpose_flip-packed filter is its data gradient (x zero outside [0,H) x [0,W)).
 #include "common.h"
 #include "conv_launch.h"
 #include "lds_frag.h"
@@ -38,9 +43,10 @@ struct Taps4BfArgs {
     int tiles_x, tiles_y;
     int n_tiles, sp_total, sp_per_xcd, xcd_map;
     float slope;
+    int off, act;               // PLAIN only: halo shift 1 - tap_base; LeakyReLU on / off
 };
 
-template <bool OUT_F32>
+template <bool OUT_F32, bool PLAIN = false>
 __global__ __launch_bounds__(64 * T4_NW) void conv_taps4_bf16_kernel(Taps4BfArgs p) {
     constexpr int TW = T4_TW, TH = T4_TH, TN = T4_TN, NW = T4_NW, NTHREADS = 64 * NW;
     constexpr int IH = TH + 1, IW = TW + 1;
@@ -97,8 +103,13 @@ __global__ __launch_bounds__(64 * T4_NW) void conv_taps4_bf16_kernel(Taps4BfArgs
         const int s = tid + i * NTHREADS;
         const int pix = s >> 1, q = s & 1;
         const int r = pix / IW, c = pix - r * IW;
-        const int gr = oy0 + r, gc = ox0 + c;
-        const bool ok = pix < IH * IW && gr < p.H && gc < p.W;
+        int gr = oy0 + r, gc = ox0 + c;
+        bool ok = pix < IH * IW && gr < p.H && gc < p.W;
+        if constexpr (PLAIN) {      // tap_base = 0: the halo row / column lie before the tile, and before the image they are zeros
+            gr -= p.off;
+            gc -= p.off;
+            ok = pix < IH * IW && gr >= 0 && gr < p.H && gc >= 0 && gc < p.W;
+        }
         gin[i] = ok ? (unsigned)((((size_t)gr * p.W + gc) * p.Cin + q * 8) * 2) : OOR;
     }
     u32x4 rin[NIN];
@@ -181,7 +192,7 @@ __global__ __launch_bounds__(64 * T4_NW) void conv_taps4_bf16_kernel(Taps4BfArgs
         for (int j = 0; j < 4; ++j) {
             const int ch = n0 + 64 * hn + 16 * j + l15;
             const bool in = ch < p.Cout;
-            bv[j] = in ? p.bias[ch] : 0.f;
+            bv[j] = (in && (!PLAIN || p.bias != nullptr)) ? p.bias[ch] : 0.f;
             ps[j] = (in && has_post) ? p.post_scale[ch] : 1.f;
             pt[j] = (in && has_post) ? p.post_shift[ch] : 0.f;
         }
@@ -194,7 +205,7 @@ __global__ __launch_bounds__(64 * T4_NW) void conv_taps4_bf16_kernel(Taps4BfArgs
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float v = acc[2 * rr + i][4 * hn + j][r] + bv[j];
-                        v = v > 0.f ? v : v * p.slope;
+                        if (!PLAIN || p.act) v = v > 0.f ? v : v * p.slope;
                         if (has_post) v = v * ps[j] + pt[j];
                         slab[(16 * i + 4 * kg + r) * SLAB_P + 16 * j + l15] = v;
                     }
@@ -208,8 +219,9 @@ __global__ __launch_bounds__(64 * T4_NW) void conv_taps4_bf16_kernel(Taps4BfArgs
                 const int xx = ox0 + m;
                 if (!(yy < p.valid_h && xx < p.valid_w)) v0 = v1 = f32x4{0.f, 0.f, 0.f, 0.f};      // +0.0 outside the valid region
                 if (yy < p.Ho && xx < p.Wo && nbase < p.Cout) {
-                    const size_t o =
-                        ((((size_t)b * p.s2d_h + (yy >> 1)) * p.s2d_w + (xx >> 1)) * 4 + (yy & 1) * 2 + (xx & 1)) * p.Cout + nbase;
+                    const size_t o = PLAIN
+                        ? (((size_t)b * p.Ho + yy) * p.Wo + xx) * p.Cout + nbase
+                        : ((((size_t)b * p.s2d_h + (yy >> 1)) * p.s2d_w + (xx >> 1)) * 4 + (yy & 1) * 2 + (xx & 1)) * p.Cout + nbase;
                     if (wide) {
                         if constexpr (OUT_F32) {
                             __builtin_nontemporal_store(v0, reinterpret_cast<f32x4*>(yo + o));
@@ -234,9 +246,11 @@ __global__ __launch_bounds__(64 * T4_NW) void conv_taps4_bf16_kernel(Taps4BfArgs
     }
 }
 
-// wpk[nt][kc][tap = ty*2+tx][g][n][0..7] (bf16, nearest-even) <- w[cout][cin][1+ty][1+tx] (fp32, torch KCRS); one thread per 16-B slot
+// wpk[nt][kc][tap = ty*2+tx][g][n][0..7] (bf16, nearest-even) <- w[cout][cin][1+ty][1+tx] (fp32, torch KCRS); one thread per 16-B slot.
+// transpose_flip: the data-gradient filter instead, as pack_weights_kernel of conv3x3.hip builds it: (Cout, Cin) describe the PACKED
+// filter, the source is [Cin][Cout][3][3], tap (ty, tx) holds w[ci][co][2-ty][2-tx] (taps {0,1}^2 of the transposed, rotated filter)
 __global__ void pack_weights_taps4_bf16_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpk, int Cout, int Cin, int nkc,
-                                               size_t total) {
+                                               size_t total, int transpose_flip) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     size_t t = idx;
@@ -245,23 +259,81 @@ __global__ void pack_weights_taps4_bf16_kernel(const float* __restrict__ w, unsi
     const int tap = t % 4; t /= 4;
     const int kc = t % nkc; t /= nkc;
     const int co = (int)t * T4_TN + n;
-    const int kh = 1 + (tap >> 1), kw = 1 + (tap & 1);
+    const int kh = transpose_flip ? 2 - (tap >> 1) : 1 + (tap >> 1), kw = transpose_flip ? 2 - (tap & 1) : 1 + (tap & 1);
     bf16x8 v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int ci = kc * 16 + g * 8 + j;
-        v[j] = (__bf16)((co < Cout && ci < Cin) ? w[(((size_t)co * Cin + ci) * 3 + kh) * 3 + kw] : 0.f);
+        const size_t src = transpose_flip ? (size_t)ci * Cout + co : (size_t)co * Cin + ci;
+        v[j] = (__bf16)((co < Cout && ci < Cin) ? w[(src * 3 + kh) * 3 + kw] : 0.f);
     }
     reinterpret_cast<bf16x8*>(wpk)[idx] = v;
 }
 
-template <bool OUT_F32>
+// witw_space_to_depth2 (NHWC source, Cp == 4C) with a bf16 store: one thread per V = 8 or 4 channels of one quadrant,
+// y[b,h2,w2,q*C+c] = bf16(x[b,2h2+(q>>1),2w2+(q&1),c] * scale[c] + shift[c]) inside the H x W valid region, +0.0 outside it (the
+// affine is NOT applied there). The fp32 arithmetic is space_to_depth2_quad_kernel's; one nearest-even rounding at the store.
+template <int V>
+__global__ void space_to_depth2_bf16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, int Hp, int Wp, int H, int W, int C,
+                                            size_t total, const float* __restrict__ scale, const float* __restrict__ shift) {
+    typedef __bf16 bf16xv __attribute__((ext_vector_type(V)));
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int H2 = (H + 1) >> 1, W2 = (W + 1) >> 1, CV = C / V;
+    const int cv = idx % CV;
+    size_t t = idx / CV;
+    const int q = t & 3;
+    t >>= 2;
+    const int w2 = t % W2;
+    t /= W2;
+    const int h2 = t % H2;
+    const size_t b = t / H2;
+    const int h = 2 * h2 + (q >> 1), w = 2 * w2 + (q & 1);
+    bf16xv o;
+#pragma unroll
+    for (int j = 0; j < V; ++j) o[j] = (__bf16)0.f;
+    if (h < H && w < W) {
+        const float* src = x + ((b * Hp + h) * Wp + w) * C + V * cv;
+#pragma unroll
+        for (int k = 0; k < V / 4; ++k) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * k);
+            if (scale != nullptr) {
+                const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + V * cv + 4 * k);
+                const f32x4 sf = *reinterpret_cast<const f32x4*>(shift + V * cv + 4 * k);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = v[j] * sc[j] + sf[j];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[4 * k + j] = (__bf16)v[j];
+        }
+    }
+    reinterpret_cast<bf16xv*>(y)[idx] = o;
+}
+
+// y[i] = bf16(x[i]), nearest-even: four elements per thread, the tail one at a time
+__global__ void f32_to_bf16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, size_t n) {
+    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+    const size_t i4 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i4 + 4 <= n) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + i4);
+        bf16x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (__bf16)v[j];
+        *reinterpret_cast<bf16x4*>(y + i4) = o;
+    } else {
+        __bf16* yb = reinterpret_cast<__bf16*>(y);
+        for (size_t i = i4; i < n; ++i) yb[i] = (__bf16)x[i];
+    }
+}
+
+template <bool OUT_F32, bool PLAIN = false>
 int launch_taps4_bf(Taps4BfArgs a, hipStream_t st) {
-    const long long grid = witw_conv_grid(a, T4_TH, T4_TN, "conv3x3_bf16_fwd_taps4");
+    const long long grid = witw_conv_grid(a, T4_TH, T4_TN, PLAIN ? "conv3x3_bf16_fwd_taps4_plain" : "conv3x3_bf16_fwd_taps4");
     if (!grid) return WITW_ERR_INVALID;
-    hipLaunchKernelGGL((conv_taps4_bf16_kernel<OUT_F32>), dim3((unsigned)grid), dim3(64 * T4_NW), 0, st, a);
+    hipLaunchKernelGGL((conv_taps4_bf16_kernel<OUT_F32, PLAIN>), dim3((unsigned)grid), dim3(64 * T4_NW), 0, st, a);
     WITW_CHECK_LAUNCH("conv_taps4_bf16");
-    witw_note_variant("conv_taps4_bf16_kernel<%s>", OUT_F32 ? "true" : "false");
+    if (PLAIN) witw_note_variant("conv_taps4_bf16_kernel<true,true>");
+    else witw_note_variant("conv_taps4_bf16_kernel<%s>", OUT_F32 ? "true" : "false");
     return WITW_OK;
 }
 
@@ -274,16 +346,20 @@ long long witw_conv3x3_bf16_packed_elems_taps4(int cout, int cin) {
     return (long long)cdiv(cout, T4_TN) * cdiv(cin, 16) * 4 * 2 * T4_TN * 8;
 }
 
-int witw_conv3x3_bf16_pack_weights_taps4(const float* w_kcrs, void* wpk_bf16, int cout, int cin, void* stream) {
+int witw_conv3x3_bf16_pack_weights_taps4_ex(const float* w_kcrs, void* wpk_bf16, int cout, int cin, int transpose_flip, void* stream) {
     WITW_CHECK_ARG(w_kcrs && wpk_bf16, "bf16 pack_weights_taps4: null pointer");
     WITW_CHECK_ARG(cout > 0 && cin > 0, "bf16 pack_weights_taps4: bad shape cout=%d cin=%d", cout, cin);
     const int nkc = cdiv(cin, 16);
     const size_t total = (size_t)cdiv(cout, T4_TN) * nkc * 4 * 2 * T4_TN;
     WITW_CHECK_ARG((total + 255) / 256 <= 0x7fffffffull, "bf16 pack_weights_taps4: grid too large");
     hipLaunchKernelGGL(pack_weights_taps4_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_kcrs,
-                       (unsigned short*)wpk_bf16, cout, cin, nkc, total);
+                       (unsigned short*)wpk_bf16, cout, cin, nkc, total, transpose_flip != 0);
     WITW_CHECK_LAUNCH("bf16 pack_weights_taps4");
     return WITW_OK;
+}
+
+int witw_conv3x3_bf16_pack_weights_taps4(const float* w_kcrs, void* wpk_bf16, int cout, int cin, void* stream) {
+    return witw_conv3x3_bf16_pack_weights_taps4_ex(w_kcrs, wpk_bf16, cout, cin, 0, stream);
 }
 
 // x NHWC bf16 [B,H,W,Cin] (Cin % 16 == 0), wpk from witw_conv3x3_bf16_pack_weights_taps4, bias / post_scale / post_shift fp32 [Cout]
@@ -311,9 +387,68 @@ int witw_conv3x3_bf16_fwd_taps4(const void* x_bf16, const void* wpk_bf16, const 
     a.tiles_x = cdiv(a.Wo, T4_TW);
     a.tiles_y = 0;
     a.slope = lrelu_slope;
+    a.off = 0; a.act = 1;
     a.xcd_map = witw_conv_xcd_map();
     hipStream_t st = (hipStream_t)stream;
     return out_f32 ? launch_taps4_bf<true>(a, st) : launch_taps4_bf<false>(a, st);
+}
+
+// The PLAIN form: x NHWC bf16 [B,H,W,Cin] (Cin % 16 == 0), wpk from witw_conv3x3_bf16_pack_weights_taps4_ex, bias fp32 [Cout] or NULL
+// -> y fp32 [B,H,W,Cout] = act(conv + bias) for rows < valid_h and columns < valid_w, +0.0 elsewhere; every element of y is written.
+int witw_conv3x3_bf16_fwd_taps4_plain(const void* x_bf16, const void* wpk_bf16, const float* bias, float* y, int B, int H, int W, int Cin,
+                                      int Cout, int lrelu, float lrelu_slope, int tap_base, int valid_h, int valid_w, void* stream) {
+    WITW_CHECK_ARG(x_bf16 && wpk_bf16 && y, "conv3x3_bf16_fwd_taps4_plain: null pointer");
+    WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cout > 0, "conv3x3_bf16_fwd_taps4_plain: bad shape B=%d H=%d W=%d Cout=%d", B, H, W, Cout);
+    WITW_CHECK_ARG(Cin > 0 && (Cin % 16) == 0, "conv3x3_bf16_fwd_taps4_plain: Cin=%d must be a positive multiple of 16", Cin);
+    WITW_CHECK_ARG(tap_base == 0 || tap_base == 1, "conv3x3_bf16_fwd_taps4_plain: tap_base=%d must be 0 or 1", tap_base);
+    WITW_CHECK_ARG(valid_h > 0 && valid_w > 0 && valid_h <= H && valid_w <= W,
+                   "conv3x3_bf16_fwd_taps4_plain: valid region %dx%d outside the %dx%d map", valid_h, valid_w, H, W);
+    WITW_CHECK_ARG((size_t)H * W * Cin * 2 < 0x80000000ull, "conv3x3_bf16_fwd_taps4_plain: image too large for one buffer descriptor");
+    WITW_CHECK_ARG((size_t)cdiv(Cout, T4_TN) * Cin * (4 * T4_TN * 2) < 0x80000000ull,
+                   "conv3x3_bf16_fwd_taps4_plain: packed filter too large for one buffer descriptor");
+    Taps4BfArgs a;
+    a.x = (const unsigned short*)x_bf16; a.wpk = (const unsigned short*)wpk_bf16; a.bias = bias;
+    a.post_scale = nullptr; a.post_shift = nullptr; a.y = y;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+    a.valid_h = valid_h; a.valid_w = valid_w;
+    a.s2d_h = 0; a.s2d_w = 0;
+    a.Ho = H; a.Wo = W;
+    a.tiles_x = cdiv(a.Wo, T4_TW);
+    a.tiles_y = 0;
+    a.slope = lrelu_slope;
+    a.off = 1 - tap_base; a.act = lrelu != 0;
+    a.xcd_map = witw_conv_xcd_map();
+    return launch_taps4_bf<true, true>(a, (hipStream_t)stream);
+}
+
+// x fp32 NHWC [B,Hp,Wp,C] (C % 4 == 0) with valid region H x W, scale / shift fp32 [C] or both NULL -> y bf16 [B, ceil(H/2), ceil(W/2), 4C]
+int witw_space_to_depth2_bf16(const float* x, void* y_bf16, int B, int Hp, int Wp, int H, int W, int C, const float* scale,
+                              const float* shift, void* stream) {
+    WITW_CHECK_ARG(x && y_bf16, "space_to_depth2_bf16: null pointer");
+    WITW_CHECK_ARG(B > 0 && C > 0 && (C & 3) == 0 && H > 0 && W > 0 && H <= Hp && W <= Wp, "space_to_depth2_bf16: bad shape (C=%d must be a multiple of 4)", C);
+    WITW_CHECK_ARG((scale == nullptr) == (shift == nullptr), "space_to_depth2_bf16: scale and shift go together");
+    const int V = (C & 7) == 0 ? 8 : 4;
+    const size_t total = (size_t)B * ((H + 1) / 2) * ((W + 1) / 2) * 4 * (C / V);
+    WITW_CHECK_ARG((total + 255) / 256 <= 0x7fffffffULL, "space_to_depth2_bf16: tensor too large");
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (V == 8)
+        hipLaunchKernelGGL(space_to_depth2_bf16_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, x, (unsigned short*)y_bf16, Hp, Wp, H, W, C,
+                           total, scale, shift);
+    else
+        hipLaunchKernelGGL(space_to_depth2_bf16_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, (unsigned short*)y_bf16, Hp, Wp, H, W, C,
+                           total, scale, shift);
+    WITW_CHECK_LAUNCH("space_to_depth2_bf16");
+    return WITW_OK;
+}
+
+int witw_f32_to_bf16(const float* x, void* y_bf16, long long n, void* stream) {
+    WITW_CHECK_ARG(x && y_bf16 && n > 0, "f32_to_bf16: null pointer or n <= 0");
+    const size_t threads = ((size_t)n + 3) / 4;
+    WITW_CHECK_ARG((threads + 255) / 256 <= 0x7fffffffULL, "f32_to_bf16: tensor too large");
+    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
+                       (unsigned short*)y_bf16, (size_t)n);
+    WITW_CHECK_LAUNCH("f32_to_bf16");
+    return WITW_OK;
 }
 
 }  // extern "C"

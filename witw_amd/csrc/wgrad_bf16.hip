@@ -248,9 +248,13 @@ constexpr int NH_XP = 24;               // pixel pitch of a halo row in the LDS 
 // rows (k-steps) into KS contiguous blocks, one per wave group: every wave has MFMA work on its own rows instead of multiplying
 // zeros (cvig_semantic's layer 0, 5 -> 64 channels on 128 x 512 maps, ran 2 of 8 waves' worth of useful MFMAs and was MFMA-bound
 // where it should be HBM-bound). The wave groups' sums are added in the LDS at the end of the kernel (fixed order).
-template <int SH, int R, int NS, int NWM, int NWN>
+// T4 (cvig_baseline's blocks 2-4 under train_precision='bf16'): only the taps (kh, kw) in {1,2}^2, the live ones of a Conv2d(k=4, s=2)
+// as a 2x2 convolution over the space-to-depth image -- 4 accumulators and 4 MFMAs per k-step instead of 9, the same staging (the halo
+// row and column in front of the tile are staged and not read), partials [split][4][Cin][Cout] with tap t = (kh-1)*2 + (kw-1).
+template <int SH, int R, int NS, int NWM, int NWN, bool T4 = false>
 __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16_nhwc_kernel(WgradNhArgs p) {
     constexpr int NW = 8;
+    constexpr int NT = T4 ? 4 : 9;                    // taps computed
     constexpr int KS = NW / (NWM * NWN);              // wave groups along k (rows of the stage)
     constexpr int RW = R / KS;                        // output rows per wave and stage
     static_assert(NWM * NWN * KS == NW && RW * KS == R && RW >= 1, "8 waves = NWM x NWN x KS; the rows split evenly");
@@ -343,9 +347,9 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16_nhwc_kernel(WgradNhArg
         for (int k = 0; k < NSLOT; ++k) stage_slot(k);
     };
 
-    f32x16 acc[9];
+    f32x16 acc[NT];
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+    for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
@@ -394,6 +398,7 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16_nhwc_kernel(WgradNhArg
     // Spread only where every wave owns all R rows of the stage (KS = 1: the 128-channel layers, 2-3 % faster); where the waves split
     // the rows (narrow layers: few MFMAs per wave and stage) the block in front of the MFMAs measured 2-7 % faster and is kept
     constexpr bool SPREAD = KS == 1;
+    static_assert(!T4 || !SPREAD || PER_ROW * EVERY <= NT, "a row's 4 MFMAs carry its DMA slots");
     auto compute = [&](int buf, bool prefetch) {
         const unsigned char* sb = lds + buf * STAGE_B;
         constexpr int XRW = (RW - 1) * SH + 3;      // halo rows of this wave's RW output rows
@@ -414,8 +419,9 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16_nhwc_kernel(WgradNhArg
                     for (int kw = 0; kw < 3; ++kw) fx[j][kw] = frag(sb, a_lane[kw] + (unsigned)(j * NH_XP * 128));
             }
 #pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[r * SH + t / 3][t % 3], fb, acc[t], 0, 0, 0);
+            for (int t = 0; t < NT; ++t) {
+                const int kh = T4 ? 1 + (t >> 1) : t / 3, kw = T4 ? 1 + (t & 1) : t % 3;
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[r * SH + kh][kw], fb, acc[t], 0, 0, 0);
                 // the next stage's DMA slots of this row, one behind every other MFMA
                 if (SPREAD && r < ROWS_PF && (t % EVERY) == EVERY - 1 && r * PER_ROW + t / EVERY < min(NSLOT, (r + 1) * PER_ROW)) {
                     if (prefetch) stage_slot(r * PER_ROW + t / EVERY);
@@ -464,10 +470,10 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16_nhwc_kernel(WgradNhArg
     if (KS > 1) {
         float* red = reinterpret_cast<float*>(lds);
 #pragma unroll
-        for (int t = 0; t < 10; ++t) {                 // t = 9: the two bias tiles
+        for (int t = 0; t < NT + 1; ++t) {             // t = NT: the two bias tiles
             __syncthreads();                           // the stage buffers / the previous tap's exchange have been read
             if (ks > 0) {
-                if (t < 9) {
+                if (t < NT) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) red[(wave_u * 16 + r) * 64 + lane] = acc[t][r];
                 } else {
@@ -482,7 +488,7 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16_nhwc_kernel(WgradNhArg
 #pragma unroll 1
                 for (int k = 1; k < KS; ++k) {
                     const int src = wave_u + k * (NWM * NWN);
-                    if (t < 9) {
+                    if (t < NT) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) acc[t][r] += red[(src * 16 + r) * 64 + lane];
                     } else {
@@ -498,9 +504,9 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16_nhwc_kernel(WgradNhArg
     }
 
     // ---- partial tile -> workspace [split][tap][ci][co]
-    float* out = p.ws + (size_t)split * 9 * p.Cin * p.Cout;
+    float* out = p.ws + (size_t)split * NT * p.Cin * p.Cout;
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
+    for (int t = 0; t < NT; ++t) {
         const int co = co0 + wn * 32 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -880,6 +886,61 @@ int witw_conv3x3_wgrad_bf16_nhwc(const void* x_nhwc, const void* dz_nhwc, float*
         return rc;
     if (k16) witw_note_variant("conv3x3_wgrad_bf16_nhwc16_kernel<%d,%d>", stride_h, t.rows);
     else witw_note_variant("conv3x3_wgrad_bf16_nhwc_kernel<%d,%d,%d,%d>", stride_h, t.rows, nwm, nwn);
+    return WITW_OK;
+}
+
+// ---- the 2x2 sub-window form (witw_conv3x3_wgrad_taps4 on bf16 operands): stride 1, zero padding, always the 32x32x16 kernel
+static WgradTiling wgrad_nh_t4_tiling() { return {witw_cu_count(), WB_TM, WB_TN, wgrad_nh_rows(1), NH_P}; }
+
+long long witw_conv3x3_wgrad_bf16_taps4_workspace_floats(int B, int H, int W, int Cin, int Cout) {
+    const WgradGeom g = wgrad_geom(wgrad_nh_t4_tiling(), B, 1, H, W, Cin, Cout, 1);
+    return wgrad_workspace_floats(g, g.splits, Cout);
+}
+
+// x [B][H][W][Cin], dz [B][H][W][Cout] bf16 NHWC (Cin % 8 == 0, Cout % 4 == 0) -> taps {1,2}^2 of dw [Cout][cin_real][3][3] fp32:
+//   dw[n, ci, 1+ty, 1+tx] (+)= sum_{b,r,c} dz[b,r,c,n] * x[b,r+ty,c+tx,ci]        (x zero past H / W)
+// the five other taps exact zeros (accumulate == 0) or untouched; db [Cout] (+)= sum dz, or NULL.
+int witw_conv3x3_wgrad_bf16_taps4(const void* x_nhwc, const void* dz_nhwc, float* dw, float* db, float* workspace, int B, int H, int W,
+                                  int Cin, int cin_real, int Cout, int accumulate, void* stream) {
+    WgradGeom g;
+    if (int rc = wgrad_prologue(g, "conv3x3_wgrad_bf16_taps4", 4, wgrad_nh_t4_tiling(), B, 1, x_nhwc, dz_nhwc, dw, db, workspace, B, H, W, Cin,
+                                cin_real, Cout, 1))
+        return rc;
+    WITW_CHECK_ARG((Cin % 8) == 0, "conv3x3_wgrad_bf16_taps4: Cin=%d must be a multiple of 8", Cin);
+    WITW_CHECK_ARG((size_t)B * H * W * Cin * 2 < 0x80000000ull && (size_t)B * H * W * Cout * 2 < 0x80000000ull,
+                   "conv3x3_wgrad_bf16_taps4: operand too large for one buffer descriptor");
+    hipStream_t st = (hipStream_t)stream;
+    WgradNhArgs a;
+    a.x = (const unsigned short*)x_nhwc; a.dz = (const unsigned short*)dz_nhwc; a.ws = workspace;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Ho = g.Ho; a.Wo = W;
+    a.circ = 0;
+    a.nseg = g.nseg; a.nrg = g.nrg; a.chunks = g.chunks; a.cps = g.cps;
+    a.tiles_ci = cdiv(Cin, WB_TM); a.tiles_co = cdiv(Cout, WB_TN);
+    a.splits = g.splits;
+    a.bias_part = g.bias_part;
+    int nwm, nwn;
+    wgrad_nh_roles(Cin, Cout, 1, &nwm, &nwn);
+    const dim3 grid((unsigned)(a.tiles_ci * a.tiles_co * a.splits));
+    // the five taps outside the 2x2 sub-window get an exact zero gradient
+    if (!accumulate && hipMemsetAsync(dw, 0, sizeof(float) * (size_t)Cout * cin_real * 9, st) != hipSuccess) {
+        witw_set_error("conv3x3_wgrad_bf16_taps4: memset failed");
+        return WITW_ERR_LAUNCH;
+    }
+#define WITW_NH4_LAUNCH(NWM_, NWN_) hipLaunchKernelGGL((conv3x3_wgrad_bf16_nhwc_kernel<1, 8, 2, NWM_, NWN_, true>), grid, dim3(512), 0, st, a)
+    if (nwm == 2) {
+        if (nwn == 4) WITW_NH4_LAUNCH(2, 4);
+        else if (nwn == 2) WITW_NH4_LAUNCH(2, 2);
+        else WITW_NH4_LAUNCH(2, 1);
+    } else {
+        if (nwn == 4) WITW_NH4_LAUNCH(1, 4);
+        else if (nwn == 2) WITW_NH4_LAUNCH(1, 2);
+        else WITW_NH4_LAUNCH(1, 1);
+    }
+#undef WITW_NH4_LAUNCH
+    WITW_CHECK_LAUNCH("conv3x3_wgrad_bf16_taps4");
+    if (int rc = witw_wgrad_reduce(workspace, g.bias_part, dw, db, Cin, cin_real, Cout, 4, g.parts, g.splits, accumulate, WGRAD_SERIAL, stream))
+        return rc;
+    witw_note_variant("conv3x3_wgrad_bf16_nhwc_kernel<1,8,%d,%d,taps4>", nwm, nwn);
     return WITW_OK;
 }
 

@@ -32,7 +32,11 @@ class Globals:
     precision = 'fp32'       # arithmetic of the encoders' eval forward: 'fp32', 'bf16' (blocks 1-4 on the bf16 MFMA) or 'bf16_all' (all seven); bf16 is inference only
 
 
+    train_precision = 'fp32'  # arithmetic of the training step: 'fp32', or 'bf16' (forward, data and weight gradient of blocks 2-4 on the bf16 MFMA)
+
+
 PRECISIONS = ('fp32', 'bf16', 'bf16_all')
+TRAIN_PRECISIONS = ('fp32', 'bf16')
 
 
 # how many units make one full turn of the panorama, per first letter of the unit name; None: the shift already is in pixels
@@ -150,16 +154,23 @@ class SurfaceEncoder(nn.Module):
     """model/cvig_baseline.py:228-279; parameters live in nn.Conv2d / nn.BatchNorm2d children named
     conv1..7 / bn1..7 (same state-dict keys), the forward runs on the HIP kernels."""
 
-    def __init__(self, orientation=False, bands=3, p=3., precision=None):
+    def __init__(self, orientation=False, bands=3, p=3., precision=None, train_precision=None):
         """precision: None = Globals.precision; 'fp32', or 'bf16' = the eval forward runs blocks 1-4 with bf16 operands and fp32
         accumulation (bf16 activations between them, fp32 into block 5; the filters are rounded from the fp32 master weights, the
         BatchNorm fold, blocks 5-7, pooling and normalisation stay fp32); 'bf16_all' = blocks 5-7 as well: block 4 stores bf16, blocks
         5-7 run the bf16 split-K convolution over bf16 mosaics (baseline_bf16.conv_taps4_splitk_bf16), their fp32 outputs are pooled
-        unrounded and rounded once on the way into the next block. Training is fp32 only."""
+        unrounded and rounded once on the way into the next block. `precision` never changes the training step.
+        train_precision: None = Globals.train_precision; 'fp32', or 'bf16' = the training step runs the three convolutions of blocks 2-4
+        (forward, data gradient, weight gradient) with bf16 operands and fp32 accumulation. Rounded once, nearest-even: the filters (from
+        the fp32 master weights, per weight version), a block's input and a block's output gradient. Master weights, gradients, BatchNorm
+        statistics, LeakyReLU gates, blocks 1 and 5-7, pooling and the loss stay fp32. At most 5 input channels, as precision='bf16'."""
         super().__init__()
         self.precision = Globals.precision if precision is None else precision
         if self.precision not in PRECISIONS:
             raise _lib.WitwError("cvig_baseline encoder: precision must be 'fp32', 'bf16' or 'bf16_all', got %r" % (self.precision,))
+        self.train_precision = Globals.train_precision if train_precision is None else train_precision
+        if self.train_precision not in TRAIN_PRECISIONS:
+            raise _lib.WitwError("cvig_baseline encoder: train_precision must be 'fp32' or 'bf16', got %r" % (self.train_precision,))
         self.orientation, self.bands, self.p = orientation, bands, p
         self.inputs = self.bands + 2 * self.orientation
         widths = [self.inputs, 64, 128, 256, 512, 512, 512, 512]
@@ -219,8 +230,18 @@ class SurfaceEncoder(nn.Module):
             self._packed[('bf16', i)] = hit
         return hit[1]
 
-    def _layer_k3(self, i):
-        self._layer(i, fold=False)
+    def _layer_bf16_t(self, i):
+        """the bf16 data-gradient filter of block i (_layer_t's, rounded once), re-packed in place when the weights have changed"""
+        self._layer(i, fold=False, pack=False)
+        wkey, k3 = self._packed[i][0], self._packed[i][3]
+        hit = self._packed.get(('bf16_t', i))
+        if hit is None or hit[0] != wkey:
+            hit = (wkey, baseline_bf16.PackedConvBf16Taps4(k3, None, reuse=hit[1] if hit else None, transpose_flip=True))
+            self._packed[('bf16_t', i)] = hit
+        return hit[1]
+
+    def _layer_k3(self, i, pack=True):
+        self._layer(i, fold=False, pack=pack)
         return self._packed[i][3]
 
     def _layer_t(self, i):
@@ -252,8 +273,11 @@ class SurfaceEncoder(nn.Module):
             raise _lib.WitwError('cvig_baseline encoder needs sides >= 382 px, got %dx%d' % (H, W))
         bf16 = self.precision in ('bf16', 'bf16_all')
         bf16_all = self.precision == 'bf16_all'
-        if bf16 and self.training:
+        bf16_train = self.training and self.train_precision == 'bf16'
+        if bf16 and self.training and not bf16_train:
             raise _lib.WitwError("cvig_baseline encoder: precision='%s' is inference only -- fp32 is the only training arithmetic" % self.precision)
+        if bf16_train and self.inputs > 5:
+            raise _lib.WitwError("cvig_baseline encoder: train_precision='bf16' takes at most 5 input channels, got %d" % self.inputs)
         if bf16 and self.inputs > 5:
             raise _lib.WitwError("cvig_baseline encoder: precision='%s' needs the fused first block (at most 5 input channels, got %d)"
                                  % (self.precision, self.inputs))
@@ -335,7 +359,9 @@ def _pad_hw(y, H, W):
 
 
 class _BaselineEncoderFn(torch.autograd.Function):
-    """Train-mode forward (BatchNorm2d batch statistics, running-stat update) and backward of one encoder call."""
+    """Train-mode forward (BatchNorm2d batch statistics, running-stat update) and backward of one encoder call.
+    enc.train_precision == 'bf16': blocks 2-4 keep their input h as bf16 only (rounded once, behind the producer's BatchNorm affine) and
+    run forward, data gradient and weight gradient through baseline_bf16; their activations a, the statistics and the gates stay fp32."""
 
     @staticmethod
     def forward(ctx, x, enc, *params):
@@ -345,13 +371,17 @@ class _BaselineEncoderFn(torch.autograd.Function):
             g = torch.empty((B, 1536), dtype=torch.float32, device=x.device)
             vh, vw = H, W
             saved = []
+            bf = enc.train_precision == 'bf16'
             for i in range(1, 8):
-                packed, _es, _et, _cp = enc._layer(i, fold=False)
+                on_bf16 = bf and 2 <= i <= 4
+                packed, _es, _et, _cp = enc._layer(i, fold=False, pack=not on_bf16)
                 bn = getattr(enc, 'bn%d' % i)
                 vh, vw = (vh - 4) // 2 + 1, (vw - 4) // 2 + 1
                 if i >= 5:      # maps of 16 x 16 and below: split-K over a mosaic of g x g images, as the eval path (15 of 16 lanes of
                     gm = _mosaic_g(h)                     # the narrow-geometry kernel idle otherwise); zero-padded to the input's size
                     a = _pad_hw(ops.conv_taps4_splitk(_to_mosaic(h, gm), packed, B, gm, (vh, vw), lrelu_slope=0.2), h.shape[1], h.shape[2])
+                elif on_bf16:
+                    a = baseline_bf16.conv_taps4_plain_bf16(h, enc._layer_bf16(i), (vh, vw), lrelu_slope=0.2)
                 else:
                     a = ops.conv3x3_fwd(h, packed, relu=False, lrelu_slope=0.2)              # LeakyReLU(conv), :267-275
                 mean, invstd, scale, shift = ops.bn_train_stats(a, (vh, vw), bn.weight, bn.bias, bn.running_mean,
@@ -362,10 +392,12 @@ class _BaselineEncoderFn(torch.autograd.Function):
                 saved.append((h, a, (vh, vw), mean, invstd, scale, shift))
                 if i >= 5:
                     ops.gem_pool(a, (vh, vw), g, 512 * (i - 5), enc.p, scale, shift)
-                if i < 7:
+                if bf and 1 <= i <= 3:      # the input of a bf16 block: the same affine in fp32, one rounding at the store
+                    h = baseline_bf16.space_to_depth2_bf16(a, valid_hw=(vh, vw), scale=scale, shift=shift)
+                elif i < 7:
                     h = ops.space_to_depth2(a, valid_hw=(vh, vw), cpad=enc._layer(i + 1, fold=False)[3], scale=scale, shift=shift)
             f = ops.embed_normalize_(g.clone())
-        ctx.enc, ctx.saved, ctx.g = enc, saved, g
+        ctx.enc, ctx.saved, ctx.g, ctx.bf = enc, saved, g, bf
         ctx.override = getattr(enc, '_bwd_override', {})
         enc._bwd_override = {}
         enc._last_saved = saved if getattr(enc, 'keep_activations', False) else None     # diagnostics / parity tests
@@ -389,12 +421,19 @@ class _BaselineEncoderFn(torch.autograd.Function):
             else:       # blocks 1-4 (the large maps): the BatchNorm backward reads the space-to-depth gradient in place
                 dy, s2d_grad = dx_s2d, True
             dz, dgamma, dbeta = ops.bn_lrelu_bwd(ctx.override.get(i, a), dy, valid, mean, invstd, bn.weight, 0.2, dy_s2d=s2d_grad)
-            k3 = enc._layer_k3(i)
-            dk3, dbias = ops.conv3x3_wgrad(h, dz, k3.shape[1], stride_h=1, circular=False, taps4=True)
+            on_bf16 = ctx.bf and 2 <= i <= 4
+            k3 = enc._layer_k3(i, pack=not on_bf16)
+            if on_bf16:
+                dz = baseline_bf16.to_bf16(dz)      # the block's output gradient: rounded once, read by both gradients
+                dk3, dbias = baseline_bf16.conv3x3_wgrad_bf16_taps4(h, dz, k3.shape[1])
+            else:
+                dk3, dbias = ops.conv3x3_wgrad(h, dz, k3.shape[1], stride_h=1, circular=False, taps4=True)
             # tap (ta+1, tb+1) of the 3x3 filter holds W[:, :, 2ta+dy, 2tb+dx] as channel (dy,dx,c): gathered back in one launch
             dw = ops.k3_to_conv4x4(dk3, conv.weight.shape[1])
             grads[4 * (i - 1):4 * i] = [dw, dbias, dgamma, dbeta]
-            if i > 1:
+            if on_bf16:
+                dx_s2d = baseline_bf16.conv_taps4_plain_bf16(dz, enc._layer_bf16_t(i))
+            elif i > 1:
                 pk_t = enc._layer_t(i)
                 if i >= 5:      # the same small maps in the data gradient: mosaic + split-K (dz is zero outside its valid region,
                     gm = _mosaic_g(dz)                    # so the last row / column of every cell is the zero border a window may touch)
@@ -867,7 +906,8 @@ def _bn_modules(*encoders):
     return [getattr(e, 'bn%d' % i) for e in encoders for i in range(1, 8)]
 
 
-def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_epochs=999999, csv_path=None, seed=0, loss='exhaustive'):
+def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_epochs=999999, csv_path=None, seed=0, loss='exhaustive',
+          train_precision=None):
     """model/cvig_baseline.py:318-404 on the HIP kernels: same flow, prints and checkpoint names; Adam with torch's
     defaults (lr 1e-3) over every encoder parameter.
     Under an initialised process group (N ranks, one per GPU) it is the reference's nn.DataParallel run (:339-343) with a rank in
@@ -879,12 +919,17 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
     the one-process loop on the same split. Rank 0 prints and saves. `seed` fixes the train / validation split, which every rank
     must draw alike; it is not used on one rank. loss='batch_hard' (not in the reference) trains on every anchor's hardest negative
     of the global batch instead (batch_hard_triplet_loss / sharded_batch_hard_loss), and validation then evaluates that loss, so
-    that "best" is judged by the loss that is trained."""
+    that "best" is judged by the loss that is trained. train_precision: None = Globals.train_precision; 'fp32', or 'bf16' = the training
+    step runs blocks 2-4 on the bf16 MFMA (SurfaceEncoder(train_precision='bf16')) and the validation phase runs the encoders' eval forward
+    with precision='bf16'. The same under N ranks; checkpoints are the fp32 master weights in either case."""
     import pathlib
     import time
     from . import parallel
     if loss not in LOSSES:
         raise _lib.WitwError("train: loss must be 'exhaustive' or 'batch_hard', got %r" % (loss,))
+    train_precision = Globals.train_precision if train_precision is None else train_precision
+    if train_precision not in TRAIN_PRECISIONS:
+        raise _lib.WitwError("train: train_precision must be 'fp32' or 'bf16', got %r" % (train_precision,))
     world, rank = parallel.world(), parallel.rank()
     if world > 1 and batch_size % world:
         raise _lib.WitwError('train: the global batch_size %d is not a multiple of the %d ranks' % (batch_size, world))
@@ -909,8 +954,9 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
                                                    num_workers=num_workers, collate_fn=_fov.collate_raw)
         val_loader = torch.utils.data.DataLoader(val_set, batch_size=batch_size, shuffle=False, drop_last=False,
                                                  num_workers=num_workers, collate_fn=_fov.collate_raw)
-    surface_encoder = SurfaceEncoder().to(device)
-    overhead_encoder = OverheadEncoder().to(device)
+    enc_kw = {'precision': 'bf16', 'train_precision': 'bf16'} if train_precision == 'bf16' else {'train_precision': 'fp32'}
+    surface_encoder = SurfaceEncoder(**enc_kw).to(device)
+    overhead_encoder = OverheadEncoder(**enc_kw).to(device)
     encoders = [surface_encoder, overhead_encoder]
     parallel.broadcast_parameters(encoders)
     dense_loss, sharded_loss = {'exhaustive': (exhaustive_minibatch_triplet_loss, sharded_exhaustive_loss),
@@ -1042,13 +1088,21 @@ def main(argv=None):
                         help='Test mode: arithmetic of the encoders. fp32 = fp32 MFMA throughout (within 2e-5 of fp64); bf16 = blocks 1-4 '
                              '(86 %% of the multiply-adds) with bf16 operands and fp32 accumulation on the bf16 MFMA, blocks 5-7 and the '
                              'head in fp32 (embedding within 1e-2 of fp64, relative to its norm); bf16_all = the convolutions of blocks 5-7 on the '
-                             'bf16 MFMA as well (split-K, fp32 sums; same bound). Training is fp32 only. [Default = fp32]')
+                             'bf16 MFMA as well (split-K, fp32 sums; same bound). Not the training arithmetic: see --train-precision. '
+                             '[Default = fp32]')
+    parser.add_argument('--train-precision', default=None, choices=list(TRAIN_PRECISIONS),
+                        help='Train mode: arithmetic of the training step. fp32 = fp32 MFMA throughout; bf16 = forward, data gradient and '
+                             'weight gradient of blocks 2-4 with bf16 operands and fp32 accumulation (fp32 master weights, statistics and '
+                             'gradients), validation with the bf16 eval forward. [Default = fp32]')
     args = parser.parse_args(argv)
+    if args.mode != 'train' and args.train_precision is not None:
+        parser.error("--train-precision belongs to --mode train")
     if args.mode == 'train' and args.precision != 'fp32':
         parser.error("--precision %s is inference only: --mode train runs in fp32 (use it with --mode test)" % args.precision)
     _fov.init_distributed()       # under `python -m torch.distributed.run --nproc-per-node N`: one process per GPU; else nothing
     if args.mode == 'train':
-        train(dataset=args.dataset, loss=args.loss)
+        extra = {} if args.train_precision is None else {'train_precision': args.train_precision}      # only when the flag was given
+        train(dataset=args.dataset, loss=args.loss, **extra)
     elif args.mode == 'test':
         test(dataset=args.dataset, match_method=args.match_method, precision=args.precision)
 
