@@ -137,6 +137,10 @@ int witw_conv3x3_wino(int enable);
  * bits either way (A/B runs). WITW_CONV_WINO_WGS=n in the environment forces the workgroup count (test aid). enable < 0 only
  * queries; returns the previous setting. */
 int witw_conv3x3_wino_run(int enable);
+/* 1 (default, or WITW_CONV_WINO_DMA in the environment): a Winograd launch stages the input tile and filter slab of a K chunk by
+ * LDS-DMA (buffer loads that write the LDS directly); 0: through registers. Same bits either way (A/B runs). enable < 0 only
+ * queries; returns the previous setting. */
+int witw_conv3x3_wino_dma(int enable);
 /* backward of the fused MaxPool2d(2,2): pool_code (written by the forward when non-NULL: first arg-max position
  * dy*2+dx in torch's scan order) routes dy [B,Hp,Wp,C] into dx [B,H,W,C] (H>=2Hp, W>=2Wp). */
 int witw_maxpool2x2_bwd(const float* dy, const unsigned char* pool_code, float* dx, int B, int Hp, int Wp, int H, int W,

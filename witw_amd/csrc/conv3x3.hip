@@ -17,6 +17,7 @@
 // yields the operands of 4 MFMA k-steps: MFMA step j takes channel j of quad 0 from
 // lanes 0-31 and channel j of quad 1 from lanes 32-63 (A and B agree on that order).
 #include "common.h"
+#include "lds_frag.h"
 #include <stdlib.h>
 #include <algorithm>
 
@@ -64,6 +65,8 @@ struct ConvArgs {
     // Winograd form only: the launch starts wino_wgs workgroups, and workgroup w walks the run w, w + wino_wgs, ... of the
     // wino_items indices of the workgroup -> tile map (one index per workgroup when witw_conv3x3_wino_run is off)
     int wino_items, wino_wgs;
+    // Winograd form only: a K chunk is staged by LDS-DMA (0: global -> registers -> LDS; same bits)
+    int wino_dma;
 #ifdef WITW_STAMPS
     unsigned long long* stamps;   // diagnostic build only (tools/conv_stamps.cpp)
 #endif
@@ -80,16 +83,22 @@ struct ConvArgs {
 // tile is NW rows x 64 columns x 64 channels whatever TN names, the halo tile is staged exactly as in the direct form and the
 // filter slab of a K chunk is [kw][t][quad][64] (12 slices instead of 9 of twice the width). Every output gets the same
 // arithmetic in the same order (chunk -> kw -> channel) at NW = 4 and 8.
-template <int NW, bool POOL>
+// DMA: a K chunk is staged by LDS-DMA (dma16, lds_frag.h), NIN + NWT pieces of 1 KB per wave, with no staging registers and no LDS
+// write instructions; !DMA: global -> registers -> LDS (witw_conv3x3_wino_dma(0): A/B runs, the bitwise tests). A piece lands in
+// 64 consecutive slots, so the DMA form's slot s is LDS slot s of the stage (plane s / (IH*IW), pixel s % (IH*IW)) where the
+// register form's is (plane s & 1, pixel s >> 1). The input region of a stage is rounded up to whole pieces (IN_PAD) in both
+// forms; the slots behind the tile take zeros from the buffer's range check.
+template <int NW, bool POOL, bool DMA>
 __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
     constexpr int TH = NW, TW = 64, IW = TW + 2, IH = TH + 2;
     constexpr int NTHREADS = 64 * NW;
     constexpr int WTN = 64;                    // output channels per workgroup
     constexpr int IN_F4 = 2 * IH * IW;
     constexpr int W_F4 = 12 * 2 * WTN;         // [kw][t][quad][n]
-    constexpr int STAGE_F4 = IN_F4 + W_F4;
     constexpr int NIN = (IN_F4 + NTHREADS - 1) / NTHREADS;
     constexpr int NWT = W_F4 / NTHREADS;
+    constexpr int IN_PAD = NIN * NTHREADS;     // input region of a stage: whole LDS-DMA pieces
+    constexpr int STAGE_F4 = IN_PAD + W_F4;
     static_assert(NWT * NTHREADS == W_F4, "the filter slab splits evenly over the workgroup");
 
     // an opaque copy: nothing derived from it is shared with the direct form's code, whose registers would stay live over this form's
@@ -129,7 +138,8 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
     // the tile being accumulated (the epilogue's), and the source of the staging instructions: the same tile up to its last chunk,
     // whose "next chunk" is chunk 0 of the run's next item
     int ntile, b, oy0, ox0;
-    __amdgpu_buffer_rsrc_t in_rs, w_rs;
+    __amdgpu_buffer_rsrc_t in_rs, w_rs;      // !DMA
+    i32x4 in_rd, w_rd;                       // DMA: the same records as four SGPRs each
     unsigned gin[NIN];
     auto decode = [&](int item, int& nt_, int& b_, int& oy0_, int& ox0_) {
         int sp = item_sp(item, nt_);
@@ -141,10 +151,16 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
     };
     // live = false: records of zero bytes, every staging load returns zeros without a memory access (behind a run's last item)
     auto stage_from = [&](int nt_, int b_, int oy0_, int ox0_, bool live) {
-        in_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b_ * img_floats), 0, live ? (unsigned)(img_floats * 4) : 0u,
-                                                  0x00020000);
-        w_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const f32x4*>(p.wpk_wino) + (size_t)nt_ * nkc * W_F4), 0,
-                                                 live ? (unsigned)nkc * W_F4 * 16u : 0u, 0x00020000);
+        const float* in_base = p.x + (size_t)b_ * img_floats;
+        const f32x4* w_base = reinterpret_cast<const f32x4*>(p.wpk_wino) + (size_t)nt_ * nkc * W_F4;
+        const unsigned in_bytes = live ? (unsigned)(img_floats * 4) : 0u, w_bytes = live ? (unsigned)nkc * W_F4 * 16u : 0u;
+        if constexpr (DMA) {
+            in_rd = raw_rsrc(in_base, in_bytes);
+            w_rd = raw_rsrc(w_base, w_bytes);
+        } else {
+            in_rs = __builtin_amdgcn_make_buffer_rsrc((void*)in_base, 0, in_bytes, 0x00020000);
+            w_rs = __builtin_amdgcn_make_buffer_rsrc((void*)w_base, 0, w_bytes, 0x00020000);
+        }
         if (!live) return;
         // the slot's (row, column) is worked out anew for every item: kept in registers over the K loop it would not fit
         int t = tid;
@@ -152,7 +168,8 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
 #pragma unroll
         for (int i = 0; i < NIN; ++i) {
             const int s = t + i * NTHREADS;
-            const int pix = s >> 1, q = s & 1;
+            const int q = DMA ? (s >= IH * IW) : (s & 1);
+            const int pix = DMA ? s - q * (IH * IW) : s >> 1;
             const int r = pix / IW, c = pix - r * IW;
             const int gr = oy0_ - 1 + r;
             int gc = ox0_ - 1 + c;
@@ -169,8 +186,18 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
     decode(it, ntile, b, oy0, ox0);
     stage_from(ntile, b, oy0, ox0, true);
     const unsigned gwoff = (unsigned)tid * 16u;
+    // staging of a K chunk, one instruction at a time (i < NIN: input tile, then the filter slab). DMA: piece i of this wave, slots
+    // [i * NTHREADS + 64 * wave, + 64) of the stage's input region or of its filter slab
+    const unsigned smem_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_address(smem));
+    const unsigned wave_lds = (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;
+    auto dma_one = [&](int buf, int kc, int i) {
+        const unsigned st = smem_lds + (unsigned)buf * (STAGE_F4 * 16u) + wave_lds;
+        if (i < NIN) dma16(in_rd, st + (unsigned)i * (NTHREADS * 16u), gin[i], (unsigned)kc * 32u);
+        else dma16(w_rd, st + (unsigned)(IN_PAD + (i - NIN) * NTHREADS) * 16u, gwoff,
+                   (unsigned)kc * W_F4 * 16u + (unsigned)(i - NIN) * (NTHREADS * 16u));
+    };
+    // !DMA: global -> registers -> LDS
     f32x4 rin[NIN], rw[NWT];
-    // staging of a K chunk, one instruction at a time (i < NIN: input tile, then the filter slab): global -> registers -> LDS
     auto load_one = [&](int kc, int i) {
         if (i < NIN) rin[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rs, gin[i], (unsigned)kc * 32u, 0));
         else rw[i - NIN] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
@@ -183,7 +210,7 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
             f32x4* dst = (NIN * NTHREADS == IN_F4 || s < IN_F4) ? in_s + (s & 1) * (IH * IW) + (s >> 1) : smem + 2 * STAGE_F4;
             *dst = rin[i];
         } else {
-            in_s[IN_F4 + tid + (i - NIN) * NTHREADS] = rw[i - NIN];
+            in_s[IN_PAD + tid + (i - NIN) * NTHREADS] = rw[i - NIN];
         }
     };
 
@@ -221,15 +248,21 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
         acc[t][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][t][j], fb[bset][t][j], acc[t][ct], 0, 0, 0);
     };
 
+    if constexpr (DMA) {
 #pragma unroll
-    for (int i = 0; i < NIN + NWT; ++i) load_one(0, i);
+        for (int i = 0; i < NIN + NWT; ++i) dma_one(0, 0, i);
+        wait_vmcnt<0>();
+    } else {
 #pragma unroll
-    for (int i = 0; i < NIN + NWT; ++i) store_one(0, i);
+        for (int i = 0; i < NIN + NWT; ++i) load_one(0, i);
+#pragma unroll
+        for (int i = 0; i < NIN + NWT; ++i) store_one(0, i);
+    }
     __syncthreads();
     // filter slices before input rows, pinned: the transform's wait for the rows then leaves no read in flight at the loop's head,
     // where a read still pending from here would turn the first MFMA's counted wait into a full drain on every trip
 #pragma unroll
-    for (int i = 0; i < 4; ++i) read_b(0, smem + IN_F4, 0, i);
+    for (int i = 0; i < 4; ++i) read_b(0, smem + IN_PAD, 0, i);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) read_a(0, smem, 0, i);
@@ -250,6 +283,7 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
             if (i >= 8) transform2(set ^ 1, i - 8);
             __builtin_amdgcn_sched_barrier(0);
             if (barrier_mid && i == 7) {
+                if constexpr (DMA) wait_vmcnt<0>();      // this wave's pieces of the next chunk have landed; the barrier publishes them
                 __syncthreads();
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -264,34 +298,49 @@ __device__ __forceinline__ void conv_wino_h2(const ConvArgs& p, f32x4* smem) {
     // is a counted one. Step 4 has none to offer: there the chunk's barrier, whose drain is the loop's only full one, stands
     // between the reads (MFMAs 0..3) and the transform (MFMAs 8..15). It still separates the last read of this stage (step 4)
     // from its next overwrite (step 3 of the next chunk), and the writes of the next stage (step 3) from their first read (step 5).
+    // DMA: the next chunk's pieces go out under steps 0..2 instead (the other stage is free from the previous chunk's barrier on),
+    // in the gaps that hold neither a fragment read nor a transform: all six in step 0's consecutive gaps, beside its reads, cost
+    // 0.9 ms per step against the register path, spread over the bare gaps they win 1.4 ms. Each wave waits for its own pieces
+    // (vmcnt) in front of the barrier of step 4, and step 3, which has no staging writes to offer, takes the second half of kw 2's
+    // filter slices as its younger LDS instructions.
     // One K chunk on stage `cur`, staging chunk kn of the staging source into the other stage.
     auto chunk = [&](int cur, int kn) __attribute__((always_inline)) {
         const f32x4* in_s = smem + cur * STAGE_F4;
-        const f32x4* w_s = in_s + IN_F4;
+        const f32x4* w_s = in_s + IN_PAD;
         const f32x4* in_n = smem + (cur ^ 1) * STAGE_F4;
+        // DMA pieces: the gaps of steps 0..2 that hold neither a fragment read nor a transform (6, 7; NW = 4: 6..9)
+        constexpr int PER = (NIN + NWT + 2) / 3;
+        auto dma_gap = [&](int s, int i) {
+            const int j = s * PER + (i - 6);
+            if (i >= 6 && i < 6 + PER && j < NIN + NWT) dma_one(cur ^ 1, kn, j);
+        };
         step(0, 0, 0, [&](int i) {
             if (i < 4) read_a(1, in_s, 1, i);
             else if (i < 6) read_b(1, w_s, 1, i - 4);
+            else if (DMA) dma_gap(0, i);
             else if (i < 6 + NIN + NWT) load_one(kn, i - 6);
         }, false);
         step(1, 0, 1, [&](int i) {
             if (i < 4) read_a(0, in_s, 2, i);
             else if (i < 6) read_b(1, w_s, 1, i - 2);
+            else if (DMA) dma_gap(1, i);
         }, false);
         step(0, 1, 0, [&](int i) {
             if (i < 4) read_a(1, in_s, 3, i);
-            else if (i < 8) read_b(0, w_s, 2, i - 4);
+            else if (i < (DMA ? 6 : 8)) read_b(0, w_s, 2, i - 4);
+            else if (DMA) dma_gap(2, i);
         }, false);
         step(1, 1, 1, [&](int i) {
             if (i < 4) read_a(0, in_s, 4, i);
-            else if (i < 4 + NIN + NWT) store_one(cur ^ 1, i - 4);
+            else if (DMA && i < 6) read_b(0, w_s, 2, i - 2);
+            else if (!DMA && i < 4 + NIN + NWT) store_one(cur ^ 1, i - 4);
         }, false);
         step(0, 0, 0, [&](int i) {
             if (i < 4) read_a(1, in_s, 5, i);
         }, true);
         step(1, 0, 1, [&](int i) {
             if (i < 4) read_a(0, in_n, 0, i);
-            else if (i < 8) read_b(1, in_n + IN_F4, 0, i - 4);
+            else if (i < 8) read_b(1, in_n + IN_PAD, 0, i - 4);
         }, false);
 #pragma unroll
         for (int t = 0; t < 4; ++t) fb[0][t] = fb[1][t];
@@ -443,7 +492,9 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_f32_kernel(ConvArgs p) {
     // WINO: the classes that also run the Winograd F(2,3)-along-H form (conv_wino_h2) when the launcher sets p.wino
     constexpr bool WINO = SH == 1 && TAPS == 9 && GEO == 0 && (TN == 128 || POOL);
     // its two stages, the dummy slot and, behind them, a 4 KB epilogue slab per wave (both stages are live between two items of a run)
-    constexpr int WINO_F4 = WINO ? 2 * (2 * (NW + 2) * IW + 12 * 2 * 64) + 1 + NW * 256 : 0;
+    // (the input region of a stage in whole 1 KB pieces per wave, as the LDS-DMA staging writes it)
+    constexpr int WINO_IN_F4 = (2 * (NW + 2) * IW + NTHREADS - 1) / NTHREADS * NTHREADS;
+    constexpr int WINO_F4 = WINO ? 2 * (WINO_IN_F4 + 12 * 2 * 64) + 1 + NW * 256 : 0;
     constexpr int DIRECT_F4 = (2 * STAGE_F4 + 1 > NW * 512) ? 2 * STAGE_F4 + 1 : NW * 512;
     constexpr int SMEM_F4 = DIRECT_F4 > WINO_F4 ? DIRECT_F4 : WINO_F4;
     __shared__ f32x4 smem[SMEM_F4];
@@ -452,7 +503,8 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_nhwc_f32_kernel(ConvArgs p) {
         // weighted as the unlikely side: the run loop around the K loop otherwise outweighs the direct form's blocks in the register
         // allocator's spill costs, and the direct epilogue spills (72 VGPRs in <128,1,false,8,0,9>)
         if (__builtin_expect(p.wino != 0, 0)) {
-            conv_wino_h2<NW, POOL>(p, smem);
+            if (p.wino_dma) conv_wino_h2<NW, POOL, true>(p, smem);
+            else conv_wino_h2<NW, POOL, false>(p, smem);
             return;
         }
     }
@@ -1032,6 +1084,7 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restri
 
 int env_int(const char* name, int dflt);
 int wino_run();
+int wino_dma();
 
 template <int TN, int SH, bool POOL, int NW, int GEO, int TAPS = 9>
 int launch_conv_nw(ConvArgs a, hipStream_t st) {
@@ -1057,6 +1110,7 @@ int launch_conv_nw(ConvArgs a, hipStream_t st) {
         const int forced = env_int("WITW_CONV_WINO_WGS", 0);      // test aid: runs of more than one item on small shapes
         a.wino_wgs = (int)std::min<long long>(grid, forced > 0 ? forced : witw_cu_count());
     }
+    a.wino_dma = a.wino ? wino_dma() : 0;
     hipLaunchKernelGGL((conv3x3_nhwc_f32_kernel<TN, SH, POOL, NW, GEO, TAPS>), dim3(a.wino ? (unsigned)a.wino_wgs : (unsigned)grid, gy),
                        dim3(64 * NW), 0, st, a);
     WITW_CHECK_LAUNCH("conv3x3_nhwc_f32");
@@ -1112,6 +1166,17 @@ int wino_run() {
         g_wino_run = e ? (atoi(e) != 0) : 1;
     }
     return g_wino_run;
+}
+
+// 1 (default): a Winograd launch stages its K chunks by LDS-DMA; 0: through registers (WITW_CONV_WINO_DMA=0 /
+// witw_conv3x3_wino_dma(0): A/B runs, the bitwise tests)
+int g_wino_dma = -1;
+int wino_dma() {
+    if (g_wino_dma < 0) {
+        const char* e = getenv("WITW_CONV_WINO_DMA");
+        g_wino_dma = e ? (atoi(e) != 0) : 1;
+    }
+    return g_wino_dma;
 }
 
 template <int TN, int SH, bool POOL>
@@ -1401,6 +1466,14 @@ int witw_conv3x3_wino(int enable) {
 int witw_conv3x3_wino_run(int enable) {
     const int prev = wino_run();
     if (enable >= 0) g_wino_run = enable != 0;
+    return prev;
+}
+
+// 1 (default): a Winograd launch stages its K chunks by LDS-DMA; 0: through registers (same bits). enable < 0 only queries.
+// Returns the previous setting.
+int witw_conv3x3_wino_dma(int enable) {
+    const int prev = wino_dma();
+    if (enable >= 0) g_wino_dma = enable != 0;
     return prev;
 }
 

@@ -1464,6 +1464,12 @@ def conv_wino_run(enable=None):
     return bool(_lib.load().witw_conv3x3_wino_run(-1 if enable is None else int(bool(enable))))
 
 
+def conv_wino_dma(enable=None):
+    """Query (enable=None) or set whether a Winograd launch stages its K chunks by LDS-DMA (witw_conv3x3_wino_dma; off: through
+    registers, same bits); returns the previous setting."""
+    return bool(_lib.load().witw_conv3x3_wino_dma(-1 if enable is None else int(bool(enable))))
+
+
 def last_kernel_variant():
     """Name of the conv kernel instantiation the calling thread's last conv launcher picked (witw_last_kernel_variant), spelled
     as in rocprof kernel names."""
