@@ -1,14 +1,15 @@
 """Host-side wrappers of csrc/conv_taps4_bf16.hip: the bf16 filter packing and the 2x2-tap convolution of blocks 2-4 of cvig_baseline's
 encoders at inference (SurfaceEncoder(precision='bf16')). With ops.conv4x4s2_first(out_bf16=True) they are the bf16 part of that
 forward and live here, not in ops.py; their memory-contract cases are in tests/test_baseline_bf16_gpu.py. No CPU fallback.
-precision='bf16_all' adds the wrappers of csrc/conv_taps4_splitk_bf16.hip for blocks 5-7: conv_taps4_splitk_bf16 and
-space_to_depth2_mosaic_bf16 (memory-contract cases in tests/test_baseline_bf16_all_gpu.py).
+precision='bf16_all' adds blocks 5-7: conv_taps4_splitk_bf16 (csrc/conv_taps4_splitk_bf16.hip) and space_to_depth2_mosaic_bf16 (the
+bf16 store of csrc/baseline.hip's mosaic kernel); memory-contract cases in tests/test_baseline_bf16_all_gpu.py.
 train_precision='bf16' (training: forward, data gradient and weight gradient of blocks 2-4) adds the transpose_flip packing,
-conv_taps4_plain_bf16, space_to_depth2_bf16, to_bf16 and conv3x3_wgrad_bf16_taps4 (tests/test_baseline_bf16_train_gpu.py)."""
+conv_taps4_plain_bf16, space_to_depth2_bf16 (csrc/baseline.hip), to_bf16 and conv3x3_wgrad_bf16_taps4
+(tests/test_baseline_bf16_train_gpu.py)."""
 import torch
 
 from . import _lib
-from .ops import _Packed, _dev_f32, _p, _prof_begin, _prof_end, _stream, _wgrad_setup
+from .ops import _Packed, _dev_f32, _p, _post_affine, _prof_begin, _prof_end, _stream, _wgrad_setup
 
 
 class PackedConvBf16Taps4(_Packed):
@@ -35,27 +36,41 @@ class PackedConvBf16Taps4(_Packed):
         self._bias_buffer(reuse, None if transpose_flip else bias)
 
 
+def _bf16_nhwc(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and t.dim() == 4):
+        raise _lib.WitwError('%s must be a contiguous bfloat16 NHWC GPU tensor (no CPU fallback)' % name)
+    return t
+
+
+def _fwd_packed(name, packed):
+    if not isinstance(packed, PackedConvBf16Taps4) or packed.tap_base != 1:
+        raise _lib.WitwError('%s: a forward-packed PackedConvBf16Taps4 filter is required' % name)
+
+
+def _channels(name, channels, packed):
+    if channels != packed.cin_pad:
+        raise _lib.WitwError('%s: input has %d channels, packed weights expect %d' % (name, channels, packed.cin_pad))
+
+
+def _valid_region(name, vh, vw, H, W, what='map'):
+    """(vh, vw) as ints inside the H x W map, checked before anything is allocated"""
+    vh, vw = int(vh), int(vw)
+    if not (1 <= vh <= H and 1 <= vw <= W):
+        raise _lib.WitwError('%s: valid region %dx%d outside the %dx%d %s' % (name, vh, vw, H, W, what))
+    return vh, vw
+
+
 def conv_taps4_s2d_bf16(x_nhwc, packed, valid_hw, lrelu_slope=0.2, post_scale=None, post_shift=None, out_f32=False):
     """conv_taps4_s2d on bf16 operands with fp32 accumulation (witw_conv3x3_bf16_fwd_taps4): x bf16 [B,H,W,Cin_pad], packed a
     PackedConvBf16Taps4 -> [B, ceil(vh/2), ceil(vw/2), 4*Cout], bf16 (one nearest-even rounding behind the fp32 epilogue bias ->
     LeakyReLU -> affine) or fp32 with out_f32 (no rounding), +0.0 outside the (vh, vw) valid outputs."""
     lib = _lib.load()
-    if not (isinstance(x_nhwc, torch.Tensor) and x_nhwc.is_cuda and x_nhwc.dtype == torch.bfloat16 and x_nhwc.is_contiguous() and x_nhwc.dim() == 4):
-        raise _lib.WitwError('conv_taps4_s2d_bf16: x must be a contiguous bfloat16 NHWC GPU tensor (no CPU fallback)')
-    if not isinstance(packed, PackedConvBf16Taps4) or packed.tap_base != 1:
-        raise _lib.WitwError('conv_taps4_s2d_bf16: a forward-packed PackedConvBf16Taps4 filter is required')
+    x_nhwc = _bf16_nhwc(x_nhwc, 'conv_taps4_s2d_bf16: x')
     B, H, W, C = x_nhwc.shape
-    if C != packed.cin_pad:
-        raise _lib.WitwError('conv_taps4_s2d_bf16: input has %d channels, packed weights expect %d' % (C, packed.cin_pad))
-    if (post_scale is None) != (post_shift is None):
-        raise _lib.WitwError('conv_taps4_s2d_bf16: post_scale and post_shift come together')
-    if post_scale is not None:
-        post_scale, post_shift = _dev_f32(post_scale, 'post_scale'), _dev_f32(post_shift, 'post_shift')
-        if post_scale.numel() != packed.cout or post_shift.numel() != packed.cout:
-            raise _lib.WitwError('post_scale/post_shift must have Cout entries')
-    vh, vw = (int(v) for v in valid_hw)
-    if not (1 <= vh <= H and 1 <= vw <= W):      # before anything is allocated: the library's error, not torch's
-        raise _lib.WitwError('conv_taps4_s2d_bf16: valid region %dx%d outside the %dx%d map' % (vh, vw, H, W))
+    _fwd_packed('conv_taps4_s2d_bf16', packed)
+    _channels('conv_taps4_s2d_bf16', C, packed)
+    post_scale, post_shift = _post_affine('conv_taps4_s2d_bf16', post_scale, post_shift, packed.cout)
+    vh, vw = _valid_region('conv_taps4_s2d_bf16', *valid_hw, H, W)      # before anything is allocated: the library's error, not torch's
     y = torch.empty((B, (vh + 1) // 2, (vw + 1) // 2, 4 * packed.cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x_nhwc.device)
     prof = _prof_begin()
     _lib.check(lib.witw_conv3x3_bf16_fwd_taps4(x_nhwc.data_ptr(), packed.wpk.data_ptr(), packed.bias.data_ptr(), _p(post_scale), _p(post_shift),
@@ -73,28 +88,18 @@ def conv_taps4_splitk_bf16(x_mosaic_bf16, packed, n_images, g, valid_hw, lrelu_s
     the raw fp32 sums of ksplit K slices (None: the library's choice) into a workspace, witw_taps4_splitk_finish adds them in slice order."""
     lib = _lib.load()
     x = x_mosaic_bf16
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 4):
-        raise _lib.WitwError('conv_taps4_splitk_bf16: x must be a contiguous bfloat16 NHWC GPU tensor (no CPU fallback)')
-    if not isinstance(packed, PackedConvBf16Taps4) or packed.tap_base != 1:
-        raise _lib.WitwError('conv_taps4_splitk_bf16: a forward-packed PackedConvBf16Taps4 filter is required')
+    _bf16_nhwc(x, 'conv_taps4_splitk_bf16: x')
+    _fwd_packed('conv_taps4_splitk_bf16', packed)
     Bm, H, W, C = x.shape
     n_images, g = int(n_images), int(g)
     if g < 1 or n_images < 1 or H % g or W % g or Bm != (n_images + g * g - 1) // (g * g):
         raise _lib.WitwError('conv_taps4_splitk_bf16: %s is not a %dx%d mosaic of %d images' % (tuple(x.shape), g, g, n_images))
-    if C != packed.cin_pad:
-        raise _lib.WitwError('conv_taps4_splitk_bf16: input has %d channels, packed weights expect %d' % (C, packed.cin_pad))
+    _channels('conv_taps4_splitk_bf16', C, packed)
     if packed.cout % 4:
         raise _lib.WitwError('conv_taps4_splitk_bf16: Cout=%d must be a multiple of 4' % packed.cout)
-    if (post_scale is None) != (post_shift is None):
-        raise _lib.WitwError('conv_taps4_splitk_bf16: post_scale and post_shift come together')
-    if post_scale is not None:
-        post_scale, post_shift = _dev_f32(post_scale, 'post_scale'), _dev_f32(post_shift, 'post_shift')
-        if post_scale.numel() != packed.cout or post_shift.numel() != packed.cout:
-            raise _lib.WitwError('post_scale/post_shift must have Cout entries')
+    post_scale, post_shift = _post_affine('conv_taps4_splitk_bf16', post_scale, post_shift, packed.cout)
     h, w = H // g, W // g
-    vh, vw = (int(v) for v in valid_hw)
-    if not (1 <= vh <= h and 1 <= vw <= w):
-        raise _lib.WitwError('conv_taps4_splitk_bf16: valid region %dx%d outside the %dx%d cell' % (vh, vw, h, w))
+    vh, vw = _valid_region('conv_taps4_splitk_bf16', *valid_hw, h, w, 'cell')
     S = lib.witw_conv3x3_bf16_taps4_ksplit(Bm, H, W, C, packed.cout) if ksplit is None else int(ksplit)
     if not 1 <= S <= C // 16:
         raise _lib.WitwError('conv_taps4_splitk_bf16: ksplit=%d outside [1, Cin/16 = %d]' % (S, C // 16))
@@ -129,12 +134,6 @@ def space_to_depth2_mosaic_bf16(y_f32, g=1):
 
 
 # ----------------------------------------------------------------------------- training (train_precision='bf16')
-def _bf16_nhwc(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and t.dim() == 4):
-        raise _lib.WitwError('%s must be a contiguous bfloat16 NHWC GPU tensor (no CPU fallback)' % name)
-    return t
-
-
 def conv_taps4_plain_bf16(x_nhwc, packed, valid_hw=None, lrelu_slope=None):
     """ops.conv3x3_fwd with a taps4 filter on bf16 operands with fp32 accumulation (witw_conv3x3_bf16_fwd_taps4_plain): x bf16
     [B,H,W,Cin_pad], packed a PackedConvBf16Taps4 -> fp32 [B,H,W,Cout] in the plain layout, never rounded, +0.0 outside the (vh, vw)
@@ -149,9 +148,7 @@ def conv_taps4_plain_bf16(x_nhwc, packed, valid_hw=None, lrelu_slope=None):
         raise _lib.WitwError('conv_taps4_plain_bf16: input has %d channels, packed weights expect %d' % (C, packed.cin_pad))
     if packed.tap_base == 0 and lrelu_slope is not None:
         raise _lib.WitwError('conv_taps4_plain_bf16: a data-gradient filter takes no activation')
-    vh, vw = (H, W) if valid_hw is None else (int(v) for v in valid_hw)
-    if not (1 <= vh <= H and 1 <= vw <= W):
-        raise _lib.WitwError('conv_taps4_plain_bf16: valid region %dx%d outside the %dx%d map' % (vh, vw, H, W))
+    vh, vw = _valid_region('conv_taps4_plain_bf16', *((H, W) if valid_hw is None else valid_hw), H, W)
     y = torch.empty((B, H, W, packed.cout), dtype=torch.float32, device=x.device)
     prof = _prof_begin()
     _lib.check(lib.witw_conv3x3_bf16_fwd_taps4_plain(x.data_ptr(), packed.wpk.data_ptr(), packed.bias.data_ptr() if packed.tap_base else None,
@@ -171,9 +168,7 @@ def space_to_depth2_bf16(x_nhwc, valid_hw=None, scale=None, shift=None):
     if x.dim() != 4 or x.shape[3] % 4:
         raise _lib.WitwError('space_to_depth2_bf16: x must be NHWC with C %% 4 == 0, got %s' % (tuple(x.shape),))
     B, Hp, Wp, C = x.shape
-    H, W = (Hp, Wp) if valid_hw is None else (int(v) for v in valid_hw)
-    if not (1 <= H <= Hp and 1 <= W <= Wp):
-        raise _lib.WitwError('space_to_depth2_bf16: valid region %dx%d outside the %dx%d map' % (H, W, Hp, Wp))
+    H, W = _valid_region('space_to_depth2_bf16', *((Hp, Wp) if valid_hw is None else valid_hw), Hp, Wp)
     if (scale is None) != (shift is None):
         raise _lib.WitwError('space_to_depth2_bf16: scale and shift come together')
     if scale is not None:

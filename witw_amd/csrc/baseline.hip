@@ -44,15 +44,18 @@ __global__ void space_to_depth2_kernel(const float* __restrict__ x, float* __res
     y[idx] = v;
 }
 
-// The same for an NHWC source with C % 4 == 0 and Cp == 4C (every block but the first): one thread per channel quad, 16-byte
-// loads and stores, the same arithmetic per element.
-__global__ void space_to_depth2_quad_kernel(const float* __restrict__ x, float* __restrict__ y, int Hp, int Wp, int H, int W, int C,
-                                            size_t total4, const float* __restrict__ scale, const float* __restrict__ shift) {
+// The same for an NHWC source with C % 4 == 0 and Cp == 4C (every block but the first): one thread per V channels of one quadrant,
+// 16-byte loads, the same arithmetic per element, +0.0 outside the H x W valid region (the affine is NOT applied there). OUT = float
+// stores V = 4 channels as they are; OUT = __bf16 stores V = 8 or 4 with one nearest-even rounding at the store.
+template <typename OUT, int V>
+__global__ void space_to_depth2_quad_kernel(const float* __restrict__ x, OUT* __restrict__ y, int Hp, int Wp, int H, int W, int C,
+                                            size_t total, const float* __restrict__ scale, const float* __restrict__ shift) {
+    typedef OUT out_v __attribute__((ext_vector_type(V)));
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total4) return;
-    const int H2 = (H + 1) >> 1, W2 = (W + 1) >> 1, C4 = C >> 2;
-    const int c4 = idx % C4;
-    size_t t = idx / C4;
+    if (idx >= total) return;
+    const int H2 = (H + 1) >> 1, W2 = (W + 1) >> 1, CV = C / V;
+    const int cv = idx % CV;
+    size_t t = idx / CV;
     const int q = t & 3;
     t >>= 2;
     const int w2 = t % W2;
@@ -60,29 +63,40 @@ __global__ void space_to_depth2_quad_kernel(const float* __restrict__ x, float* 
     const int h2 = t % H2;
     const size_t b = t / H2;
     const int h = 2 * h2 + (q >> 1), w = 2 * w2 + (q & 1);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (h < H && w < W) {
-        v = *reinterpret_cast<const f32x4*>(x + ((b * Hp + h) * Wp + w) * C + 4 * c4);
-        if (scale != nullptr) {
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * c4), sf = *reinterpret_cast<const f32x4*>(shift + 4 * c4);
+    out_v o;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = v[j] * sc[j] + sf[j];
+    for (int j = 0; j < V; ++j) o[j] = (OUT)0.f;
+    if (h < H && w < W) {
+        const float* src = x + ((b * Hp + h) * Wp + w) * C + V * cv;
+#pragma unroll
+        for (int k = 0; k < V; k += 4) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(src + k);
+            if (scale != nullptr) {
+                const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + V * cv + k), sf = *reinterpret_cast<const f32x4*>(shift + V * cv + k);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = v[j] * sc[j] + sf[j];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[k + j] = (OUT)v[j];
         }
     }
-    reinterpret_cast<f32x4*>(y)[idx] = v;
+    reinterpret_cast<out_v*>(y)[idx] = o;
 }
 
 // Mosaic space-to-depth: x NHWC [B,H,W,C] (all valid) -> y [ceil(B/g^2), g*H2, g*W2, 4C], H2 = ceil(H/2): image b sits in cell
 // (b % g^2) of mosaic image b / g^2, cells row-major, each the space-to-depth(2) image of x[b]; zeros where no source exists.
 // A k=4,s=2 layer over an H2 x W2 s2d map has (H2-1) x (W2-1) valid outputs, so no valid output's 2x2 window crosses a cell:
 // the deep cvig_baseline layers (8x8 and 4x4 maps) run as g = 2 / g = 4 mosaics that fill the conv kernel's 16x16 tile.
-__global__ void s2d_mosaic_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C, int g, size_t total4) {
+// One thread per V channels of one output pixel's quadrant; OUT and V as in space_to_depth2_quad_kernel.
+template <typename OUT, int V>
+__global__ void s2d_mosaic_kernel(const float* __restrict__ x, OUT* __restrict__ y, int B, int H, int W, int C, int g, size_t total) {
+    typedef OUT out_v __attribute__((ext_vector_type(V)));
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total4) return;
+    if (idx >= total) return;
     const int H2 = (H + 1) >> 1, W2 = (W + 1) >> 1;
-    const int C4 = C >> 2;
-    const int c4 = idx % C4;
-    size_t t = idx / C4;
+    const int CV = C / V;
+    const int cv = idx % CV;
+    size_t t = idx / CV;
     const int q = t & 3;
     t >>= 2;
     const int X = t % (g * W2);
@@ -92,9 +106,19 @@ __global__ void s2d_mosaic_kernel(const float* __restrict__ x, float* __restrict
     const int cy = Y / H2, y2 = Y - cy * H2, cx = X / W2, x2 = X - cx * W2;
     const int b = (bm * g + cy) * g + cx;
     const int h = 2 * y2 + (q >> 1), w = 2 * x2 + (q & 1);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (b < B && h < H && w < W) v = *reinterpret_cast<const f32x4*>(x + (((size_t)b * H + h) * W + w) * C + 4 * c4);
-    reinterpret_cast<f32x4*>(y)[idx] = v;
+    out_v o;
+#pragma unroll
+    for (int j = 0; j < V; ++j) o[j] = (OUT)0.f;
+    if (b < B && h < H && w < W) {
+        const float* src = x + (((size_t)b * H + h) * W + w) * C + V * cv;
+#pragma unroll
+        for (int k = 0; k < V; k += 4) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(src + k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[k + j] = (OUT)v[j];
+        }
+    }
+    reinterpret_cast<out_v*>(y)[idx] = o;
 }
 
 // Epilogue of a split-K taps4 convolution run over a g x g mosaic: ws [S][Bm, g*h, g*w, C] raw partial sums ->
@@ -586,6 +610,22 @@ __global__ void k3_to_conv4x4_kernel(const float* __restrict__ k3, float* __rest
     w[idx] = k3[((co * cpad + ch) * 3 + (ky >> 1) + 1) * 3 + (kx >> 1) + 1];
 }
 
+// Both mosaic entry points: fp32 stores 4 channels per thread, bf16 stores 8 when C allows it
+template <typename OUT>
+int s2d_mosaic_launch(const char* what, const float* x, OUT* y, int B, int H, int W, int C, int g, void* stream) {
+    WITW_CHECK_ARG(x && y, "%s: null pointer", what);
+    WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && g >= 1 && g <= 64, "%s: bad shape", what);
+    const int V = (sizeof(OUT) == 2 && (C & 7) == 0) ? 8 : 4;
+    const size_t total = (size_t)cdiv(B, g * g) * (g * ((H + 1) / 2)) * (g * ((W + 1) / 2)) * 4 * (C / V);
+    WITW_CHECK_ARG((total + 255) / 256 <= 0x7fffffffULL, "%s: tensor too large", what);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (V == 4) hipLaunchKernelGGL((s2d_mosaic_kernel<OUT, 4>), grid, dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C, g, total);
+    else if constexpr (sizeof(OUT) == 2)
+        hipLaunchKernelGGL((s2d_mosaic_kernel<OUT, 8>), grid, dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C, g, total);
+    WITW_CHECK_LAUNCH(what);
+    return WITW_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -597,8 +637,8 @@ int witw_space_to_depth2(const float* x, float* y, int B, int Hp, int Wp, int H,
     const size_t total = (size_t)B * ((H + 1) / 2) * ((W + 1) / 2) * Cpad;
     WITW_CHECK_ARG((total + 255) / 256 <= 0x7fffffffULL, "space_to_depth2: tensor too large");
     if (!in_nchw && !normalize && (C & 3) == 0 && Cpad == 4 * C)
-        hipLaunchKernelGGL(space_to_depth2_quad_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
-                           y, Hp, Wp, H, W, C, total / 4, scale, shift);
+        hipLaunchKernelGGL((space_to_depth2_quad_kernel<float, 4>), dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, x, y, Hp, Wp, H, W, C, total / 4, scale, shift);
     else
         hipLaunchKernelGGL(space_to_depth2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, B,
                            Hp, Wp, H, W, C, Cpad, in_nchw, normalize, total, scale, shift);
@@ -606,15 +646,34 @@ int witw_space_to_depth2(const float* x, float* y, int B, int Hp, int Wp, int H,
     return WITW_OK;
 }
 
-int witw_space_to_depth2_mosaic(const float* x, float* y, int B, int H, int W, int C, int g, void* stream) {
-    WITW_CHECK_ARG(x && y, "space_to_depth2_mosaic: null pointer");
-    WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && g >= 1 && g <= 64, "space_to_depth2_mosaic: bad shape");
-    const size_t total4 = (size_t)cdiv(B, g * g) * (g * ((H + 1) / 2)) * (g * ((W + 1) / 2)) * C;     // 4C / 4
-    WITW_CHECK_ARG((total4 + 255) / 256 <= 0x7fffffffULL, "space_to_depth2_mosaic: tensor too large");
-    hipLaunchKernelGGL(s2d_mosaic_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W,
-                       C, g, total4);
-    WITW_CHECK_LAUNCH("space_to_depth2_mosaic");
+// x fp32 NHWC [B,Hp,Wp,C] (C % 4 == 0) with valid region H x W, scale / shift fp32 [C] or both NULL -> y bf16 [B, ceil(H/2), ceil(W/2), 4C]
+int witw_space_to_depth2_bf16(const float* x, void* y_bf16, int B, int Hp, int Wp, int H, int W, int C, const float* scale,
+                              const float* shift, void* stream) {
+    WITW_CHECK_ARG(x && y_bf16, "space_to_depth2_bf16: null pointer");
+    WITW_CHECK_ARG(B > 0 && C > 0 && (C & 3) == 0 && H > 0 && W > 0 && H <= Hp && W <= Wp, "space_to_depth2_bf16: bad shape (C=%d must be a multiple of 4)", C);
+    WITW_CHECK_ARG((scale == nullptr) == (shift == nullptr), "space_to_depth2_bf16: scale and shift go together");
+    const int V = (C & 7) == 0 ? 8 : 4;
+    const size_t total = (size_t)B * ((H + 1) / 2) * ((W + 1) / 2) * 4 * (C / V);
+    WITW_CHECK_ARG((total + 255) / 256 <= 0x7fffffffULL, "space_to_depth2_bf16: tensor too large");
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (V == 8)
+        hipLaunchKernelGGL((space_to_depth2_quad_kernel<__bf16, 8>), grid, dim3(256), 0, (hipStream_t)stream, x, (__bf16*)y_bf16, Hp, Wp, H, W, C,
+                           total, scale, shift);
+    else
+        hipLaunchKernelGGL((space_to_depth2_quad_kernel<__bf16, 4>), grid, dim3(256), 0, (hipStream_t)stream, x, (__bf16*)y_bf16, Hp, Wp, H, W, C,
+                           total, scale, shift);
+    WITW_CHECK_LAUNCH("space_to_depth2_bf16");
     return WITW_OK;
+}
+
+int witw_space_to_depth2_mosaic(const float* x, float* y, int B, int H, int W, int C, int g, void* stream) {
+    return s2d_mosaic_launch("space_to_depth2_mosaic", x, y, B, H, W, C, g, stream);
+}
+
+// witw_space_to_depth2_mosaic with a bf16 output: x fp32 NHWC [B,H,W,C] -> y bf16 [ceil(B/g^2), g*ceil(H/2), g*ceil(W/2), 4C], one
+// nearest-even rounding, +0.0 where no source exists.
+int witw_space_to_depth2_mosaic_bf16(const float* x, void* y_bf16, int B, int H, int W, int C, int g, void* stream) {
+    return s2d_mosaic_launch("space_to_depth2_mosaic_bf16", x, (__bf16*)y_bf16, B, H, W, C, g, stream);
 }
 
 // ws: the [ksplit][Bm, g*h, g*w, C] partial sums witw_conv3x3_fwd_taps4_ex(ksplit > 1) wrote for B images laid out as g x g

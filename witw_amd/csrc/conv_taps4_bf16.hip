@@ -270,46 +270,6 @@ __global__ void pack_weights_taps4_bf16_kernel(const float* __restrict__ w, unsi
     reinterpret_cast<bf16x8*>(wpk)[idx] = v;
 }
 
-// witw_space_to_depth2 (NHWC source, Cp == 4C) with a bf16 store: one thread per V = 8 or 4 channels of one quadrant,
-// y[b,h2,w2,q*C+c] = bf16(x[b,2h2+(q>>1),2w2+(q&1),c] * scale[c] + shift[c]) inside the H x W valid region, +0.0 outside it (the
-// affine is NOT applied there). The fp32 arithmetic is space_to_depth2_quad_kernel's; one nearest-even rounding at the store.
-template <int V>
-__global__ void space_to_depth2_bf16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, int Hp, int Wp, int H, int W, int C,
-                                            size_t total, const float* __restrict__ scale, const float* __restrict__ shift) {
-    typedef __bf16 bf16xv __attribute__((ext_vector_type(V)));
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int H2 = (H + 1) >> 1, W2 = (W + 1) >> 1, CV = C / V;
-    const int cv = idx % CV;
-    size_t t = idx / CV;
-    const int q = t & 3;
-    t >>= 2;
-    const int w2 = t % W2;
-    t /= W2;
-    const int h2 = t % H2;
-    const size_t b = t / H2;
-    const int h = 2 * h2 + (q >> 1), w = 2 * w2 + (q & 1);
-    bf16xv o;
-#pragma unroll
-    for (int j = 0; j < V; ++j) o[j] = (__bf16)0.f;
-    if (h < H && w < W) {
-        const float* src = x + ((b * Hp + h) * Wp + w) * C + V * cv;
-#pragma unroll
-        for (int k = 0; k < V / 4; ++k) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * k);
-            if (scale != nullptr) {
-                const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + V * cv + 4 * k);
-                const f32x4 sf = *reinterpret_cast<const f32x4*>(shift + V * cv + 4 * k);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = v[j] * sc[j] + sf[j];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[4 * k + j] = (__bf16)v[j];
-        }
-    }
-    reinterpret_cast<bf16xv*>(y)[idx] = o;
-}
-
 // y[i] = bf16(x[i]), nearest-even: four elements per thread, the tail one at a time
 __global__ void f32_to_bf16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, size_t n) {
     typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -419,26 +379,6 @@ int witw_conv3x3_bf16_fwd_taps4_plain(const void* x_bf16, const void* wpk_bf16, 
     a.off = 1 - tap_base; a.act = lrelu != 0;
     a.xcd_map = witw_conv_xcd_map();
     return launch_taps4_bf<true, true>(a, (hipStream_t)stream);
-}
-
-// x fp32 NHWC [B,Hp,Wp,C] (C % 4 == 0) with valid region H x W, scale / shift fp32 [C] or both NULL -> y bf16 [B, ceil(H/2), ceil(W/2), 4C]
-int witw_space_to_depth2_bf16(const float* x, void* y_bf16, int B, int Hp, int Wp, int H, int W, int C, const float* scale,
-                              const float* shift, void* stream) {
-    WITW_CHECK_ARG(x && y_bf16, "space_to_depth2_bf16: null pointer");
-    WITW_CHECK_ARG(B > 0 && C > 0 && (C & 3) == 0 && H > 0 && W > 0 && H <= Hp && W <= Wp, "space_to_depth2_bf16: bad shape (C=%d must be a multiple of 4)", C);
-    WITW_CHECK_ARG((scale == nullptr) == (shift == nullptr), "space_to_depth2_bf16: scale and shift go together");
-    const int V = (C & 7) == 0 ? 8 : 4;
-    const size_t total = (size_t)B * ((H + 1) / 2) * ((W + 1) / 2) * 4 * (C / V);
-    WITW_CHECK_ARG((total + 255) / 256 <= 0x7fffffffULL, "space_to_depth2_bf16: tensor too large");
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (V == 8)
-        hipLaunchKernelGGL(space_to_depth2_bf16_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, x, (unsigned short*)y_bf16, Hp, Wp, H, W, C,
-                           total, scale, shift);
-    else
-        hipLaunchKernelGGL(space_to_depth2_bf16_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, (unsigned short*)y_bf16, Hp, Wp, H, W, C,
-                           total, scale, shift);
-    WITW_CHECK_LAUNCH("space_to_depth2_bf16");
-    return WITW_OK;
 }
 
 int witw_f32_to_bf16(const float* x, void* y_bf16, long long n, void* stream) {

@@ -1,6 +1,6 @@
 // Split-K form of the bf16 2x2-tap convolution (conv_taps4_bf16.hip) for blocks 5-7 of cvig_baseline's encoders at inference
 // (SurfaceEncoder(precision='bf16_all')): maps of 16 x 16 and below with K = 4 taps x 2048 channels, laid out as g x g mosaics of
-// space-to-depth(2) cells (witw_space_to_depth2_mosaic_bf16 below; g = 1 is the plain batch block 4 hands over). bf16 operands, fp32
+// space-to-depth(2) cells (witw_space_to_depth2_mosaic_bf16, baseline.hip; g = 1 is the plain batch block 4 hands over). bf16 operands, fp32
 // accumulation on v_mfma_f32_16x16x32_bf16 (gfx950), RAW fp32 partial sums of one K slice per workgroup into a workspace
 //
 //   ws[s, b, y, x, n] = sum_{c in slice s} sum_{ty,tx in {0,1}} x[b, y+ty, x+tx, c] * k3[n, c, 1+ty, 1+tx]      (x zero past H / W)
@@ -24,7 +24,6 @@
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SK_TW = 16, SK_TH = 16, SK_TN = 128, SK_NW = 4;
 
@@ -212,42 +211,6 @@ __global__ __launch_bounds__(64 * SK_NW) __attribute__((amdgpu_waves_per_eu(2, 2
     }
 }
 
-// s2d_mosaic_kernel (baseline.hip) with one nearest-even rounding at a bf16 store: x fp32 NHWC [B,H,W,C] -> y bf16
-// [ceil(B/g^2), g*H2, g*W2, 4C], +0.0 where no source exists. One thread per V channels of one output pixel's quadrant.
-template <int V>
-__global__ void s2d_mosaic_bf16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, int B, int H, int W, int C, int g,
-                                       size_t total) {
-    typedef __bf16 out_v __attribute__((ext_vector_type(V)));
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int H2 = (H + 1) >> 1, W2 = (W + 1) >> 1;
-    const int CV = C / V;
-    const int cv = idx % CV;
-    size_t t = idx / CV;
-    const int q = t & 3;
-    t >>= 2;
-    const int X = t % (g * W2);
-    t /= (g * W2);
-    const int Y = t % (g * H2);
-    const int bm = (int)(t / (g * H2));
-    const int cy = Y / H2, y2 = Y - cy * H2, cx = X / W2, x2 = X - cx * W2;
-    const int b = (bm * g + cy) * g + cx;
-    const int h = 2 * y2 + (q >> 1), w = 2 * x2 + (q & 1);
-    out_v o;
-#pragma unroll
-    for (int j = 0; j < V; ++j) o[j] = (__bf16)0.f;
-    if (b < B && h < H && w < W) {
-        const float* src = x + (((size_t)b * H + h) * W + w) * C + V * cv;
-#pragma unroll
-        for (int j = 0; j < V; j += 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(src + j);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[j + e] = (__bf16)v[e];
-        }
-    }
-    reinterpret_cast<out_v*>(y)[idx] = o;
-}
-
 int forced_ksplit() {
     const char* e = getenv("WITW_CONV_KSPLIT");
     return e ? atoi(e) : 0;
@@ -301,23 +264,6 @@ int witw_conv3x3_bf16_fwd_taps4_splitk(const void* x_bf16, const void* wpk_bf16,
     hipLaunchKernelGGL(conv_taps4_splitk_bf16_kernel, dim3((unsigned)grid, (unsigned)ksplit), dim3(64 * SK_NW), 0, (hipStream_t)stream, a);
     WITW_CHECK_LAUNCH("conv_taps4_splitk_bf16");
     witw_note_variant("conv_taps4_splitk_bf16_kernel");
-    return WITW_OK;
-}
-
-// witw_space_to_depth2_mosaic with a bf16 output: x fp32 NHWC [B,H,W,C] -> y bf16 [ceil(B/g^2), g*ceil(H/2), g*ceil(W/2), 4C], one
-// nearest-even rounding, +0.0 where no source exists.
-int witw_space_to_depth2_mosaic_bf16(const float* x, void* y_bf16, int B, int H, int W, int C, int g, void* stream) {
-    WITW_CHECK_ARG(x && y_bf16, "space_to_depth2_mosaic_bf16: null pointer");
-    WITW_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && g >= 1 && g <= 64, "space_to_depth2_mosaic_bf16: bad shape");
-    const int V = (C & 7) == 0 ? 8 : 4;
-    const size_t total = (size_t)cdiv(B, g * g) * (g * ((H + 1) / 2)) * (g * ((W + 1) / 2)) * 4 * (C / V);
-    WITW_CHECK_ARG((total + 255) / 256 <= 0x7fffffffULL, "space_to_depth2_mosaic_bf16: tensor too large");
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (V == 8)
-        hipLaunchKernelGGL(s2d_mosaic_bf16_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, x, (unsigned short*)y_bf16, B, H, W, C, g, total);
-    else
-        hipLaunchKernelGGL(s2d_mosaic_bf16_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, (unsigned short*)y_bf16, B, H, W, C, g, total);
-    WITW_CHECK_LAUNCH("space_to_depth2_mosaic_bf16");
     return WITW_OK;
 }
 

@@ -32,6 +32,17 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _post_affine(name, post_scale, post_shift, cout):
+    """The per-channel affine behind a conv epilogue: both None, or both fp32 on the device with Cout entries -> (post_scale, post_shift)"""
+    if (post_scale is None) != (post_shift is None):
+        raise _lib.WitwError('%s: post_scale and post_shift come together' % name)
+    if post_scale is not None:
+        post_scale, post_shift = _dev_f32(post_scale, 'post_scale'), _dev_f32(post_shift, 'post_shift')
+        if post_scale.numel() != cout or post_shift.numel() != cout:
+            raise _lib.WitwError('%s: post_scale/post_shift must have Cout entries' % name)
+    return post_scale, post_shift
+
+
 def _prof_begin():
     """Open a PROFILE bracket on the launch stream: None when nobody measures, else the (start, end) events, start recorded."""
     if PROFILE is None:
@@ -296,10 +307,7 @@ def conv3x3_fwd(x_nhwc, packed, stride_h=1, circular=False, relu=True, pool=Fals
     B, _h, W, C = x.shape
     H, flop_rows, y, drop_scale = _conv_fwd_setup('conv3x3_fwd', x, C, packed, stride_h, pool, out_nchw, dilate_h, out_h, drop_scale, gate)
     act = 2 if lrelu_slope is not None else int(bool(relu))
-    if post_scale is not None:
-        post_scale, post_shift = _dev_f32(post_scale, 'post_scale'), _dev_f32(post_shift, 'post_shift')
-        if post_scale.numel() != packed.cout or post_shift.numel() != packed.cout:
-            raise _lib.WitwError('post_scale/post_shift must have Cout entries')
+    post_scale, post_shift = _post_affine('conv3x3_fwd', post_scale, post_shift, packed.cout)
     code = torch.empty(y.shape, dtype=torch.uint8, device=x.device) if (pool and want_pool_code) else None
     prof = _prof_begin()
     if getattr(packed, 'taps4', False):
@@ -334,10 +342,7 @@ def _taps4_args(x_nhwc, packed, lrelu_slope, post_scale, post_shift):
         raise _lib.WitwError('a taps4-packed filter is required')
     if x.shape[3] != packed.cin_pad:
         raise _lib.WitwError('conv taps4: input has %d channels, packed weights expect %d' % (x.shape[3], packed.cin_pad))
-    if post_scale is not None:
-        post_scale, post_shift = _dev_f32(post_scale, 'post_scale'), _dev_f32(post_shift, 'post_shift')
-        if post_scale.numel() != packed.cout or post_shift.numel() != packed.cout:
-            raise _lib.WitwError('post_scale/post_shift must have Cout entries')
+    post_scale, post_shift = _post_affine('conv taps4', post_scale, post_shift, packed.cout)
     act = 2 if lrelu_slope is not None else 0
     return x, act, post_scale, post_shift
 
@@ -372,10 +377,7 @@ def conv4x4s2_first(x_nchw, weight, bias, post_scale=None, post_shift=None, norm
     B, C, H, W = x.shape
     if tuple(w.shape) != (64, C, 4, 4) or tuple(b.shape) != (64,):
         raise _lib.WitwError('conv4x4s2_first: weight %s / bias %s do not fit a %d-channel input' % (tuple(w.shape), tuple(b.shape), C))
-    if (post_scale is None) != (post_shift is None):
-        raise _lib.WitwError('conv4x4s2_first: post_scale and post_shift come together')
-    if post_scale is not None:
-        post_scale, post_shift = _dev_f32(post_scale, 'post_scale'), _dev_f32(post_shift, 'post_shift')
+    post_scale, post_shift = _post_affine('conv4x4s2_first', post_scale, post_shift, 64)
     vh, vw = (H - 4) // 2 + 1, (W - 4) // 2 + 1
     y = torch.empty((B, (vh + 1) // 2, (vw + 1) // 2, 256), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device)
     prof = _prof_begin()
