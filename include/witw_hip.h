@@ -719,7 +719,8 @@ int witw_k3_to_conv4x4(const float* k3, float* w, int co, int ci, int cpad, void
 
 /* ---- JPEG back end on the device: what libjpeg does behind entropy decoding for the images the reference reads
  *      (skimage.io.imread -> PIL -> libjpeg-turbo, model/cvig_fov.py:88-89, in the DataLoader workers of :402). The entropy
- *      decoding stays on the host (witw_amd/csrc_host/jpeg_coef.cpp -> libwitw_jpeg.so: witw_jpeg_info, witw_jpeg_decode_coef).
+ *      decoding stays on the host (witw_amd/csrc_host/jpeg_coef.cpp -> libwitw_jpeg.so: witw_jpeg_info, witw_jpeg_decode_coef;
+ *      their _ex forms take progressive files too, all scans decoded into the same coefficient blocks).
  *      Byte-identical to Pillow's decode (JDCT_ISLOW, fancy upsampling).
  * witw_jpeg_idct: dequantisation + 'islow' integer inverse DCT. coef: DEVICE int16 [total_blocks][64] natural order; qt: DEVICE
  * uint16 [tables][64]; planes: DEVICE int64 [n_planes][6] = {first block, table index, byte offset of the output plane, blocks

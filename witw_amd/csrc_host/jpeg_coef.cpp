@@ -3,6 +3,8 @@
 // DC prediction, de-zigzag -- of baseline / extended-sequential 8-bit JFIF files into quantised DCT coefficient blocks. Everything
 // behind it (dequantisation, the integer 'islow' inverse DCT, chroma upsampling, YCbCr -> RGB) runs on the GPU
 // (csrc/jpeg.hip). Plain C ABI, no GPU runtime: DataLoader workers load this library, never libwitw_hip.so.
+// Opt-in (the _ex entry points with flag bit 0): PROGRESSIVE files (SOF2) too -- every scan of the file is decoded here into the same
+// coefficient blocks its sequential twin would hold (decode_progressive below), so the device back end does not know the difference.
 //
 // Coefficient layout: component c holds bh[c] x bw[c] blocks (the MCU-padded block grid, raster order), each 64 int16 in NATURAL
 // (row-major) order; components follow one another. Quantisation tables: 64 uint16 per component, natural order.
@@ -116,12 +118,45 @@ struct Parsed {
     int scan_ncomp, scan_comp[4];
     bool jfif, adobe;         // APP0 'JFIF' / APP14 'Adobe' seen (libjpeg picks the colour space from them, jdapimin.c)
     int adobe_transform;
+    bool progressive;         // SOF2 (accepted only on request): `scan` is then the length field of the FIRST SOS segment
     int status;               // 0 ok, < 0 see witw_jpeg_* below
 };
 
 inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
-int parse(const uint8_t* d, size_t n, Parsed& P) {
+bool read_dqt(Parsed& P, const uint8_t* s, int sl) {
+    int k = 0;
+    while (k < sl) {
+        const int pq = s[k] >> 4, tq = s[k] & 15;
+        ++k;
+        if (tq > 3 || pq > 1 || k + 64 * (pq + 1) > sl) return false;
+        for (int j = 0; j < 64; ++j) {
+            P.qt[tq][ZZ[j]] = (uint16_t)(pq ? be16(s + k + 2 * j) : s[k + j]);
+        }
+        P.qt_present[tq] = true;
+        k += 64 * (pq + 1);
+    }
+    return true;
+}
+
+bool read_dht(Parsed& P, const uint8_t* s, int sl) {
+    int k = 0;
+    while (k < sl) {
+        if (k + 17 > sl) return false;
+        const int tc = s[k] >> 4, th = s[k] & 15;
+        if (tc > 1 || th > 3) return false;
+        int nsym = 0;
+        for (int j = 0; j < 16; ++j) nsym += s[k + 1 + j];
+        if (nsym > 256 || k + 17 + nsym > sl) return false;
+        if (!build_huff(tc ? P.ac[th] : P.dc[th], s + k + 1, s + k + 17, nsym, tc != 0)) return false;
+        k += 17 + nsym;
+    }
+    return true;
+}
+
+// accept_progressive: a SOF2 file that meets the constraints of a sequential one parses too (P.progressive); its scans are
+// validated one by one as they are decoded (decode_progressive)
+int parse(const uint8_t* d, size_t n, Parsed& P, bool accept_progressive = false) {
     memset(&P, 0, sizeof(P));
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return -1;
     size_t i = 2;
@@ -139,18 +174,8 @@ int parse(const uint8_t* d, size_t n, Parsed& P) {
         const uint8_t* s = d + i + 2;
         const int sl = len - 2;
         if (m == 0xDB) {
-            int k = 0;
-            while (k < sl) {
-                const int pq = s[k] >> 4, tq = s[k] & 15;
-                ++k;
-                if (tq > 3 || pq > 1 || k + 64 * (pq + 1) > sl) return -1;
-                for (int j = 0; j < 64; ++j) {
-                    P.qt[tq][ZZ[j]] = (uint16_t)(pq ? be16(s + k + 2 * j) : s[k + j]);
-                }
-                P.qt_present[tq] = true;
-                k += 64 * (pq + 1);
-            }
-        } else if (m == 0xC0 || m == 0xC1) {
+            if (!read_dqt(P, s, sl)) return -1;
+        } else if (m == 0xC0 || m == 0xC1 || (m == 0xC2 && accept_progressive)) {
             if (sl < 6 || s[0] != 8) return -2;                   // 8-bit samples only
             P.H = be16(s + 1); P.W = be16(s + 3); P.ncomp = s[5];
             if (P.H <= 0 || P.W <= 0 || (P.ncomp != 1 && P.ncomp != 3) || sl < 6 + 3 * P.ncomp) return -2;
@@ -161,20 +186,11 @@ int parse(const uint8_t* d, size_t n, Parsed& P) {
                 if (P.c[c].h < 1 || P.c[c].h > 2 || P.c[c].v < 1 || P.c[c].v > 2 || P.c[c].tq > 3) return -2;
             }
             have_sof = true;
+            P.progressive = m == 0xC2;
         } else if (m == 0xC2 || (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) {
             return -2;                                              // progressive / lossless / arithmetic: host decoder
         } else if (m == 0xC4) {
-            int k = 0;
-            while (k < sl) {
-                if (k + 17 > sl) return -1;
-                const int tc = s[k] >> 4, th = s[k] & 15;
-                if (tc > 1 || th > 3) return -1;
-                int nsym = 0;
-                for (int j = 0; j < 16; ++j) nsym += s[k + 1 + j];
-                if (nsym > 256 || k + 17 + nsym > sl) return -1;
-                if (!build_huff(tc ? P.ac[th] : P.dc[th], s + k + 1, s + k + 17, nsym, tc != 0)) return -1;
-                k += 17 + nsym;
-            }
+            if (!read_dht(P, s, sl)) return -1;
         } else if (m == 0xE0) {                                     // jdmarker.c examine_app0
             if (sl >= 14 && !memcmp(s, "JFIF\0", 5)) P.jfif = true;
         } else if (m == 0xEE) {                                     // jdmarker.c examine_app14
@@ -184,6 +200,7 @@ int parse(const uint8_t* d, size_t n, Parsed& P) {
             P.restart = be16(s);
         } else if (m == 0xDA) {
             if (!have_sof || sl < 1) return -1;
+            if (P.progressive) { P.scan = d + i; break; }          // the first of several scans: decode_progressive walks them
             const int ns = s[0];
             if (ns != P.ncomp || sl < 1 + 2 * ns + 3) return -2;   // one interleaved scan with every component
             for (int k = 0; k < ns; ++k) {
@@ -222,7 +239,8 @@ int parse(const uint8_t* d, size_t n, Parsed& P) {
         P.c[c].bw = P.mcux * P.c[c].h; P.c[c].bh = P.mcuy * P.c[c].v;
         P.c[c].off = off;
         off += (int64_t)P.c[c].bw * P.c[c].bh;
-        if (!P.qt_present[P.c[c].tq] || !P.dc[P.c[c].td].present || !P.ac[P.c[c].ta].present) return -1;
+        // (a progressive file names its tables scan by scan)
+        if (!P.progressive && (!P.qt_present[P.c[c].tq] || !P.dc[P.c[c].td].present || !P.ac[P.c[c].ta].present)) return -1;
     }
     return 0;
 }
@@ -234,60 +252,26 @@ Parsed& parsed() {
     return *p;
 }
 
-}  // namespace
+// The entropy-coded bytes of ONE scan, unstuffed once: FF 00 -> FF, RSTn markers dropped (their byte positions kept), any other marker
+// ends the data; zeros behind the end so that the bit reader may run ahead. One per thread, reused from file to file.
+struct Unstuffed {
+    // PAD zero bytes behind the data: a block of a corrupt stream can read at most 64 x (16 + 15 + 1) + 63 bits = 264 bytes past the
+    // end before the per-block check of the decoders stops the decode
+    static constexpr size_t PAD = 512;
+    uint8_t* clean = nullptr;
+    size_t clean_cap = 0;
+    uint32_t* rst_pos = nullptr;      // position in `clean` | number of the RSTn marker << 29
+    size_t rst_cap = 0;
+    size_t w = 0, n_rst = 0;          // bytes in `clean`, restart markers seen
 
-extern "C" {
-
-// info[0..]: H, W, ncomp, hmax, vmax, total blocks, then per component (4 slots): h, v, blocks wide, blocks high.
-// Returns 0; -1 = not a decodable JPEG stream; -2 = a JPEG this decoder leaves to the host library (progressive, arithmetic,
-// 12-bit, CMYK, non-interleaved scans, sampling other than 4:4:4 / 4:2:2 (h2v1) / 4:2:0 / grey, RGB-colourspace files: Adobe
-// transform 0 or component ids 'R','G','B' without a JFIF marker).
-int witw_jpeg_info(const uint8_t* data, size_t n, int32_t* info /* 22 */) {
-    Parsed& P = parsed();
-    const int rc = parse(data, n, P);
-    if (rc) return rc;
-    info[0] = P.H; info[1] = P.W; info[2] = P.ncomp; info[3] = P.hmax; info[4] = P.vmax;
-    int64_t total = 0;
-    for (int c = 0; c < 4; ++c) {
-        const bool on = c < P.ncomp;
-        info[6 + 4 * c] = on ? P.c[c].h : 0; info[7 + 4 * c] = on ? P.c[c].v : 0;
-        info[8 + 4 * c] = on ? P.c[c].bw : 0; info[9 + 4 * c] = on ? P.c[c].bh : 0;
-        if (on) total += (int64_t)P.c[c].bw * P.c[c].bh;
-    }
-    info[5] = (int32_t)total;
-    return 0;
-}
-
-// coef: total blocks x 64 int16 (zero-filled here); qt: ncomp x 64 uint16. Returns 0 or a negative code as above; -3 = the
-// entropy-coded data ended early or holds an invalid code (the blocks decoded so far are kept, the rest stay zero).
-int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t* qt) {
-    Parsed& P = parsed();
-    int rc = parse(data, n, P);
-    if (rc) return rc;
-    int64_t total = 0;
-    for (int c = 0; c < P.ncomp; ++c) {
-        total += (int64_t)P.c[c].bw * P.c[c].bh;
-        memcpy(qt + 64 * c, P.qt[P.c[c].tq], 128);
-        P.c[c].pred = 0;
-    }
-    memset(coef, 0, (size_t)total * 128);
-    // ---- unstuff the entropy-coded segment once: FF 00 -> FF, RSTn markers dropped (their byte positions kept), any other
-    // marker ends the data; zeros behind the end so that the bit reader may run ahead
-    static thread_local uint8_t* clean = nullptr;
-    static thread_local size_t clean_cap = 0;
-    static thread_local uint32_t* rst_pos = nullptr;
-    static thread_local size_t rst_cap = 0;
-    const size_t seg = (size_t)(data + n - P.scan);
-    // PAD zero bytes behind the data: a block of a corrupt stream can read at most 64 x (16 + 15) bits = 248 bytes past the end
-    // before the per-block check below stops the decode
-    constexpr size_t PAD = 512;
-    if (clean_cap < seg + PAD) { delete[] clean; clean_cap = seg + PAD + seg / 4; clean = new uint8_t[clean_cap]; }
-    const size_t max_rst = P.restart ? (size_t)P.mcux * P.mcuy / P.restart + 2 : 1;
-    if (rst_cap < max_rst) { delete[] rst_pos; rst_cap = max_rst + max_rst / 4; rst_pos = new uint32_t[rst_cap]; }
-    size_t w = 0, n_rst = 0;
-    {
-        const uint8_t* q = P.scan;
-        const uint8_t* e = data + n;
+    // q: first entropy-coded byte, e: end of the file, max_rst: restart markers the scan can hold -> where the data ended (the FF of a
+    // marker, or e when the file ends first)
+    const uint8_t* load(const uint8_t* q, const uint8_t* e, size_t max_rst) {
+        const size_t seg = (size_t)(e - q);
+        if (clean_cap < seg + PAD) { delete[] clean; clean_cap = seg + PAD + seg / 4; clean = new uint8_t[clean_cap]; }
+        if (rst_cap < max_rst) { delete[] rst_pos; rst_cap = max_rst + max_rst / 4; rst_pos = new uint32_t[rst_cap]; }
+        w = n_rst = 0;
+        const uint8_t* end = e;
         while (q < e) {
             const uint8_t* f = (const uint8_t*)memchr(q, 0xFF, (size_t)(e - q));
             if (!f) { memcpy(clean + w, q, (size_t)(e - q)); w += (size_t)(e - q); break; }
@@ -298,10 +282,44 @@ int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t
             if (m == 0) { clean[w++] = 0xFF; q = f + 2; }
             else if (m >= 0xD0 && m <= 0xD7) { if (n_rst < rst_cap) rst_pos[n_rst++] = (uint32_t)w | ((uint32_t)(m - 0xD0) << 29); q = f + 2; }
             else if (m == 0xFF) { q = f + 1; }
-            else break;                                     // EOI or another marker: the entropy-coded data ends here
+            else { end = f; break; }                        // EOI or another marker: the entropy-coded data ends here
         }
+        memset(clean + w, 0, PAD);     // the reader loads 8 bytes at a time and may run ahead by one block
+        return end;
     }
-    memset(clean + w, 0, PAD);     // the reader loads 8 bytes at a time and may run ahead by one block
+};
+
+Unstuffed& unstuffed() {
+    static thread_local Unstuffed u;
+    return u;
+}
+
+void fill_info(const Parsed& P, int32_t* info) {
+    info[0] = P.H; info[1] = P.W; info[2] = P.ncomp; info[3] = P.hmax; info[4] = P.vmax;
+    int64_t total = 0;
+    for (int c = 0; c < 4; ++c) {
+        const bool on = c < P.ncomp;
+        info[6 + 4 * c] = on ? P.c[c].h : 0; info[7 + 4 * c] = on ? P.c[c].v : 0;
+        info[8 + 4 * c] = on ? P.c[c].bw : 0; info[9 + 4 * c] = on ? P.c[c].bh : 0;
+        if (on) total += (int64_t)P.c[c].bw * P.c[c].bh;
+    }
+    info[5] = (int32_t)total;
+}
+
+// the one interleaved scan of a sequential file (P: parse() == 0) -> 0 / -3
+int decode_sequential(Parsed& P, const uint8_t* data, size_t n, int16_t* coef, uint16_t* qt) {
+    int64_t total = 0;
+    for (int c = 0; c < P.ncomp; ++c) {
+        total += (int64_t)P.c[c].bw * P.c[c].bh;
+        memcpy(qt + 64 * c, P.qt[P.c[c].tq], 128);
+        P.c[c].pred = 0;
+    }
+    memset(coef, 0, (size_t)total * 128);
+    Unstuffed& U = unstuffed();
+    U.load(P.scan, data + n, P.restart ? (size_t)P.mcux * P.mcuy / P.restart + 2 : 1);
+    const uint8_t* const clean = U.clean;
+    const uint32_t* const rst_pos = U.rst_pos;
+    const size_t w = U.w, n_rst = U.n_rst;
     Bits b;
     b.init(clean);
     int to_restart = P.restart, next_rst = 0;
@@ -364,6 +382,278 @@ int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t
         }
     if (overran(w)) return -3;
     return 0;
+}
+
+// ---- progressive files (T.81 annex G; the procedures are those of libjpeg's jdphuff.c). The scans of a file refine one set of
+// coefficient blocks: a DC scan (Ss = 0) codes the DC differences of one or several components down to bit Al, or (Ah > 0) one more
+// bit of each; an AC scan codes the band Ss..Se of ONE component down to bit Al, with runs of blocks whose band is empty folded into
+// one EOBn symbol (EOBRUN, up to 32,767 blocks), or (Ah > 0) one more bit of it: a correction bit for every coefficient that is
+// non-zero already, new coefficients of +-(1 << Al) between them. A scan of one component walks THAT component's own block grid
+// (ceil(w_c / 8) x ceil(h_c / 8), raster order), not the MCU-padded grid of the coefficient area.
+
+inline int get_bit(Bits& b) { if (b.n < 1) b.fill(); return b.get(1); }
+
+struct ScanHeader { int ns, comp[4], Ss, Se, Ah, Al; };
+
+inline int dc_first(Bits& b, const Huff& hd, int16_t* blk, int Al, int& pred) {
+    if (b.n < 32) b.fill();
+    const int s = decode_sym(b, hd);
+    if (s < 0 || s > 15) return -3;
+    if (s) pred = (int16_t)(pred + extend(b.get(s), s));      // (kept in 16 bits: a hostile stream cannot overflow the sum)
+    blk[0] = (int16_t)(pred * (1 << Al));
+    return 0;
+}
+
+inline int ac_first(Bits& b, const Huff& ha, int16_t* blk, const ScanHeader& S, int& eobrun) {
+    if (eobrun > 0) { --eobrun; return 0; }                       // the band of this block is empty
+    for (int k = S.Ss; k <= S.Se;) {
+        if (b.n < 32) b.fill();
+        const int32_t fa = ha.fast_ac[b.peek(FAST)];
+        if (fa) {                                                 // code and value in one look-up
+            k += (fa >> 8) & 15;
+            if (k > S.Se) return -3;
+            b.skip(fa & 255);
+            blk[ZZ[k++]] = (int16_t)((fa >> 16) * (1 << S.Al));
+            continue;
+        }
+        const int rs = decode_sym(b, ha);
+        if (rs < 0) return -3;
+        const int r = rs >> 4, s = rs & 15;
+        if (s) {
+            k += r;
+            if (k > S.Se) return -3;
+            blk[ZZ[k++]] = (int16_t)(extend(b.get(s), s) * (1 << S.Al));
+        } else if (r == 15) {
+            k += 16;
+        } else {                                                  // EOBr: this block and 2^r - 1 + (r bits) more end here
+            eobrun = (1 << r) - 1;
+            if (r) eobrun += b.get(r);
+            break;
+        }
+    }
+    return 0;
+}
+
+inline int ac_refine(Bits& b, const Huff& ha, int16_t* blk, const ScanHeader& S, int& eobrun) {
+    const int p1 = 1 << S.Al, m1 = -p1;
+    auto correct = [&](int16_t& c) { if (get_bit(b) && !(c & p1)) c = (int16_t)(c + (c >= 0 ? p1 : m1)); };
+    int k = S.Ss;
+    if (eobrun == 0) {
+        while (k <= S.Se) {
+            if (b.n < 32) b.fill();
+            const int rs = decode_sym(b, ha);
+            if (rs < 0) return -3;
+            int r = rs >> 4, val = 0;
+            if (rs & 15) {                                        // a new coefficient behind r zero ones: size 1, a sign bit
+                if ((rs & 15) != 1) return -3;
+                val = b.get(1) ? p1 : m1;
+            } else if (r != 15) {                                 // EOBr: the rest of this block's band below, then 2^r - 1 + (r bits) blocks
+                eobrun = 1 << r;
+                if (r) eobrun += b.get(r);
+                break;
+            }
+            // pass r coefficients that are still zero (ZRL: 16 of them); the non-zero ones on the way take a correction bit each
+            for (; k <= S.Se; ++k) {
+                int16_t& c = blk[ZZ[k]];
+                if (c) correct(c);
+                else if (--r < 0) break;
+            }
+            if (val) {
+                if (k > S.Se) return -3;
+                blk[ZZ[k]] = (int16_t)val;
+            }
+            ++k;
+        }
+    }
+    if (eobrun > 0) {                                             // inside an EOB run: correction bits only
+        for (; k <= S.Se; ++k)
+            if (blk[ZZ[k]]) correct(blk[ZZ[k]]);
+        --eobrun;
+    }
+    return 0;
+}
+
+// the entropy-coded data of one scan, loaded into U -> 0 / -3
+int decode_scan(Parsed& P, const ScanHeader& S, const Unstuffed& U, int16_t* coef) {
+    const uint8_t* const clean = U.clean;
+    const bool interleaved = S.ns > 1;
+    int cols = P.mcux, rows = P.mcuy;
+    if (!interleaved) {                                           // the component's own blocks
+        const Comp& C = P.c[S.comp[0]];
+        cols = ((P.W * C.h + P.hmax - 1) / P.hmax + 7) / 8;
+        rows = ((P.H * C.v + P.vmax - 1) / P.vmax + 7) / 8;
+    }
+    Bits b;
+    b.init(clean);
+    int to_restart = P.restart, next_rst = 0, eobrun = 0;
+    size_t rst_i = 0;
+    auto interval_end = [&]() { return rst_i < U.n_rst ? (size_t)(U.rst_pos[rst_i] & 0x1fffffffu) : U.w; };
+    size_t seg_end = interval_end();
+    for (int c = 0; c < P.ncomp; ++c) P.c[c].pred = 0;
+    for (int my = 0; my < rows; ++my)
+        for (int mx = 0; mx < cols; ++mx) {
+            if (P.restart && to_restart == 0) {
+                if (rst_i >= U.n_rst || (int)(U.rst_pos[rst_i] >> 29) != next_rst) return -3;
+                b.init(clean + seg_end);
+                ++rst_i;
+                seg_end = interval_end();
+                next_rst = (next_rst + 1) & 7;
+                to_restart = P.restart;
+                eobrun = 0;
+                for (int c = 0; c < P.ncomp; ++c) P.c[c].pred = 0;
+            }
+            for (int k = 0; k < S.ns; ++k) {
+                Comp& C = P.c[S.comp[k]];
+                const int nh = interleaved ? C.h : 1, nv = interleaved ? C.v : 1;
+                for (int v = 0; v < nv; ++v)
+                    for (int h = 0; h < nh; ++h) {
+                        int16_t* blk = coef + (C.off + (int64_t)(my * nv + v) * C.bw + (mx * nh + h)) * 64;
+                        int rc = 0;
+                        if (S.Ss == 0) {
+                            if (S.Ah == 0) rc = dc_first(b, P.dc[C.td], blk, S.Al, C.pred);
+                            else if (get_bit(b)) blk[0] |= (int16_t)(1 << S.Al);
+                        } else {
+                            rc = S.Ah == 0 ? ac_first(b, P.ac[C.ta], blk, S, eobrun) : ac_refine(b, P.ac[C.ta], blk, S, eobrun);
+                        }
+                        if (rc) return rc;
+                        // bits taken from behind the interval's own data (the next interval's, or the zeros behind the end): damaged.
+                        // Checked block by block, so that at most the block at the damage holds anything decoded from them
+                        if ((size_t)(b.p - clean) * 8 - (size_t)b.n > seg_end * 8) return -3;
+                    }
+            }
+            if (P.restart) --to_restart;
+        }
+    return 0;
+}
+
+// P: parse(accept_progressive) == 0 and P.progressive. Walks the marker segments from the first SOS to EOI: tables and the restart
+// interval may change between scans; every scan is checked against what the earlier ones left (bits[c][k]: the bit position
+// coefficient k of component c has been refined down to, -1 = not coded yet -- libjpeg's coef_bits, but an inconsistency is an error
+// here where libjpeg warns and goes on). -> 0; -2 = the file ends before every coefficient has reached bit 0 (libjpeg smooths
+// such a file between blocks: its pixels are not those of these coefficients); -3 = damaged
+int decode_progressive(Parsed& P, const uint8_t* d, size_t n, int16_t* coef, uint16_t* qt) {
+    int64_t total = 0;
+    for (int c = 0; c < P.ncomp; ++c) {
+        total += (int64_t)P.c[c].bw * P.c[c].bh;
+        memcpy(qt + 64 * c, P.qt[P.c[c].tq], 128);
+    }
+    memset(coef, 0, (size_t)total * 128);
+    int8_t bits[4][64];
+    memset(bits, -1, sizeof(bits));
+    bool latched[4] = {false, false, false, false};      // a component keeps the quantisation table in force at its first scan (jdinput.c)
+    Unstuffed& U = unstuffed();
+    size_t i = (size_t)(P.scan - d);                     // the length field of a marker segment
+    for (int m = 0xDA; m != 0xD9;) {
+        if (i + 2 > n) return -3;
+        const int len = be16(d + i);
+        if (len < 2 || i + len > n) return -3;
+        const uint8_t* s = d + i + 2;
+        const int sl = len - 2;
+        i += len;
+        if (m == 0xDB) {
+            if (!read_dqt(P, s, sl)) return -3;
+        } else if (m == 0xC4) {
+            if (!read_dht(P, s, sl)) return -3;
+        } else if (m == 0xDD) {
+            if (sl < 2) return -3;
+            P.restart = be16(s);
+        } else if (m == 0xDA) {
+            ScanHeader S;
+            S.ns = sl ? s[0] : 0;
+            if (S.ns < 1 || S.ns > P.ncomp || sl < 1 + 2 * S.ns + 3) return -3;
+            S.Ss = s[1 + 2 * S.ns]; S.Se = s[2 + 2 * S.ns]; S.Ah = s[3 + 2 * S.ns] >> 4; S.Al = s[3 + 2 * S.ns] & 15;
+            // T.81 G.1.1.1.1 / jdphuff.c start_pass_phuff_decoder: DC alone, an AC band of one component, one bit per refinement
+            if (S.Ss == 0 ? S.Se != 0 : (S.Ss > S.Se || S.Se > 63 || S.ns != 1)) return -3;
+            if (S.Al > 13 || (S.Ah && S.Ah != S.Al + 1)) return -3;
+            for (int k = 0; k < S.ns; ++k) {
+                int ci = -1;
+                for (int c = 0; c < P.ncomp; ++c) if (P.c[c].id == s[1 + 2 * k]) ci = c;
+                for (int j = 0; j < k; ++j) if (S.comp[j] == ci) ci = -1;
+                if (ci < 0) return -3;
+                S.comp[k] = ci;
+                Comp& C = P.c[ci];
+                C.td = s[2 + 2 * k] >> 4; C.ta = s[2 + 2 * k] & 15;
+                if (C.td > 3 || C.ta > 3) return -3;
+                if (S.Ss == 0 ? (S.Ah == 0 && !P.dc[C.td].present) : !P.ac[C.ta].present) return -3;
+                if (S.Ss && bits[ci][0] < 0) return -3;                                   // AC before the component's DC
+                for (int kk = S.Ss; kk <= S.Se; ++kk) {
+                    if (bits[ci][kk] != (S.Ah ? S.Ah : -1)) return -3;                    // coded twice, or not down to Ah yet
+                    bits[ci][kk] = (int8_t)S.Al;
+                }
+                if (!latched[ci]) {
+                    if (!P.qt_present[C.tq]) return -3;
+                    memcpy(qt + 64 * ci, P.qt[C.tq], 128);
+                    latched[ci] = true;
+                }
+            }
+            const Comp& C0 = P.c[S.comp[0]];
+            const size_t units = S.ns > 1 ? (size_t)P.mcux * P.mcuy : (size_t)C0.bw * C0.bh;
+            const uint8_t* end = U.load(d + i, d + n, P.restart ? units / P.restart + 2 : 1);
+            const int rc = decode_scan(P, S, U, coef);
+            if (rc) return rc;
+            i = (size_t)(end - d);
+        } else if (m >= 0xC0 && m <= 0xCF) {
+            return -3;                                                                    // a second frame header, arithmetic conditioning
+        }                                                                                 // (APPn, COM, ...: skipped)
+        if (i + 2 > n || d[i] != 0xFF) return -3;                                         // no EOI: the file is cut short
+        while (i < n && d[i] == 0xFF) ++i;
+        if (i >= n) return -3;
+        m = d[i++];
+        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m <= 0x01) return -3;               // no segment, and none of them belongs here
+    }
+    for (int c = 0; c < P.ncomp; ++c)
+        for (int k = 0; k < 64; ++k)
+            if (bits[c][k] != 0) return -2;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// info[0..]: H, W, ncomp, hmax, vmax, total blocks, then per component (4 slots): h, v, blocks wide, blocks high.
+// Returns 0; -1 = not a decodable JPEG stream; -2 = a JPEG this decoder leaves to the host library (progressive, arithmetic,
+// 12-bit, CMYK, non-interleaved scans, sampling other than 4:4:4 / 4:2:2 (h2v1) / 4:2:0 / grey, RGB-colourspace files: Adobe
+// transform 0 or component ids 'R','G','B' without a JFIF marker).
+int witw_jpeg_info(const uint8_t* data, size_t n, int32_t* info /* 22 */) {
+    Parsed& P = parsed();
+    const int rc = parse(data, n, P);
+    if (rc) return rc;
+    fill_info(P, info);
+    return 0;
+}
+
+// coef: total blocks x 64 int16 (zero-filled here); qt: ncomp x 64 uint16. Returns 0 or a negative code as above; -3 = the
+// entropy-coded data ended early or holds an invalid code (the blocks decoded so far are kept, the rest stay zero).
+int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t* qt) {
+    Parsed& P = parsed();
+    const int rc = parse(data, n, P);
+    if (rc) return rc;
+    return decode_sequential(P, data, n, coef, qt);
+}
+
+// flags bit 0 = accept progressive files (SOF2) that meet the constraints above (8-bit, 1 or 3 components, the same samplings and
+// colour spaces); every other bit is reserved (0). With flags == 0 the two are witw_jpeg_info / witw_jpeg_decode_coef.
+enum { WITW_JPEG_ACCEPT_PROGRESSIVE = 1 };
+
+// As witw_jpeg_info, and 1 = a progressive file this decoder takes (only the header has been looked at: witw_jpeg_decode_coef_ex
+// says whether its scans are legal and complete).
+int witw_jpeg_info_ex(const uint8_t* data, size_t n, int32_t* info /* 22 */, int flags) {
+    Parsed& P = parsed();
+    const int rc = parse(data, n, P, (flags & WITW_JPEG_ACCEPT_PROGRESSIVE) != 0);
+    if (rc) return rc;
+    fill_info(P, info);
+    return P.progressive ? 1 : 0;
+}
+
+// As witw_jpeg_decode_coef (same layout: a progressive file gives the blocks its sequential twin would); for a progressive file
+// -3 also = a scan the earlier scans do not allow (Ss / Se / Ah / Al), and -2 = the file ends before every coefficient of every
+// component has been refined down to bit 0 (the host library smooths such a file: leave it there).
+int witw_jpeg_decode_coef_ex(const uint8_t* data, size_t n, int16_t* coef, uint16_t* qt, int flags) {
+    Parsed& P = parsed();
+    const int rc = parse(data, n, P, (flags & WITW_JPEG_ACCEPT_PROGRESSIVE) != 0);
+    if (rc) return rc;
+    return P.progressive ? decode_progressive(P, data, n, coef, qt) : decode_sequential(P, data, n, coef, qt);
 }
 
 // ---- entropy decoding ON THE DEVICE for files that carry restart markers (csrc/jpeg.hip, jpeg_huffman_kernel: one GPU thread per

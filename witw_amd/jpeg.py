@@ -4,7 +4,9 @@
 decode time); the coefficient blocks of a batch cross PCIe as one block and the GPU does the rest (csrc/jpeg.hip:
 dequantisation, integer inverse DCT, fancy chroma upsampling, YCbCr -> RGB) into the same interleaved uint8 image Pillow
 produces, byte for byte. Files this decoder leaves alone (progressive, arithmetic-coded, CMYK, 12-bit, unusual sampling) are
-decoded by Pillow in the worker as before and travel as bytes in the same batch.
+decoded by Pillow in the worker as before and travel as bytes in the same batch. Opt-in (PROGRESSIVE below): progressive
+files are entropy-decoded by the worker too -- all their scans, into the blocks a sequential file would hold -- and take the same
+route through the GPU.
 
 Nothing here touches the GPU at import or in a worker: libwitw_jpeg.so is host-only C++."""
 import ctypes
@@ -31,6 +33,12 @@ DESC_COLS = 30         # per image: coefficient byte offset, quantisation-table 
 # WITW_JPEG_DEVICE_ENTROPY = 0 | off | restart | 1 | all.
 _mode = os.environ.get('WITW_JPEG_DEVICE_ENTROPY', 'all').lower()
 DEVICE_ENTROPY = False if _mode in ('0', 'off', 'false') else 'restart' if _mode in ('restart', '1') else 'all'
+# Progressive files (SOF2): off = left to Pillow in the worker (pixels cross PCIe); on = the worker decodes their scans into coefficient
+# blocks (witw_jpeg_decode_coef_ex) and the GPU finishes them like any other file -- always by the host-coefficient route, whatever
+# DEVICE_ENTROPY says: scans refine one another, the device entropy decoders do not apply. A file whose scans stop short of full
+# precision stays Pillow's (libjpeg smooths it). WITW_JPEG_PROGRESSIVE = 1 | on | true; open_file / read_coef(progressive=...) override it.
+PROGRESSIVE = os.environ.get('WITW_JPEG_PROGRESSIVE', '').lower() in ('1', 'on', 'true')
+ACCEPT_PROGRESSIVE = 1     # flag bit 0 of witw_jpeg_info_ex / witw_jpeg_decode_coef_ex
 CHECK_ERRORS = True    # decode_packed(host_buf=...) re-decodes files the device flagged as damaged with Pillow (as the host path does)
 REPAIRED = [0]         # how many files that happened to
 SELFSYNC_MIN_BLOCKS = 96   # a marker-less file of at most this many blocks is decoded by ONE thread of the interval kernel (a 1024-thread
@@ -48,6 +56,10 @@ def host_lib():
         lib.witw_jpeg_info.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         lib.witw_jpeg_decode_coef.restype = ctypes.c_int
         lib.witw_jpeg_decode_coef.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        lib.witw_jpeg_info_ex.restype = ctypes.c_int
+        lib.witw_jpeg_info_ex.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
+        lib.witw_jpeg_decode_coef_ex.restype = ctypes.c_int
+        lib.witw_jpeg_decode_coef_ex.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         lib.witw_jpeg_entropy_plan_bytes.restype = ctypes.c_longlong
         lib.witw_jpeg_entropy_plan_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
         lib.witw_jpeg_entropy_plan.restype = ctypes.c_longlong
@@ -71,21 +83,28 @@ class JpegCoef(object):
 
 class JpegFile(JpegCoef):
     """A JPEG file whose header has been parsed (info) but whose entropy-coded data is still to be decoded: pack() decodes it
-    straight into its place in the batch block (no array of its own, no copy). `coef` / `qt` decode on demand."""
-    __slots__ = ('data',)
+    straight into its place in the batch block (no array of its own, no copy). `coef` / `qt` decode on demand. progressive: a
+    progressive file (open_file(progressive=True)): all its scans are decoded on the host, never on the device."""
+    __slots__ = ('data', 'progressive')
 
-    def __init__(self, info, data):
-        self.info, self.data = info, data
+    def __init__(self, info, data, progressive=False):
+        self.info, self.data, self.progressive = info, data, progressive
 
     def decode_into(self, coef, qt):
-        """coef int16 [blocks, 64], qt uint16 [components, 64]: views of the destination. -> False if the entropy data is bad."""
+        """coef int16 [blocks, 64], qt uint16 [components, 64]: views of the destination. -> False if the entropy data is bad (or,
+        progressive, its scans are illegal or stop short of full precision)."""
+        if self.progressive:
+            return host_lib().witw_jpeg_decode_coef_ex(self.data.ctypes.data, self.data.size, coef.ctypes.data, qt.ctypes.data,
+                                                       ACCEPT_PROGRESSIVE) == 0
         return host_lib().witw_jpeg_decode_coef(self.data.ctypes.data, self.data.size, coef.ctypes.data, qt.ctypes.data) == 0
 
     def entropy_plan(self):
         """What the DEVICE needs to entropy-decode this file itself (csrc_host/jpeg_coef.cpp witw_jpeg_entropy_plan: header fields,
         Huffman tables, the byte offset of every restart interval) -> (plan uint8 array, qt uint16 [components, 64]), or None for a
         file without restart markers (or one this scheme leaves to the host: more than two tables of a kind, markers out of
-        sequence). A byte scan of the file, no Huffman decoding."""
+        sequence, a progressive file). A byte scan of the file, no Huffman decoding."""
+        if self.progressive:
+            return None
         lib = host_lib()
         n = int(lib.witw_jpeg_entropy_plan_bytes(self.data.ctypes.data, self.data.size))
         if n <= 0:
@@ -115,28 +134,30 @@ class JpegFile(JpegCoef):
     qt = property(lambda self: self._decoded()[1])
 
 
-def open_file(src):
+def open_file(src, progressive=None):
     """src: a path or the bytes of a JPEG file -> JpegFile (header parsed, entropy decoding deferred to pack()), or None when the
-    file is left to the host decoder."""
+    file is left to the host decoder. progressive: take progressive files too (None: the module flag PROGRESSIVE)."""
     data = np.fromfile(src, dtype=np.uint8) if isinstance(src, (str, os.PathLike)) else np.frombuffer(src, dtype=np.uint8)
     info = np.zeros(22, dtype=np.int32)
+    if PROGRESSIVE if progressive is None else progressive:
+        rc = host_lib().witw_jpeg_info_ex(data.ctypes.data, data.size, info.ctypes.data, ACCEPT_PROGRESSIVE)
+        return JpegFile(info, data, progressive=rc == 1) if rc in (0, 1) else None
     if host_lib().witw_jpeg_info(data.ctypes.data, data.size, info.ctypes.data) != 0:
         return None
     return JpegFile(info, data)
 
 
-def read_coef(src):
-    """src: a path or the bytes of a JPEG file -> JpegCoef, or None when the file is left to the host decoder."""
-    data = np.fromfile(src, dtype=np.uint8) if isinstance(src, (str, os.PathLike)) else np.frombuffer(src, dtype=np.uint8)
-    lib = host_lib()
-    info = np.zeros(22, dtype=np.int32)
-    if lib.witw_jpeg_info(data.ctypes.data, data.size, info.ctypes.data) != 0:
+def read_coef(src, progressive=None):
+    """src: a path or the bytes of a JPEG file -> JpegCoef, or None when the file is left to the host decoder. progressive: as
+    open_file."""
+    f = open_file(src, progressive)
+    if f is None:
         return None
-    coef = np.empty((int(info[5]), 64), dtype=np.int16)
-    qt = np.empty((int(info[2]), 64), dtype=np.uint16)
-    if lib.witw_jpeg_decode_coef(data.ctypes.data, data.size, coef.ctypes.data, qt.ctypes.data) != 0:
+    coef = np.empty((int(f.info[5]), 64), dtype=np.int16)
+    qt = np.empty((int(f.info[2]), 64), dtype=np.uint16)
+    if not f.decode_into(coef, qt):
         return None               # truncated / corrupt entropy data: let the host decoder say what it thinks of the file
-    return JpegCoef(info, coef, qt)
+    return JpegCoef(f.info, coef, qt)
 
 
 def _shared_bytes(n):
