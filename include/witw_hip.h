@@ -606,6 +606,35 @@ int witw_bn_lrelu_bwd(const float* a, const float* dy, float* dz, float* dgamma,
 int witw_bn_lrelu_bwd_ex(const float* a, const float* dy, float* dz, float* dgamma, float* dbeta, const float* mean,
                          const float* invstd, const float* gamma, int B, int Hp, int Wp, int H, int W, int C, float slope,
                          int dy_s2d_cp, float* workspace, void* stream);
+/* ---- the same BatchNorm2d cut where a collective fits (csrc/baseline_bn_sync.hip): statistics of a batch that is spread over N
+ * ranks. Each direction is: partial sums on every rank -> the caller SUMS the [2*C] vectors and the counts over the ranks -> a second
+ * entry uses the summed vector and the global count. With one rank the two run back to back, no collective. Tensors, valid region,
+ * dy_s2d_cp and `workspace` (witw_bn_workspace_floats(B, H, W, C) floats, contents on entry irrelevant) are as in the entries above.
+ * Every sum is taken in a fixed order without atomics: a repeated call gives the same bits. A refusal (non-zero return) launches
+ * nothing and writes nothing; nothing is written outside the named outputs and the workspace.
+ * bn_partial_stats: part[c] = S1 = sum (a - pivot[c]), part[C + c] = S2 = sum (a - pivot[c])^2 over the valid region (any number of
+ *   values per channel, one included). pivot [C] is an INPUT and must hold the same values on every rank whose sums are added (the
+ *   layer's running_mean as it stood before the step); the closer it is to the mean, the less of the variance is lost to cancellation.
+ * bn_finalize_stats: part_sum [2*C] = the sums of every rank added, count = the values per channel behind them (global B*H*W):
+ *   mean = pivot + S1/n, biased var = max(0, S2/n - (S1/n)^2), invstd = (var + eps)^-1/2, scale = gamma * invstd, shift = beta -
+ *   mean * scale; running_mean / running_var (both NULL or neither) updated with `momentum` and the unbiased variance var * n / (n - 1).
+ *   pivot may be running_mean itself. count <= 1 is REFUSED, as witw_bn_train_stats refuses one value per channel (torch raises there
+ *   too): running_var has no unbiased update at n = 1, and nothing is written.
+ * bn_lrelu_bwd_partial: part[c] = sum dy, part[C + c] = sum dy * xhat, xhat = (a - mean[c]) * invstd[c], over the valid region.
+ * bn_lrelu_bwd_apply: sums [2*C] = those vectors of every rank added, count = the global values per channel (>= this tensor's own
+ *   B*H*W, else refused) -> dz = lrelu'(a) * gamma * invstd * (dy - sums[c]/n - xhat * sums[C + c]/n) on the valid region, 0 outside
+ *   it, every element of dz written: what witw_bn_lrelu_bwd_ex writes when count is its own B*H*W. dbeta = sums[0..C) and dgamma =
+ *   sums[C..2C) are the GLOBAL parameter gradients, complete on every rank. */
+int witw_bn_partial_stats(const float* a, int B, int Hp, int Wp, int H, int W, int C, const float* pivot, float* part,
+                          float* workspace, void* stream);
+int witw_bn_finalize_stats(const float* part_sum, const float* pivot, long long count, const float* gamma, const float* beta,
+                           float eps, float momentum, float* mean, float* invstd, float* scale, float* shift, float* running_mean,
+                           float* running_var, int C, void* stream);
+int witw_bn_lrelu_bwd_partial(const float* a, const float* dy, const float* mean, const float* invstd, int B, int Hp, int Wp, int H,
+                              int W, int C, int dy_s2d_cp, float* part, float* workspace, void* stream);
+int witw_bn_lrelu_bwd_apply(const float* a, const float* dy, float* dz, const float* mean, const float* invstd, const float* gamma,
+                            const float* sums, long long count, int B, int Hp, int Wp, int H, int W, int C, float slope,
+                            int dy_s2d_cp, void* stream);
 /* inverse of witw_space_to_depth2 for gradients: g [B,ceil(H/2),ceil(W/2),Cpad] -> dx [B,Hp,Wp,C] (+ add, may be NULL) */
 int witw_depth_to_space2(const float* g, const float* add, float* dx, int B, int Hp, int Wp, int H, int W, int C, int Cpad,
                          void* stream);

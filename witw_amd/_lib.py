@@ -101,6 +101,10 @@ SIGNATURES = {
     'witw_bn_train_stats': (c_int, [c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_float, c_float] + [c_void_p] * 8),
     'witw_bn_lrelu_bwd': (c_int, [c_void_p] * 8 + [c_int] * 6 + [c_float, c_void_p, c_void_p]),
     'witw_bn_lrelu_bwd_ex': (c_int, [c_void_p] * 8 + [c_int] * 6 + [c_float, c_int, c_void_p, c_void_p]),
+    'witw_bn_partial_stats': (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 4),
+    'witw_bn_finalize_stats': (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_float, c_float] + [c_void_p] * 6 + [c_int, c_void_p]),
+    'witw_bn_lrelu_bwd_partial': (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p] * 3),
+    'witw_bn_lrelu_bwd_apply': (c_int, [c_void_p] * 7 + [c_longlong] + [c_int] * 6 + [c_float, c_int, c_void_p]),
     'witw_depth_to_space2': (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p]),
     'witw_gem_pool_bwd': (c_int, [c_void_p] * 6 + [c_int] * 8 + [c_float, c_int, c_void_p]),
     'witw_embed_normalize_bwd': (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p]),

@@ -10,7 +10,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _lib, baseline_bf16, ops
+from . import _lib, baseline_bf16, baseline_parallel, ops
 from . import cvig_fov as _fov
 from .cvig_fov import Adam, recall_table  # noqa: F401  (same table, model/cvig_baseline.py:461-466)
 
@@ -33,6 +33,7 @@ class Globals:
 
 
     train_precision = 'fp32'  # arithmetic of the training step: 'fp32', or 'bf16' (forward, data and weight gradient of blocks 2-4 on the bf16 MFMA)
+    sync_bn = False           # training on N ranks: BatchNorm statistics of the global batch (True) or of every rank's own share (False, nn.DataParallel)
 
 
 PRECISIONS = ('fp32', 'bf16', 'bf16_all')
@@ -154,7 +155,7 @@ class SurfaceEncoder(nn.Module):
     """model/cvig_baseline.py:228-279; parameters live in nn.Conv2d / nn.BatchNorm2d children named
     conv1..7 / bn1..7 (same state-dict keys), the forward runs on the HIP kernels."""
 
-    def __init__(self, orientation=False, bands=3, p=3., precision=None, train_precision=None):
+    def __init__(self, orientation=False, bands=3, p=3., precision=None, train_precision=None, sync_bn=None):
         """precision: None = Globals.precision; 'fp32', or 'bf16' = the eval forward runs blocks 1-4 with bf16 operands and fp32
         accumulation (bf16 activations between them, fp32 into block 5; the filters are rounded from the fp32 master weights, the
         BatchNorm fold, blocks 5-7, pooling and normalisation stay fp32); 'bf16_all' = blocks 5-7 as well: block 4 stores bf16, blocks
@@ -163,8 +164,16 @@ class SurfaceEncoder(nn.Module):
         train_precision: None = Globals.train_precision; 'fp32', or 'bf16' = the training step runs the three convolutions of blocks 2-4
         (forward, data gradient, weight gradient) with bf16 operands and fp32 accumulation. Rounded once, nearest-even: the filters (from
         the fp32 master weights, per weight version), a block's input and a block's output gradient. Master weights, gradients, BatchNorm
-        statistics, LeakyReLU gates, blocks 1 and 5-7, pooling and the loss stay fp32. At most 5 input channels, as precision='bf16'."""
+        statistics, LeakyReLU gates, blocks 1 and 5-7, pooling and the loss stay fp32. At most 5 input channels, as precision='bf16'.
+        sync_bn: None = Globals.sync_bn; False = under a process group every rank normalises with the statistics of its own images (an
+        nn.DataParallel replica). True = the training step's seven BatchNorm layers take mean and variance over the GLOBAL batch: per layer
+        one all-reduce of 2C floats in the forward and one in the backward (baseline_parallel.sync_bn_train_stats / sync_bn_lrelu_bwd), the
+        running buffers are then the same on every rank, and the N-rank step is the one-process step on the concatenated batch up to
+        summation order. With no process group the same kernels run without a collective. Works under either train_precision (BatchNorm
+        is fp32 in both). Before the step's gradient all-reduce bnK.weight.grad / bnK.bias.grad hold 1/N of the gradient (see
+        sync_bn_lrelu_bwd). Never changes the eval forward."""
         super().__init__()
+        self.sync_bn = bool(Globals.sync_bn if sync_bn is None else sync_bn)
         self.precision = Globals.precision if precision is None else precision
         if self.precision not in PRECISIONS:
             raise _lib.WitwError("cvig_baseline encoder: precision must be 'fp32', 'bf16' or 'bf16_all', got %r" % (self.precision,))
@@ -372,6 +381,8 @@ class _BaselineEncoderFn(torch.autograd.Function):
             vh, vw = H, W
             saved = []
             bf = enc.train_precision == 'bf16'
+            if enc.sync_bn:      # BatchNorm over the global batch: its image count once per call, two sums per channel and layer
+                images = baseline_parallel.sync_bn_global_images(B, x.device)
             for i in range(1, 8):
                 on_bf16 = bf and 2 <= i <= 4
                 packed, _es, _et, _cp = enc._layer(i, fold=False, pack=not on_bf16)
@@ -384,8 +395,11 @@ class _BaselineEncoderFn(torch.autograd.Function):
                     a = baseline_bf16.conv_taps4_plain_bf16(h, enc._layer_bf16(i), (vh, vw), lrelu_slope=0.2)
                 else:
                     a = ops.conv3x3_fwd(h, packed, relu=False, lrelu_slope=0.2)              # LeakyReLU(conv), :267-275
-                mean, invstd, scale, shift = ops.bn_train_stats(a, (vh, vw), bn.weight, bn.bias, bn.running_mean,
-                                                                bn.running_var, bn.eps, bn.momentum)
+                if enc.sync_bn:
+                    mean, invstd, scale, shift = baseline_parallel.sync_bn_train_stats(a, (vh, vw), bn, images)
+                else:
+                    mean, invstd, scale, shift = ops.bn_train_stats(a, (vh, vw), bn.weight, bn.bias, bn.running_mean,
+                                                                    bn.running_var, bn.eps, bn.momentum)
                 bn.num_batches_tracked += 1
                 for t in (bn.running_mean, bn.running_var):      # updated through the C-ABI: invalidate the eval fold
                     t._witw_version = getattr(t, '_witw_version', 0) + 1
@@ -398,6 +412,7 @@ class _BaselineEncoderFn(torch.autograd.Function):
                     h = ops.space_to_depth2(a, valid_hw=(vh, vw), cpad=enc._layer(i + 1, fold=False)[3], scale=scale, shift=shift)
             f = ops.embed_normalize_(g.clone())
         ctx.enc, ctx.saved, ctx.g, ctx.bf = enc, saved, g, bf
+        ctx.sync_images = images if enc.sync_bn else None
         ctx.override = getattr(enc, '_bwd_override', {})
         enc._bwd_override = {}
         enc._last_saved = saved if getattr(enc, 'keep_activations', False) else None     # diagnostics / parity tests
@@ -420,7 +435,11 @@ class _BaselineEncoderFn(torch.autograd.Function):
                 ops.gem_pool_bwd(a, scale, shift, g, dg, valid, 512 * (i - 5), enc.p, out=dy)
             else:       # blocks 1-4 (the large maps): the BatchNorm backward reads the space-to-depth gradient in place
                 dy, s2d_grad = dx_s2d, True
-            dz, dgamma, dbeta = ops.bn_lrelu_bwd(ctx.override.get(i, a), dy, valid, mean, invstd, bn.weight, 0.2, dy_s2d=s2d_grad)
+            if ctx.sync_images is not None:
+                dz, dgamma, dbeta = baseline_parallel.sync_bn_lrelu_bwd(ctx.override.get(i, a), dy, valid, mean, invstd, bn.weight,
+                                                                        ctx.sync_images, 0.2, dy_s2d=s2d_grad)
+            else:
+                dz, dgamma, dbeta = ops.bn_lrelu_bwd(ctx.override.get(i, a), dy, valid, mean, invstd, bn.weight, 0.2, dy_s2d=s2d_grad)
             on_bf16 = ctx.bf and 2 <= i <= 4
             k3 = enc._layer_k3(i, pack=not on_bf16)
             if on_bf16:
@@ -907,7 +926,7 @@ def _bn_modules(*encoders):
 
 
 def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_epochs=999999, csv_path=None, seed=0, loss='exhaustive',
-          train_precision=None):
+          train_precision=None, sync_bn=None):
     """model/cvig_baseline.py:318-404 on the HIP kernels: same flow, prints and checkpoint names; Adam with torch's
     defaults (lr 1e-3) over every encoder parameter.
     Under an initialised process group (N ranks, one per GPU) it is the reference's nn.DataParallel run (:339-343) with a rank in
@@ -921,7 +940,11 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
     of the global batch instead (batch_hard_triplet_loss / sharded_batch_hard_loss), and validation then evaluates that loss, so
     that "best" is judged by the loss that is trained. train_precision: None = Globals.train_precision; 'fp32', or 'bf16' = the training
     step runs blocks 2-4 on the bf16 MFMA (SurfaceEncoder(train_precision='bf16')) and the validation phase runs the encoders' eval forward
-    with precision='bf16'. The same under N ranks; checkpoints are the fp32 master weights in either case."""
+    with precision='bf16'. The same under N ranks; checkpoints are the fp32 master weights in either case. sync_bn: None = Globals.sync_bn;
+    True = the BatchNorm layers of the training step normalise with the statistics of the GLOBAL batch instead (SurfaceEncoder(sync_bn=True):
+    two all-reduces of 2C floats per layer and direction), so that the N-rank step is the one-process step at the same batch_size; the
+    running statistics are then the same on every rank and "rank 0's are kept" holds trivially. On one rank it changes the summation
+    order only."""
     import pathlib
     import time
     from . import parallel
@@ -930,6 +953,7 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
     train_precision = Globals.train_precision if train_precision is None else train_precision
     if train_precision not in TRAIN_PRECISIONS:
         raise _lib.WitwError("train: train_precision must be 'fp32' or 'bf16', got %r" % (train_precision,))
+    sync_bn = bool(Globals.sync_bn if sync_bn is None else sync_bn)
     world, rank = parallel.world(), parallel.rank()
     if world > 1 and batch_size % world:
         raise _lib.WitwError('train: the global batch_size %d is not a multiple of the %d ranks' % (batch_size, world))
@@ -955,6 +979,7 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
         val_loader = torch.utils.data.DataLoader(val_set, batch_size=batch_size, shuffle=False, drop_last=False,
                                                  num_workers=num_workers, collate_fn=_fov.collate_raw)
     enc_kw = {'precision': 'bf16', 'train_precision': 'bf16'} if train_precision == 'bf16' else {'train_precision': 'fp32'}
+    enc_kw['sync_bn'] = sync_bn
     surface_encoder = SurfaceEncoder(**enc_kw).to(device)
     overhead_encoder = OverheadEncoder(**enc_kw).to(device)
     encoders = [surface_encoder, overhead_encoder]
@@ -1094,14 +1119,22 @@ def main(argv=None):
                         help='Train mode: arithmetic of the training step. fp32 = fp32 MFMA throughout; bf16 = forward, data gradient and '
                              'weight gradient of blocks 2-4 with bf16 operands and fp32 accumulation (fp32 master weights, statistics and '
                              'gradients), validation with the bf16 eval forward. [Default = fp32]')
+    parser.add_argument('--sync-bn', action='store_true',
+                        help='Train mode on N ranks: BatchNorm statistics of the global batch (two small all-reduces per layer and '
+                             'direction) instead of every rank normalising its own share as an nn.DataParallel replica does. '
+                             '[Default = off]')
     args = parser.parse_args(argv)
     if args.mode != 'train' and args.train_precision is not None:
         parser.error("--train-precision belongs to --mode train")
+    if args.mode != 'train' and args.sync_bn:
+        parser.error("--sync-bn belongs to --mode train")
     if args.mode == 'train' and args.precision != 'fp32':
         parser.error("--precision %s is inference only: --mode train runs in fp32 (use it with --mode test)" % args.precision)
     _fov.init_distributed()       # under `python -m torch.distributed.run --nproc-per-node N`: one process per GPU; else nothing
     if args.mode == 'train':
         extra = {} if args.train_precision is None else {'train_precision': args.train_precision}      # only when the flag was given
+        if args.sync_bn:
+            extra['sync_bn'] = True
         train(dataset=args.dataset, loss=args.loss, **extra)
     elif args.mode == 'test':
         test(dataset=args.dataset, match_method=args.match_method, precision=args.precision)

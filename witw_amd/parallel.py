@@ -12,9 +12,10 @@ model/cvig_baseline.py:339-343; normaliser 2B(B-1) with B = global batch, model/
   3. weight gradients (57.9 MB for both encoders) are summed with one all-reduce over a flat bucket.
 Retrieval (gallery >> queries) shards the gallery rows instead: rank counts are summed with an
 all-reduce of int32[queries].
-cvig_baseline's encoders DO have BatchNorm: there a rank stands for an nn.DataParallel replica -- batch statistics per rank, never
-synchronised, rank 0's running statistics kept (broadcast_buffers); its loss couples the global batch the same way
-(cvig_baseline.sharded_exhaustive_loss).
+cvig_baseline's encoders DO have BatchNorm: there a rank stands for an nn.DataParallel replica -- batch statistics per rank, rank 0's
+running statistics kept (broadcast_buffers); its loss couples the global batch the same way (cvig_baseline.sharded_exhaustive_loss).
+Opt-in (SurfaceEncoder(sync_bn=True)): the statistics of the global batch, two sums per channel all-reduced per layer and direction
+(baseline_parallel.sync_bn_train_stats / sync_bn_lrelu_bwd, phases 'bn_stats_all_reduce' / 'bn_grad_all_reduce').
 
 Everything here is backend-agnostic host logic (tested on CPU with gloo, world_size 2).
 """
