@@ -749,21 +749,25 @@ int witw_k3_to_conv4x4(const float* k3, float* w, int co, int ci, int cpad, void
 /* ---- JPEG back end on the device: what libjpeg does behind entropy decoding for the images the reference reads
  *      (skimage.io.imread -> PIL -> libjpeg-turbo, model/cvig_fov.py:88-89, in the DataLoader workers of :402). The entropy
  *      decoding stays on the host (witw_amd/csrc_host/jpeg_coef.cpp -> libwitw_jpeg.so: witw_jpeg_info, witw_jpeg_decode_coef;
- *      their _ex forms take progressive files too, all scans decoded into the same coefficient blocks).
+ *      their _ex forms take progressive files too, all scans decoded into the same coefficient blocks, and -- flag bit 1, also on
+ *      witw_jpeg_entropy_plan_ex -- 4:4:0 files: luma 1x2, an MCU of Y (top), Y (bottom), Cb, Cr).
  *      Byte-identical to Pillow's decode (JDCT_ISLOW, fancy upsampling).
  * witw_jpeg_idct: dequantisation + 'islow' integer inverse DCT. coef: DEVICE int16 [total_blocks][64] natural order; qt: DEVICE
  * uint16 [tables][64]; planes: DEVICE int64 [n_planes][6] = {first block, table index, byte offset of the output plane, blocks
  * wide, blocks high, blocks of all earlier planes}; out: the 8-bit component planes (bh*8 rows of bw*8 bytes). */
 int witw_jpeg_idct(const void* coef, const void* qt, const void* planes, int n_planes, long long total_blocks, void* out, void* stream);
 /* witw_jpeg_to_rgb: fancy chroma upsampling + YCbCr -> RGB. planes: the output above; images: DEVICE int64 [n_images][12] =
- * {H, W, components (1 | 3), mode (0 none, 1 h2v1, 2 h2v2 fancy, 3 / 4 the same replicated: chroma planes of <= 2 columns), luma offset, luma stride, Cb offset, Cr offset, chroma stride, chroma
+ * {H, W, components (1 | 3), mode (0 none, 1 h2v1, 2 h2v2 fancy, 3 / 4 the same replicated: chroma planes of <= 2 columns,
+ * 5 h1v2 fancy (4:4:0: chroma at full width, half height; (3 nearest row + next nearest + {1 upper | 2 lower}) >> 2, edge rows repeated, planes of any size)), luma offset, luma stride, Cb offset, Cr offset, chroma stride, chroma
  * rows, chroma columns (real samples), output offset}; out: H x W x components interleaved bytes per image. */
 int witw_jpeg_to_rgb(const void* planes, const void* images, int n_images, long long max_pixels, void* out, void* stream);
 /* Entropy decoding ON THE DEVICE for files that carry restart markers (the reference decodes in its loader workers,
  * model/cvig_fov.py:88-89, :402): one GPU thread per restart interval. files: DEVICE int64 [n_files][4] = {address of the file bytes
  * (8-byte aligned, 24 readable bytes behind the end), address of the file's plan (host side: witw_jpeg_entropy_plan in
  * libwitw_jpeg.so -- header fields, Huffman tables, byte offset of every interval; a byte scan, no Huffman decoding), address of the
- * file's coefficient area int16 [blocks][64] (zero-filled by the caller), file length}; max_intervals: the largest interval count of a
+ * file's coefficient area int16 [blocks][64] (zero-filled by the caller), file length}; the MCU geometry (blocks per MCU and where each
+ * lies in its component's grid: 4:4:4, 4:2:2, 4:2:0, grey, and 4:4:0 = Y, Y below it, Cb, Cr) comes from the plan's per-component
+ * (h, v); max_intervals: the largest interval count of a
  * file of the launch (grid sizing: one workgroup per 256 intervals of a file); errors: DEVICE int32 [n_files], zeroed by the
  * caller, 1 where a file's entropy-coded data is damaged, 2 for a bad plan. Coefficients bit-identical to the host decoder's
  * (witw_jpeg_decode_coef); witw_jpeg_idct / witw_jpeg_to_rgb take it from there. */

@@ -3,7 +3,15 @@
 (jpeg.open_file(progressive=True) + decode_into: coefficient blocks, the GPU does the rest) against Pillow's whole decode of the same
 bytes (what the worker does with the flag off). 512 x 512 images of photographic statistics (tests/golden/gen_jpeg_fixtures.py's
 generator), saved progressive at quality 88; per file: the median over the passes of (time of one pass over all files / files).
-Writes profiles/jpeg_progressive.json.   python tools/bench_jpeg_progressive.py [--files 64] [--passes 7]"""
+Writes profiles/jpeg_progressive.json.   python tools/bench_jpeg_progressive.py [--files 64] [--passes 7]
+
+--corpus 440: the same for 4:4:0 files (jpeg.SAMPLING_440; tests/jpeg_440_craft.py: the 4:2:2 timing images re-crafted as 4:4:0 from
+their transposed coefficient blocks, i.e. losslessly transposed). Opt-in on, a worker pays what DEVICE_ENTROPY leaves it -- the header
+parse and marker scan (entropy_plan, the default 'all'), or the host Huffman decode (decode_into); opt-in off, Pillow's whole decode.
+Writes profiles/jpeg_440.json, keeping an 'e2e' block that is already there.
+--e2e-440 DIR: the GPU half of that profile. A synthetic data set (witw_amd/e2e.py) whose 224 x 224 surfaces are re-crafted as 4:4:0,
+then `bench.py --mode e2e --workers 4 --precision bf16` as child processes, WITW_JPEG_440=1 and unset in alternating rounds; the
+median of each goes into the 'e2e' block of profiles/jpeg_440.json."""
 import argparse
 import io
 import json
@@ -35,6 +43,109 @@ def per_file_us(fn, blobs, passes):
     return statistics.median(t), min(t)
 
 
+def corpus_440(a):
+    import torch
+    from PIL import Image
+    from tests import jpeg_440_craft as C4
+    from witw_amd import jpeg
+    torch.set_num_threads(1)
+    g = np.random.Generator(np.random.Philox(key=[2026, 440]))
+    s422, s440 = [], []
+    for _ in range(a.files):
+        bio = io.BytesIO()
+        Image.fromarray(picture(g, a.size, a.size)).save(bio, 'JPEG', quality=a.quality, subsampling=1)
+        s422.append(bio.getvalue())
+        src = jpeg.read_coef(s422[-1])
+        s440.append(C4.write(a.size, a.size, *C4.transposed(src)))
+    first = jpeg.open_file(s440[0], h1v2=True)
+    coef = np.empty((int(first.info[5]), 64), dtype=np.int16)
+    qt = np.empty((int(first.info[2]), 64), dtype=np.uint16)
+
+    def host_huffman(blobs):
+        for b in blobs:
+            if not jpeg.open_file(b, h1v2=True).decode_into(coef, qt):
+                raise RuntimeError('decode failed')
+
+    def plan(blobs):
+        for b in blobs:
+            if jpeg.open_file(b, h1v2=True).entropy_plan() is None:
+                raise RuntimeError('no plan')
+
+    def pillow(blobs):
+        for b in blobs:
+            Image.open(io.BytesIO(b)).load()
+
+    for b, s in zip(s440, s422):                          # the numbers below are about a decoder that is right
+        assert np.array_equal(jpeg.read_coef(b, h1v2=True).coef, C4.transposed(jpeg.read_coef(s))[0])
+        assert np.array_equal(np.asarray(Image.open(io.BytesIO(b))), C4.decode(first.info, *C4.transposed(jpeg.read_coef(s))))
+    res = {}
+    for name, fn, blobs in (('440_host_header_and_marker_scan', plan, s440), ('440_host_entropy_decode', host_huffman, s440),
+                            ('440_pillow_full_decode', pillow, s440), ('422_host_entropy_decode', host_huffman, s422),
+                            ('422_pillow_full_decode', pillow, s422)):
+        med, best = per_file_us(fn, blobs, a.passes)
+        res[name] = {'us_per_file_median': round(med, 1), 'us_per_file_best': round(best, 1)}
+    pil = res['440_pillow_full_decode']['us_per_file_median']
+    return {'what': '%d 4:4:0 JPEG files, %d x %d, quality %d (the 4:2:2 files Pillow writes, losslessly transposed); one thread; per file = '
+                    'median over %d passes of (pass time / files). Opt-in off a worker pays 440_pillow_full_decode; opt-in on, '
+                    '440_host_header_and_marker_scan under DEVICE_ENTROPY all (the default), 440_host_entropy_decode with it off'
+                    % (a.files, a.size, a.size, a.quality, a.passes),
+            'mean_file_bytes': {'440': int(np.mean([len(b) for b in s440])), '422': int(np.mean([len(b) for b in s422]))},
+            'results': res,
+            '440_host_entropy_decode_over_pillow_full_decode': round(res['440_host_entropy_decode']['us_per_file_median'] / pil, 3),
+            '440_host_header_and_marker_scan_over_pillow_full_decode': round(res['440_host_header_and_marker_scan']['us_per_file_median'] / pil, 4),
+            'pillow': Image.__version__ if hasattr(Image, '__version__') else None}
+
+
+def _recraft_surface(path):
+    from tests import jpeg_440_craft as C4
+    from witw_amd import jpeg
+    from PIL import Image
+    a = np.asarray(Image.open(path))
+    bio = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(a.transpose(1, 0, 2))).save(bio, 'JPEG', quality=90, subsampling=1)
+    src = jpeg.read_coef(bio.getvalue())
+    data = C4.write(int(src.info[1]), int(src.info[0]), *C4.transposed(src))
+    with open(path + '.tmp', 'wb') as f:
+        f.write(data)
+    os.replace(path + '.tmp', path)
+    return len(data)
+
+
+def e2e_440(a):
+    """disk -> embeddings, 4 loader workers, bf16 encoders; surfaces 4:4:0; opt-in on against off, alternating rounds, medians"""
+    import multiprocessing as mp
+    import subprocess
+    from witw_amd import e2e
+    procs = min(16, len(os.sched_getaffinity(0)))
+    _csv, n_unique, _size = e2e.make_dataset(a.e2e_440, a.e2e_pairs, procs=procs)      # (its manifest keeps bench.py from writing the files again)
+    with mp.get_context('spawn').Pool(procs) as pool:
+        sizes = pool.map(_recraft_surface, [os.path.join(a.e2e_440, 'su_%05d.jpg' % i) for i in range(n_unique)], chunksize=8)
+    runs = {'on': [], 'off': []}
+    for r in range(a.rounds):
+        for mode in (('on', 'off') if r % 2 == 0 else ('off', 'on')):
+            env = dict(os.environ)
+            env.pop('WITW_JPEG_440', None)
+            if mode == 'on':
+                env['WITW_JPEG_440'] = '1'
+            fd_path = os.path.join(a.e2e_440, 'detail_%s_%d.json' % (mode, r))
+            cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--mode', 'e2e', '--e2e-pairs', str(a.e2e_pairs), '--workers', '4',
+                   '--precision', 'bf16', '--e2e-dir', a.e2e_440, '--no-decode-scaling', '--detail-out', fd_path]
+            p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+            if p.returncode != 0:
+                raise RuntimeError('bench.py --mode e2e failed (%d): %s' % (p.returncode, p.stderr[-800:]))
+            line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
+            d = json.load(open(fd_path)) if os.path.exists(fd_path) else line
+            runs[mode].append({'pairs_per_s': d.get('value', line.get('value')), 'steady_state_pairs_per_s': d.get('steady_state_pairs_per_s')})
+            print(mode, r, runs[mode][-1], flush=True)
+    med = {m: statistics.median(x['pairs_per_s'] for x in v) for m, v in runs.items()}
+    steady = {m: statistics.median(x['steady_state_pairs_per_s'] or 0 for x in v) for m, v in runs.items()}
+    return {'what': 'disk -> embeddings (bench.py --mode e2e): %d pairs over %d distinct, overhead 512 x 512 4:2:0 (Pillow), surface 224 x 224 '
+                    '4:4:0 (mean %d bytes); 4 loader workers, bf16 encoders, batch 128; WITW_JPEG_440=1 against unset in %d alternating '
+                    'rounds, one child process each; medians' % (a.e2e_pairs, n_unique, int(np.mean(sizes)), a.rounds),
+            'pairs_per_s_median': med, 'steady_state_pairs_per_s_median': steady, 'on_over_off': round(med['on'] / med['off'], 3),
+            'steady_state_on_over_off': round(steady['on'] / max(1e-9, steady['off']), 3), 'rounds': runs}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--files', type=int, default=64)
@@ -42,8 +153,32 @@ def main():
     ap.add_argument('--size', type=int, default=512)
     ap.add_argument('--quality', type=int, default=88)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'jpeg_progressive.json'))
+    ap.add_argument('--corpus', choices=['progressive', '440'], default='progressive')
+    ap.add_argument('--e2e-440', default=None, metavar='DIR')
+    ap.add_argument('--e2e-pairs', type=int, default=4096)
+    ap.add_argument('--rounds', type=int, default=3)
     a = ap.parse_args()
     assert a.files >= 64 and a.passes >= 5
+    if a.corpus == '440' or a.e2e_440:
+        out_path = a.out if a.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'jpeg_440.json')
+        try:
+            out = json.load(open(out_path))
+        except (OSError, ValueError):
+            out = {}
+        if a.e2e_440:
+            out['e2e'] = e2e_440(a)
+        else:
+            out = dict(corpus_440(a), **({'e2e': out['e2e']} if 'e2e' in out else {}))
+            try:
+                out['cpu'] = next(ln.split(':', 1)[1].strip() for ln in open('/proc/cpuinfo') if ln.startswith('model name'))
+            except (OSError, StopIteration):
+                pass
+        out.setdefault('e2e', 'unmeasured')
+        with open(out_path, 'w') as f:
+            json.dump(out, f, indent=1)
+            f.write('\n')
+        print(json.dumps(out))
+        return
     import torch
     from PIL import Image
     from witw_amd import jpeg

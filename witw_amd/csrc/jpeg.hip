@@ -4,7 +4,7 @@
 // whole batch cross PCIe and
 //   jpeg_idct_kernel    dequantises and runs libjpeg's 'islow' integer inverse DCT (jidctint.c: 13-bit constants, column pass
 //                       then row pass, range limit) -> one 8-bit plane per component,
-//   jpeg_to_rgb_kernel  'fancy' chroma upsampling (jdsample.c: h2v1 / h2v2 triangle filter with libjpeg's alternating rounding,
+//   jpeg_to_rgb_kernel  'fancy' chroma upsampling (jdsample.c: h2v1 / h2v2 / h1v2 triangle filter with libjpeg's alternating rounding,
 //                       edge rows / columns replicated) + YCbCr -> RGB (jdcolor.c, 16-bit fixed point) -> interleaved u8 HWC,
 // the byte layout PIL hands the reference (and witw_resize_bilinear_normalize_batched kind 1 / witw_polar_from_raw read).
 // Byte-identical to Pillow's decode: tests/test_jpeg*.py (fixtures under tests/golden/jpeg/ + files written at test time).
@@ -23,7 +23,7 @@ struct JpegPlane {       // one component of one image: int64 x 6 on the host si
 };
 
 struct JpegImage {       // int64 x 12
-    long long H, W, ncomp, mode;      // mode 0: no subsampling, 1: h2v1 fancy, 2: h2v2 fancy, 3 / 4: h2v1 / h2v2 replicated
+    long long H, W, ncomp, mode;      // mode 0: no subsampling, 1: h2v1 fancy, 2: h2v2 fancy, 3 / 4: h2v1 / h2v2 replicated, 5: h1v2 fancy
     long long y_off, y_stride, cb_off, cr_off, c_stride, ch, cw;      // chroma plane: ch x cw REAL samples
     long long out_off;                // byte offset of the H x W x ncomp output image
 };
@@ -123,10 +123,19 @@ __global__ __launch_bounds__(256) void jpeg_to_rgb_kernel(const unsigned char* _
     if (I.mode == 0) {
         cb = planes[I.cb_off + (long long)y * I.c_stride + x];
         cr = planes[I.cr_off + (long long)y * I.c_stride + x];
-    } else if (I.mode >= 3) {       // chroma planes of one or two columns: libjpeg replicates (h2v1_upsample / h2v2_upsample)
+    } else if (I.mode == 3 || I.mode == 4) {       // chroma planes of one or two columns: libjpeg replicates (h2v1_upsample / h2v2_upsample)
         const long long row = (I.mode == 4) ? (y >> 1) : y;
         cb = planes[I.cb_off + row * I.c_stride + (x >> 1)];
         cr = planes[I.cr_off + row * I.c_stride + (x >> 1)];
+    } else if (I.mode == 5) {       // h1v2 (4:4:0): (3 nearest row + next nearest row + {1 | 2}) >> 2, the upper output row of a pair looks up,
+                                    // the lower one down; beyond the plane the edge row again (h1v2_fancy_upsample: planes of any size)
+        const int ch = (int)I.ch;
+        const int cy = y >> 1;
+        const int yn = (y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0);
+        const int bias = (y & 1) ? 2 : 1;
+        const long long near = (long long)cy * I.c_stride + x, far = (long long)yn * I.c_stride + x;
+        cb = (3 * planes[I.cb_off + near] + planes[I.cb_off + far] + bias) >> 2;
+        cr = (3 * planes[I.cr_off + near] + planes[I.cr_off + far] + bias) >> 2;
     } else {
         const int cw = (int)I.cw, ch = (int)I.ch;
         const int cx = x >> 1;
@@ -845,7 +854,8 @@ int witw_jpeg_idct(const void* coef, const void* qt, const void* planes, int n_p
 }
 
 // planes: the output of witw_jpeg_idct; images: DEVICE int64 [n_images][12] = {H, W, components (1 | 3), mode (0: chroma at full
-// size, 1: h2v1, 2: h2v2 fancy upsampling, 3 / 4: the same by replication -- libjpeg's choice for chroma planes of <= 2 columns), luma plane offset, luma stride, Cb offset, Cr offset, chroma stride, chroma rows, chroma columns (real
+// size, 1: h2v1, 2: h2v2 fancy upsampling, 3 / 4: the same by replication -- libjpeg's choice for chroma planes of <= 2 columns,
+// 5: h1v2 (4:4:0) fancy upsampling: chroma at full width and half height, filtered whatever the plane's size), luma plane offset, luma stride, Cb offset, Cr offset, chroma stride, chroma rows, chroma columns (real
 // samples: ceil(H / 2) ...), output offset}; max_pixels = the largest H*W; out: H x W x components interleaved bytes per image.
 int witw_jpeg_to_rgb(const void* planes, const void* images, int n_images, long long max_pixels, void* out, void* stream) {
     WITW_CHECK_ARG(planes && images && out, "jpeg_to_rgb: null pointer");

@@ -5,6 +5,9 @@
 // (csrc/jpeg.hip). Plain C ABI, no GPU runtime: DataLoader workers load this library, never libwitw_hip.so.
 // Opt-in (the _ex entry points with flag bit 0): PROGRESSIVE files (SOF2) too -- every scan of the file is decoded here into the same
 // coefficient blocks its sequential twin would hold (decode_progressive below), so the device back end does not know the difference.
+// Opt-in (flag bit 1 of the _ex entry points): 4:4:0 files (h1v2: luma 1x2, chroma 1x1 -- a losslessly rotated 4:2:2 file). An MCU is
+// 8 x 16 pixels: Y (top), Y (bottom), Cb, Cr. Every decoder below takes its MCU geometry from the components' (h, v), so only parse()
+// knows the flag.
 //
 // Coefficient layout: component c holds bh[c] x bw[c] blocks (the MCU-padded block grid, raster order), each 64 int16 in NATURAL
 // (row-major) order; components follow one another. Quantisation tables: 64 uint16 per component, natural order.
@@ -155,8 +158,8 @@ bool read_dht(Parsed& P, const uint8_t* s, int sl) {
 }
 
 // accept_progressive: a SOF2 file that meets the constraints of a sequential one parses too (P.progressive); its scans are
-// validated one by one as they are decoded (decode_progressive)
-int parse(const uint8_t* d, size_t n, Parsed& P, bool accept_progressive = false) {
+// validated one by one as they are decoded (decode_progressive); accept_h1v2: three components sampled (1, 2), (1, 1), (1, 1) parse too
+int parse(const uint8_t* d, size_t n, Parsed& P, bool accept_progressive = false, bool accept_h1v2 = false) {
     memset(&P, 0, sizeof(P));
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return -1;
     size_t i = 2;
@@ -223,8 +226,9 @@ int parse(const uint8_t* d, size_t n, Parsed& P, bool accept_progressive = false
     for (int c = 0; c < P.ncomp; ++c) { if (P.c[c].h > P.hmax) P.hmax = P.c[c].h; if (P.c[c].v > P.vmax) P.vmax = P.c[c].v; }
     if (P.ncomp == 1) { P.c[0].h = P.c[0].v = 1; P.hmax = P.vmax = 1; }      // a single-component scan is never interleaved
     else if (P.c[1].h != 1 || P.c[1].v != 1 || P.c[2].h != 1 || P.c[2].v != 1 || P.c[0].h != P.hmax || P.c[0].v != P.vmax) return -2;
-    // the device back end upsamples h1v1, h2v1 and h2v2 only: 4:4:0 (h1v2, e.g. a losslessly rotated 4:2:2 file) goes to the host decoder
-    if (P.hmax == 1 && P.vmax == 2) return -2;
+    // 4:4:0 (h1v2, e.g. a losslessly rotated 4:2:2 file) goes to the host decoder unless the caller asked for it (the device back end
+    // upsamples h1v1, h2v1 and h2v2 and, for these callers, h1v2)
+    if (P.hmax == 1 && P.vmax == 2 && !accept_h1v2) return -2;
     // colour space as libjpeg's default_decompress_parms (jdapimin.c) decides it for three components: JFIF => YCbCr; else an
     // Adobe marker's transform flag (0 = RGB, 1 = YCbCr); else the component ids ('R','G','B' = RGB). The device back end always
     // applies YCbCr -> RGB, so every other case (and an unknown transform, which libjpeg warns about) is the host decoder's.
@@ -613,7 +617,7 @@ extern "C" {
 
 // info[0..]: H, W, ncomp, hmax, vmax, total blocks, then per component (4 slots): h, v, blocks wide, blocks high.
 // Returns 0; -1 = not a decodable JPEG stream; -2 = a JPEG this decoder leaves to the host library (progressive, arithmetic,
-// 12-bit, CMYK, non-interleaved scans, sampling other than 4:4:4 / 4:2:2 (h2v1) / 4:2:0 / grey, RGB-colourspace files: Adobe
+// 12-bit, CMYK, non-interleaved scans, sampling other than 4:4:4 / 4:2:2 (h2v1) / 4:2:0 / grey (4:4:0 on request: _ex), RGB-colourspace files: Adobe
 // transform 0 or component ids 'R','G','B' without a JFIF marker).
 int witw_jpeg_info(const uint8_t* data, size_t n, int32_t* info /* 22 */) {
     Parsed& P = parsed();
@@ -633,14 +637,15 @@ int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t
 }
 
 // flags bit 0 = accept progressive files (SOF2) that meet the constraints above (8-bit, 1 or 3 components, the same samplings and
-// colour spaces); every other bit is reserved (0). With flags == 0 the two are witw_jpeg_info / witw_jpeg_decode_coef.
-enum { WITW_JPEG_ACCEPT_PROGRESSIVE = 1 };
+// colour spaces); bit 1 = accept 4:4:0 sampling (h1v2: luma (h, v) = (1, 2), both chroma (1, 1)) beside the samplings above -- a
+// progressive 4:4:0 file needs both bits; every other bit is reserved (0). With flags == 0 the entries are their plain namesakes.
+enum { WITW_JPEG_ACCEPT_PROGRESSIVE = 1, WITW_JPEG_ACCEPT_H1V2 = 2 };
 
 // As witw_jpeg_info, and 1 = a progressive file this decoder takes (only the header has been looked at: witw_jpeg_decode_coef_ex
 // says whether its scans are legal and complete).
 int witw_jpeg_info_ex(const uint8_t* data, size_t n, int32_t* info /* 22 */, int flags) {
     Parsed& P = parsed();
-    const int rc = parse(data, n, P, (flags & WITW_JPEG_ACCEPT_PROGRESSIVE) != 0);
+    const int rc = parse(data, n, P, (flags & WITW_JPEG_ACCEPT_PROGRESSIVE) != 0, (flags & WITW_JPEG_ACCEPT_H1V2) != 0);
     if (rc) return rc;
     fill_info(P, info);
     return P.progressive ? 1 : 0;
@@ -651,7 +656,7 @@ int witw_jpeg_info_ex(const uint8_t* data, size_t n, int32_t* info /* 22 */, int
 // component has been refined down to bit 0 (the host library smooths such a file: leave it there).
 int witw_jpeg_decode_coef_ex(const uint8_t* data, size_t n, int16_t* coef, uint16_t* qt, int flags) {
     Parsed& P = parsed();
-    const int rc = parse(data, n, P, (flags & WITW_JPEG_ACCEPT_PROGRESSIVE) != 0);
+    const int rc = parse(data, n, P, (flags & WITW_JPEG_ACCEPT_PROGRESSIVE) != 0, (flags & WITW_JPEG_ACCEPT_H1V2) != 0);
     if (rc) return rc;
     return P.progressive ? decode_progressive(P, data, n, coef, qt) : decode_sequential(P, data, n, coef, qt);
 }
@@ -670,20 +675,23 @@ int witw_jpeg_decode_coef_ex(const uint8_t* data, size_t n, int16_t* coef, uint1
 // path (witw_jpeg_decode_coef) as before.
 enum { WITW_JPEG_PLAN_FIXED = 736 };
 
-long long witw_jpeg_entropy_plan_bytes(const uint8_t* data, size_t n) {      // 0: not a file for this decoder
+// (flags: bit 1 as above; a progressive file has no plan whatever bit 0 says: its scans refine one another)
+long long witw_jpeg_entropy_plan_bytes_ex(const uint8_t* data, size_t n, int flags) {      // 0: not a file for this decoder
     Parsed& P = parsed();
-    if (parse(data, n, P)) return 0;
+    if (parse(data, n, P, false, (flags & WITW_JPEG_ACCEPT_H1V2) != 0)) return 0;
     if (P.restart <= 0) return WITW_JPEG_PLAN_FIXED + 4;      // no restart markers: ONE interval, decoded by the self-synchronising kernel
     const long long mcus = (long long)P.mcux * P.mcuy;
     return WITW_JPEG_PLAN_FIXED + 4 * ((mcus + P.restart - 1) / P.restart);
 }
 
+long long witw_jpeg_entropy_plan_bytes(const uint8_t* data, size_t n) { return witw_jpeg_entropy_plan_bytes_ex(data, n, 0); }
+
 // plan: plan_cap bytes (witw_jpeg_entropy_plan_bytes); qt: ncomp x 64 uint16 (as witw_jpeg_decode_coef writes them).
 // Returns the plan's size in bytes, or -1 / -2 as witw_jpeg_info, -2 also for files with more than two Huffman tables of a kind in
 // use, -3 when the restart markers found do not number intervals - 1 in sequence.
-long long witw_jpeg_entropy_plan(const uint8_t* data, size_t n, uint8_t* plan, size_t plan_cap, uint16_t* qt) {
+long long witw_jpeg_entropy_plan_ex(const uint8_t* data, size_t n, uint8_t* plan, size_t plan_cap, uint16_t* qt, int flags) {
     Parsed& P = parsed();
-    const int rc = parse(data, n, P);
+    const int rc = parse(data, n, P, false, (flags & WITW_JPEG_ACCEPT_H1V2) != 0);
     if (rc) return rc;
     // no restart markers: the whole scan is ONE interval ([2] = every MCU of the image); the device finds its way into the middle of
     // it by self-synchronisation (csrc/jpeg.hip, jpeg_selfsync_kernel)
@@ -750,6 +758,10 @@ long long witw_jpeg_entropy_plan(const uint8_t* data, size_t n, uint8_t* plan, s
     if (found != n_int - 1) return -3;
     h[27] = (int32_t)(end - data);
     return need;
+}
+
+long long witw_jpeg_entropy_plan(const uint8_t* data, size_t n, uint8_t* plan, size_t plan_cap, uint16_t* qt) {
+    return witw_jpeg_entropy_plan_ex(data, n, plan, plan_cap, qt, 0);
 }
 
 }  // extern "C"

@@ -48,6 +48,7 @@ class Globals:
     # shared memory (witw_amd/ring.py) instead of torch's pickling + pinning thread.
     device_jpeg = True
     jpeg_progressive = None      # device_jpeg: progressive files too (True / False; None = jpeg.PROGRESSIVE, WITW_JPEG_PROGRESSIVE)
+    jpeg_440 = None              # device_jpeg: 4:4:0 files too (True / False; None = jpeg.SAMPLING_440, WITW_JPEG_440)
     pinned_ring = True
     # not in the reference: how test() ranks the queries against the gallery. 'direct' = the reference's sum on every pair,
     # 'dft' = the spectral pass with exact re-scoring (same ranks), 'auto' = 'dft' from cvig_fov.SPECTRAL_FROM pairs on;
@@ -1483,7 +1484,7 @@ class ImagePairDataset(torch.utils.data.Dataset):
     def _globals(cls):
         return Globals
 
-    def __init__(self, dataset, csv_path, base_path=None, transform=None, raw=False, jpeg_progressive=None):
+    def __init__(self, dataset, csv_path, base_path=None, transform=None, raw=False, jpeg_progressive=None, jpeg_440=None):
         import os
         import pandas as pd
         self.raw = raw      # not in the reference: True = hand over the decoder's uint8 HWC arrays (collate_packed / GpuPreprocess
@@ -1493,6 +1494,7 @@ class ImagePairDataset(torch.utils.data.Dataset):
         # DataLoader worker, forked or spawned; None = jpeg.PROGRESSIVE as the WORKER sees it: a forked worker inherits the parent's
         # module, a spawned one imports it afresh and reads WITW_JPEG_PROGRESSIVE from the environment it inherited
         self.jpeg_progressive = jpeg_progressive
+        self.jpeg_440 = jpeg_440      # raw='jpeg': 4:4:0 files too (jpeg.SAMPLING_440 / WITW_JPEG_440); travels exactly as jpeg_progressive does
         self.csv_path = csv_path
         self.base_path = base_path if base_path is not None else os.path.dirname(csv_path)
         self.transform = transform
@@ -1524,13 +1526,13 @@ class ImagePairDataset(torch.utils.data.Dataset):
         return a if a.dtype == np.uint8 else ImagePairDataset._read(path)
 
     @staticmethod
-    def _read_jpeg(path, progressive=None):
+    def _read_jpeg(path, progressive=None, h1v2=None):
         """raw='jpeg': a JPEG file is only ENTROPY-decoded here (witw_amd/jpeg.py: quantised DCT coefficient blocks); the GPU
         finishes it into the bytes Pillow would have produced. Other formats, and JPEG flavours the device path leaves alone,
         are decoded by Pillow as with raw=True."""
         from . import jpeg
         if str(path).lower().endswith(('.jpg', '.jpeg')):
-            c = jpeg.open_file(path, progressive)      # header only; collate_packed entropy-decodes straight into the batch block
+            c = jpeg.open_file(path, progressive, h1v2)      # header only; collate_packed entropy-decodes straight into the batch block
             if c is not None:
                 return c
         return ImagePairDataset._read_raw(path)
@@ -1538,7 +1540,7 @@ class ImagePairDataset(torch.utils.data.Dataset):
     def __getitem__(self, idx):
         if self.raw == 'jpeg':
             def read(path):
-                return self._read_jpeg(path, self.jpeg_progressive)
+                return self._read_jpeg(path, self.jpeg_progressive, getattr(self, 'jpeg_440', None))
         else:
             read = self._read_raw if self.raw else self._read
         data = {'surface': read(self.file_paths.iloc[idx]['surface']),
@@ -2005,7 +2007,7 @@ def train(dataset='cvusa', fov=360, val_quantity=1000, batch_size=64, num_worker
     # raw='jpeg': a worker only entropy-decodes JPEG files, the GPU finishes them (witw_amd/jpeg.py; the same bytes); True:
     # Pillow's bytes; either way converted / resized / normalised on the GPU
     trainval_set = ImagePairDataset(dataset=dataset, csv_path=csv_path, raw='jpeg' if getattr(Globals, 'device_jpeg', True) else True,
-                                    jpeg_progressive=getattr(Globals, 'jpeg_progressive', None))
+                                    jpeg_progressive=getattr(Globals, 'jpeg_progressive', None), jpeg_440=getattr(Globals, 'jpeg_440', None))
     split_gen = torch.Generator().manual_seed(seed) if world > 1 else None      # every rank must draw the same split
     train_set, val_set = torch.utils.data.random_split(trainval_set, [len(trainval_set) - val_quantity, val_quantity],
                                                        generator=split_gen)
@@ -2123,7 +2125,7 @@ def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, 
     # the reference crops test panoramas at a random orientation too (:495-499); Globals.test_random_orientation = False
     # makes the evaluation repeatable
     test_set = ImagePairDataset(dataset=dataset, csv_path=csv_path, raw='jpeg' if getattr(Globals, 'device_jpeg', True) else True,
-                                jpeg_progressive=getattr(Globals, 'jpeg_progressive', None))
+                                jpeg_progressive=getattr(Globals, 'jpeg_progressive', None), jpeg_440=getattr(Globals, 'jpeg_440', None))
     # under torch.distributed every rank embeds a contiguous shard of the test set and keeps its gallery rows
     shard_begin, shard_end = parallel.shard_range(len(test_set))
     shard = torch.utils.data.Subset(test_set, range(shard_begin, shard_end)) if world > 1 else test_set

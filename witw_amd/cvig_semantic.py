@@ -48,8 +48,8 @@ class ImagePairDataset(_fov.ImagePairDataset):
     def _globals(cls):
         return Globals
 
-    def __init__(self, dataset, csv_path, base_path=None, transform=None, raw=False, jpeg_progressive=None):
-        super().__init__(dataset, csv_path, base_path, transform, raw, jpeg_progressive)
+    def __init__(self, dataset, csv_path, base_path=None, transform=None, raw=False, jpeg_progressive=None, jpeg_440=None):
+        super().__init__(dataset, csv_path, base_path, transform, raw, jpeg_progressive, jpeg_440)
         self.semantic = Globals.dataset_paths[dataset]['semantic']
 
     @staticmethod

@@ -146,7 +146,8 @@ def bench(a, device, n_pairs=None, workers=None, keep_dir=None, decode=None, pre
     dev_entropy = decode == 'device' and bool(jpeg_mod.DEVICE_ENTROPY) and (restart_rows > 0 or restart_blocks > 0 or jpeg_mod.DEVICE_ENTROPY == 'all')
     t_make = time.perf_counter() - t0
 
-    ds = cvig_fov.ImagePairDataset('cvusa', csv, raw='jpeg' if decode == 'device' else True, jpeg_progressive=getattr(a, 'jpeg_progressive', None))
+    ds = cvig_fov.ImagePairDataset('cvusa', csv, raw='jpeg' if decode == 'device' else True, jpeg_progressive=getattr(a, 'jpeg_progressive', None),
+                                   jpeg_440=getattr(a, 'jpeg_440', None))
     split = cvig_fov.loader_split(B, workers)      # workers decode quarter batches (as test() does): first batch 4x sooner
     # batch blocks are built by the workers directly in page-locked shared memory (ring.PinnedRing): no pickling copy, no pinning
     # thread; --no-ring: torch's own path (shared-memory pickling + pin_memory thread)

@@ -6,7 +6,8 @@ dequantisation, integer inverse DCT, fancy chroma upsampling, YCbCr -> RGB) into
 produces, byte for byte. Files this decoder leaves alone (progressive, arithmetic-coded, CMYK, 12-bit, unusual sampling) are
 decoded by Pillow in the worker as before and travel as bytes in the same batch. Opt-in (PROGRESSIVE below): progressive
 files are entropy-decoded by the worker too -- all their scans, into the blocks a sequential file would hold -- and take the same
-route through the GPU.
+route through the GPU. Opt-in too (SAMPLING_440 below): 4:4:0 files (h1v2, e.g. a losslessly rotated 4:2:2 file) take every
+route a 4:2:2 file takes.
 
 Nothing here touches the GPU at import or in a worker: libwitw_jpeg.so is host-only C++."""
 import ctypes
@@ -39,6 +40,12 @@ DEVICE_ENTROPY = False if _mode in ('0', 'off', 'false') else 'restart' if _mode
 # precision stays Pillow's (libjpeg smooths it). WITW_JPEG_PROGRESSIVE = 1 | on | true; open_file / read_coef(progressive=...) override it.
 PROGRESSIVE = os.environ.get('WITW_JPEG_PROGRESSIVE', '').lower() in ('1', 'on', 'true')
 ACCEPT_PROGRESSIVE = 1     # flag bit 0 of witw_jpeg_info_ex / witw_jpeg_decode_coef_ex
+# 4:4:0 files (h1v2: luma 1x2, chroma 1x1 -- a portrait photo turned losslessly from a 4:2:2 file): off = left to Pillow in the worker; on =
+# taken like a 4:2:2 file, through whichever entropy route DEVICE_ENTROPY picks (the MCU is Y, Y below it, Cb, Cr; the plan tells the
+# device decoders) and upsampling mode 5 of the back end (decode_tables). A progressive 4:4:0 file is taken only when PROGRESSIVE is on
+# as well. WITW_JPEG_440 = 1 | on | true; open_file / read_coef(h1v2=...) override it.
+SAMPLING_440 = os.environ.get('WITW_JPEG_440', '').lower() in ('1', 'on', 'true')
+ACCEPT_H1V2 = 2            # flag bit 1 of the _ex entries of libwitw_jpeg.so
 CHECK_ERRORS = True    # decode_packed(host_buf=...) re-decodes files the device flagged as damaged with Pillow (as the host path does)
 REPAIRED = [0]         # how many files that happened to
 SELFSYNC_MIN_BLOCKS = 96   # a marker-less file of at most this many blocks is decoded by ONE thread of the interval kernel (a 1024-thread
@@ -64,6 +71,10 @@ def host_lib():
         lib.witw_jpeg_entropy_plan_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
         lib.witw_jpeg_entropy_plan.restype = ctypes.c_longlong
         lib.witw_jpeg_entropy_plan.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        lib.witw_jpeg_entropy_plan_bytes_ex.restype = ctypes.c_longlong
+        lib.witw_jpeg_entropy_plan_bytes_ex.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        lib.witw_jpeg_entropy_plan_ex.restype = ctypes.c_longlong
+        lib.witw_jpeg_entropy_plan_ex.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
         _HOST = lib
     return _HOST
 
@@ -84,18 +95,19 @@ class JpegCoef(object):
 class JpegFile(JpegCoef):
     """A JPEG file whose header has been parsed (info) but whose entropy-coded data is still to be decoded: pack() decodes it
     straight into its place in the batch block (no array of its own, no copy). `coef` / `qt` decode on demand. progressive: a
-    progressive file (open_file(progressive=True)): all its scans are decoded on the host, never on the device."""
-    __slots__ = ('data', 'progressive')
+    progressive file (open_file(progressive=True)): all its scans are decoded on the host, never on the device. flags: what the file
+    was opened under (ACCEPT_PROGRESSIVE | ACCEPT_H1V2): the _ex entries take it again when the file is decoded or planned."""
+    __slots__ = ('data', 'progressive', 'flags')
 
-    def __init__(self, info, data, progressive=False):
-        self.info, self.data, self.progressive = info, data, progressive
+    def __init__(self, info, data, progressive=False, flags=0):
+        self.info, self.data, self.progressive, self.flags = info, data, progressive, flags
 
     def decode_into(self, coef, qt):
         """coef int16 [blocks, 64], qt uint16 [components, 64]: views of the destination. -> False if the entropy data is bad (or,
         progressive, its scans are illegal or stop short of full precision)."""
-        if self.progressive:
+        if self.flags:
             return host_lib().witw_jpeg_decode_coef_ex(self.data.ctypes.data, self.data.size, coef.ctypes.data, qt.ctypes.data,
-                                                       ACCEPT_PROGRESSIVE) == 0
+                                                       self.flags) == 0
         return host_lib().witw_jpeg_decode_coef(self.data.ctypes.data, self.data.size, coef.ctypes.data, qt.ctypes.data) == 0
 
     def entropy_plan(self):
@@ -106,12 +118,12 @@ class JpegFile(JpegCoef):
         if self.progressive:
             return None
         lib = host_lib()
-        n = int(lib.witw_jpeg_entropy_plan_bytes(self.data.ctypes.data, self.data.size))
+        n = int(lib.witw_jpeg_entropy_plan_bytes_ex(self.data.ctypes.data, self.data.size, self.flags))
         if n <= 0:
             return None
         plan = np.empty((n,), dtype=np.uint8)
         qt = np.empty((int(self.info[2]), 64), dtype=np.uint16)
-        if lib.witw_jpeg_entropy_plan(self.data.ctypes.data, self.data.size, plan.ctypes.data, n, qt.ctypes.data) != n:
+        if lib.witw_jpeg_entropy_plan_ex(self.data.ctypes.data, self.data.size, plan.ctypes.data, n, qt.ctypes.data, self.flags) != n:
             return None
         return plan, qt
 
@@ -134,23 +146,26 @@ class JpegFile(JpegCoef):
     qt = property(lambda self: self._decoded()[1])
 
 
-def open_file(src, progressive=None):
+def open_file(src, progressive=None, h1v2=None):
     """src: a path or the bytes of a JPEG file -> JpegFile (header parsed, entropy decoding deferred to pack()), or None when the
-    file is left to the host decoder. progressive: take progressive files too (None: the module flag PROGRESSIVE)."""
+    file is left to the host decoder. progressive: take progressive files too (None: the module flag PROGRESSIVE); h1v2: take 4:4:0
+    files too (None: the module flag SAMPLING_440)."""
     data = np.fromfile(src, dtype=np.uint8) if isinstance(src, (str, os.PathLike)) else np.frombuffer(src, dtype=np.uint8)
     info = np.zeros(22, dtype=np.int32)
-    if PROGRESSIVE if progressive is None else progressive:
-        rc = host_lib().witw_jpeg_info_ex(data.ctypes.data, data.size, info.ctypes.data, ACCEPT_PROGRESSIVE)
-        return JpegFile(info, data, progressive=rc == 1) if rc in (0, 1) else None
+    flags = (ACCEPT_PROGRESSIVE if (PROGRESSIVE if progressive is None else progressive) else 0) | \
+        (ACCEPT_H1V2 if (SAMPLING_440 if h1v2 is None else h1v2) else 0)
+    if flags:
+        rc = host_lib().witw_jpeg_info_ex(data.ctypes.data, data.size, info.ctypes.data, flags)
+        return JpegFile(info, data, progressive=rc == 1, flags=flags) if rc in (0, 1) else None
     if host_lib().witw_jpeg_info(data.ctypes.data, data.size, info.ctypes.data) != 0:
         return None
     return JpegFile(info, data)
 
 
-def read_coef(src, progressive=None):
-    """src: a path or the bytes of a JPEG file -> JpegCoef, or None when the file is left to the host decoder. progressive: as
+def read_coef(src, progressive=None, h1v2=None):
+    """src: a path or the bytes of a JPEG file -> JpegCoef, or None when the file is left to the host decoder. progressive, h1v2: as
     open_file."""
-    f = open_file(src, progressive)
+    f = open_file(src, progressive, h1v2)
     if f is None:
         return None
     coef = np.empty((int(f.info[5]), 64), dtype=np.int16)
@@ -251,7 +266,7 @@ def decode_tables(d):
     """The launch tables of the device back end from the host descriptor rows of the JPEG entries of a batch (d: int64 [n, DESC_COLS],
     none of them raw) -> (planes int64 [P, 6] = {first coefficient block, quantisation table index, byte offset of the plane in the
     component buffer, blocks wide, blocks high, first block of the plane in the launch}, images int64 [n, 12] = {H, W, components,
-    upsampling mode, luma plane offset, luma pitch, Cb offset, Cr offset, chroma pitch, chroma rows, chroma columns, output byte
+    upsampling mode (0 none, 1 h2v1, 2 h2v2, 3 / 4 those two replicated, 5 h1v2 = 4:4:0), luma plane offset, luma pitch, Cb offset, Cr offset, chroma pitch, chroma rows, chroma columns, output byte
     offset}, blocks in all, component bytes, output bytes, byte offset of the first quantisation table). Whole-array numpy: a
     per-image Python loop here cost 8 ms per 128 pairs, as much as the bf16 encoders take for them."""
     n = d.shape[0]
@@ -269,12 +284,18 @@ def decode_tables(d):
     plane_first[valid] = blk_off
     qti = ((d[:, 1] - qt_base) // 128)[:, None] + np.arange(3)[None, :]
     planes = np.stack([cb[valid], qti[valid], blk_off * 64, bw[valid], bh[valid], blk_off], axis=1).astype(np.int64)
-    mode = np.where((hmax == 1) & (vmax == 1), 0, np.where((hmax == 2) & (vmax == 1), 1, np.where((hmax == 2) & (vmax == 2), 2, -1)))
+    # (1, 2) = 4:4:0, taken only as the host parser describes such a file -- the luma component itself sampled 1 x 2 (info[6:8]); a row
+    # that claims the sampling without it was not written by witw_jpeg_info_ex
+    is_440 = (hmax == 1) & (vmax == 2) & (d[:, 8] == 1) & (d[:, 9] == 2)
+    mode = np.where((hmax == 1) & (vmax == 1), 0, np.where((hmax == 2) & (vmax == 1), 1, np.where((hmax == 2) & (vmax == 2), 2,
+                                                                                                  np.where(is_440, 5, -1))))
     if (mode < 0).any():
         i = int(np.nonzero(mode < 0)[0][0])
         raise ValueError('jpeg: sampling %dx%d reached the device path' % (int(hmax[i]), int(vmax[i])))
     cw, ch = -(-W // hmax), -(-H // vmax)
-    mode = mode + 2 * ((mode > 0) & (cw <= 2))      # libjpeg replicates chroma planes of at most two columns instead of filtering them
+    # libjpeg replicates chroma planes of at most two columns instead of filtering them -- where it would filter HORIZONTALLY: the
+    # vertical-only h1v2 filter runs on planes of any size (jdsample.c jinit_upsampler)
+    mode = mode + 2 * ((mode > 0) & (mode < 3) & (cw <= 2))
     images = np.zeros((n, 12), dtype=np.int64)
     images[:, 0], images[:, 1], images[:, 2], images[:, 3] = H, W, ncomp, mode
     images[:, 4], images[:, 5] = plane_first[:, 0] * 64, bw[:, 0] * 8
