@@ -1,5 +1,5 @@
 """Candidate lists longer than 32 places, CPU side: the slice loop of ops.topk_smallest (ops._topk_slices) and the merge of the
-shards' lists (cvig_fov._merge_topk) on a torch rendering of the kernels' rule -- a run returns the n smallest rows in the order
+shards' lists (retrieval._merge_topk) on a torch rendering of the kernels' rule -- a run returns the n smallest rows in the order
 (distance, gallery index), NaN counted as +inf, and a resumed run only the rows strictly behind its bound; a bound with index -1
 (the missing candidate) has nothing behind it. The lists must equal the stable sort of the whole column."""
 import pytest

@@ -10,7 +10,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _lib, baseline_bf16, baseline_parallel, ops
+from . import _lib, baseline_bf16, baseline_parallel, ops, parallel, retrieval, slab_loss
 from . import cvig_fov as _fov
 from .cvig_fov import Adam, recall_table  # noqa: F401  (same table, model/cvig_baseline.py:461-466)
 
@@ -496,8 +496,8 @@ def _slab_kernels():
 
 
 class _ShardedExhaustiveLossFn(torch.autograd.Function):
-    """exhaustive_minibatch_triplet_loss over the GLOBAL batch with the distance matrix sharded by COLUMNS over the ranks, shaped
-    like cvig_fov._ShardedMatchLossFn: rank r evaluates all B overhead embeddings against its own b surface embeddings (a [B,b]
+    """exhaustive_minibatch_triplet_loss over the GLOBAL batch with the distance matrix sharded by COLUMNS over the ranks, on the
+    column-slab protocol of witw_amd.slab_loss: rank r evaluates all B overhead embeddings against its own b surface embeddings (a [B,b]
     slab of squared distances; the loss is symmetric in its two arguments, so which side is gathered is free). Exchanges:
     forward = all-gather of the overhead embeddings and of the diagonal (B floats), all-reduce of the loss partial; backward =
     all-reduce of the row sums of l' (B floats), reduce-scatter of the overhead-embedding gradients (every rank holds the part
@@ -506,43 +506,17 @@ class _ShardedExhaustiveLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, surface_local, overhead_local, soft_margin, alpha, margin, k):
-        from . import parallel
-        world = parallel.world()
-        y = surface_local.contiguous()
-        b = y.shape[0]
-        if overhead_local.shape != y.shape or y.dim() != 2:
-            raise _lib.WitwError('sharded_exhaustive_loss: need [b, n] embeddings of one shape, got %s and %s'
-                                 % (tuple(surface_local.shape), tuple(overhead_local.shape)))
-        if world > 1:
-            with parallel.phase('batch_share_all_gather'):       # decided on gathered data: every rank raises, none is left waiting
-                shares = parallel._all_gather_cat(torch.tensor([b], dtype=torch.int64, device=y.device)).tolist()
-            if len(set(shares)) != 1:
-                raise _lib.WitwError('sharded_exhaustive_loss: unequal batch shares across the ranks %s -- every rank must bring the '
-                                     'same number of pairs (train with drop_last)' % (shares,))
-            with parallel.phase('overhead_all_gather'):
-                x = parallel._all_gather_cat(overhead_local.contiguous())
-        else:
-            x = overhead_local.contiguous()
-        col0 = parallel.rank() * b
-        B = x.shape[0]
+        x, y, b, col0, B, world = slab_loss.open_slab(overhead_local, surface_local, who='sharded_exhaustive_loss')
         with parallel.phase('slab_distances'):
             T = k.pairwise_sqdist(x, y)
-        own = T[col0:col0 + b].diagonal().contiguous()
-        if world > 1:
-            with parallel.phase('diagonal_all_gather'):
-                diag = parallel._all_gather_cat(own)
-        else:
-            diag = own
-        with parallel.phase('loss_partial_all_reduce'):
-            part = k.exhaustive_loss_slab_fwd(T, diag, col0, soft_margin, alpha, margin)
-            parallel.all_reduce_sum_(part)
+        diag = slab_loss.gather_diagonal(T, col0, b, world > 1)
+        part = slab_loss.sum_partial(lambda: k.exhaustive_loss_slab_fwd(T, diag, col0, soft_margin, alpha, margin), True)
         ctx.save_for_backward(x, y, T, diag)
         ctx.cfg = (col0, b, soft_margin, alpha, margin, k)
         return (part / (2. * B * (B - 1))).reshape(())
 
     @staticmethod
     def backward(ctx, g_loss):
-        from . import parallel
         x, y, T, diag = ctx.saved_tensors
         col0, b, soft_margin, alpha, margin, k = ctx.cfg
         with parallel.phase('row_sums_all_reduce'):
@@ -551,10 +525,7 @@ class _ShardedExhaustiveLossFn(torch.autograd.Function):
         with parallel.phase('slab_backward'):
             G = k.exhaustive_loss_slab_bwd(T, diag, rowsig, colsig, g_loss.contiguous(), col0, soft_margin, alpha, margin)
             dx, dy = k.sqdist_rect_bwd(x, y, G, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
-        if dx is not None:
-            with parallel.phase('overhead_grad_reduce_scatter'):
-                dx = parallel.reduce_scatter_rows(dx, b)
-        return dy, dx, None, None, None, None
+        return dy, slab_loss.scatter_overhead_grad(dx, b, True), None, None, None, None
 
 
 def sharded_exhaustive_loss(surface_local, overhead_local, soft_margin=False, alpha=10., margin=1., _kernels=None):
@@ -578,7 +549,7 @@ def _hard_kernels():
 
 
 class _ShardedBatchHardLossFn(torch.autograd.Function):
-    """The batch-hard form of the loss over the GLOBAL batch on the column slabs of _ShardedExhaustiveLossFn: every anchor against
+    """The batch-hard form of the loss over the GLOBAL batch on the column-slab protocol of witw_amd.slab_loss: every anchor against
     its hardest negative only (minimum of its row / column of T with the diagonal masked; the mined indices are constants for the
     gradient). Exchanges: forward = all-gather of the overhead embeddings, of the diagonal (B floats) and of the per-rank row minima
     ([w,B] values + global column indices, merged in rank order: the lowest index wins a tie), all-reduce of the loss partial (each
@@ -590,43 +561,14 @@ class _ShardedBatchHardLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, surface_local, overhead_local, soft_margin, alpha, margin, k, sharded):
-        from . import parallel
-        world, rank = (parallel.world(), parallel.rank()) if sharded else (1, 0)      # not sharded: one slab, whatever group there is
-        y = surface_local.contiguous()
-        b = y.shape[0]
-        if overhead_local.shape != y.shape or y.dim() != 2:
-            raise _lib.WitwError('sharded_batch_hard_loss: need [b, n] embeddings of one shape, got %s and %s'
-                                 % (tuple(surface_local.shape), tuple(overhead_local.shape)))
-        if world > 1:
-            with parallel.phase('batch_share_all_gather'):       # decided on gathered data: every rank raises, none is left waiting
-                shares = parallel._all_gather_cat(torch.tensor([b], dtype=torch.int64, device=y.device)).tolist()
-            if len(set(shares)) != 1:
-                raise _lib.WitwError('sharded_batch_hard_loss: unequal batch shares across the ranks %s -- every rank must bring the '
-                                     'same number of pairs (train with drop_last)' % (shares,))
-            with parallel.phase('overhead_all_gather'):
-                x = parallel._all_gather_cat(overhead_local.contiguous())
-        else:
-            x = overhead_local.contiguous()
-        col0 = rank * b
-        B = x.shape[0]
+        x, y, b, col0, B, world = slab_loss.open_slab(overhead_local, surface_local, who='sharded_batch_hard_loss', sharded=sharded)
         if B < 2:
             raise _lib.WitwError('sharded_batch_hard_loss: batch %d < 2 (every anchor needs a negative)' % B)
         with parallel.phase('slab_distances'):
             T = k.pairwise_sqdist(x, y)
-        own = T[col0:col0 + b].diagonal().contiguous()
-        if world > 1:
-            with parallel.phase('diagonal_all_gather'):
-                diag = parallel._all_gather_cat(own)
-        else:
-            diag = own
-        with parallel.phase('row_minima_all_gather'):
-            rv, ri, cv, ci = k.batch_hard_slab_mine(T, col0)
-            if world > 1:
-                rv, ri = k.batch_hard_merge_rows(parallel._all_gather_cat(rv[None]), parallel._all_gather_cat(ri[None]))
-        with parallel.phase('loss_partial_all_reduce'):
-            part = k.hard_slab_loss(T, rv, cv, col0, soft_margin, alpha, margin)
-            if world > 1:
-                parallel.all_reduce_sum_(part)
+        diag = slab_loss.gather_diagonal(T, col0, b, world > 1)
+        rv, ri, cv, ci = slab_loss.mine_global(k, T, col0, world > 1)
+        part = slab_loss.sum_partial(lambda: k.hard_slab_loss(T, rv, cv, col0, soft_margin, alpha, margin), world > 1)
         ctx.save_for_backward(x, y, diag, rv, ri, cv, ci)
         ctx.cfg = (col0, b, world, soft_margin, alpha, margin, k)
         ctx.mark_non_differentiable(rv, ri, cv, ci)
@@ -635,7 +577,6 @@ class _ShardedBatchHardLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, *_g):
-        from . import parallel
         if g_loss is None:
             return None, None, None, None, None, None, None
         x, y, diag, rv, ri, cv, ci = ctx.saved_tensors
@@ -643,10 +584,7 @@ class _ShardedBatchHardLossFn(torch.autograd.Function):
         with parallel.phase('slab_backward'):
             pg, pc, pw = k.hard_pairs(diag, rv, ri, cv, ci, g_loss.contiguous(), col0, soft_margin, alpha, margin)
             dx, dy = k.sqdist_pairs_bwd(x, y, pg, pc, pw, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
-        if dx is not None and world > 1:
-            with parallel.phase('overhead_grad_reduce_scatter'):
-                dx = parallel.reduce_scatter_rows(dx, b)
-        return dy, dx, None, None, None, None, None
+        return dy, slab_loss.scatter_overhead_grad(dx, b, world > 1), None, None, None, None, None
 
 
 def sharded_batch_hard_loss(surface_local, overhead_local, soft_margin=False, alpha=10., margin=1., mined=False, _kernels=None):
@@ -679,13 +617,7 @@ DIRECT_ROWS = 65535      # gallery rows per ops.pairwise_sqdist call (its row in
 GEMM_MARGIN = 32         # candidates kept beyond place k by the GEMM pass's top-k: one more slice of ops.topk_smallest
 GEMM_FROM = _fov.SPECTRAL_FROM      # 'auto' is 'gemm' from this many queries on (measured against 'direct')
 
-_RETRIEVE_TLS = __import__('threading').local()
-
-
-def last_retrieve_stats():
-    """Re-scoring statistics of the calling thread's last retrieve(method='gemm'): pairs, rescored_true / _rank / _topk,
-    fallback_queries, eps (retrieve.last_stats is process-wide)."""
-    return dict(getattr(_RETRIEVE_TLS, 'stats', None) or {})
+last_retrieve_stats = retrieval.last_retrieve_stats
 
 
 def band_eps(n, gn_max, qn_max):
@@ -713,19 +645,8 @@ def _default_kernels():
                            topk_smallest=ops.topk_smallest, row_sqnorm=br.row_sqnorm, sqdist_gemm=br.sqdist_gemm, sqdist_pairs=br.sqdist_pairs)
 
 
-def _direct_kernels(kn):
-    """the op set cvig_fov._direct_pass runs on: its `match` is ops.pairwise_sqdist(take_sqrt=True) over blocks of at most
-    DIRECT_ROWS gallery rows"""
-    from types import SimpleNamespace
-
-    def match_fwd(gallery, queries, **_kw):
-        blocks = [kn.pairwise_sqdist(gallery[r0:r0 + DIRECT_ROWS], queries, take_sqrt=True) for r0 in range(0, gallery.shape[0], DIRECT_ROWS)]
-        return None, (blocks[0] if len(blocks) == 1 else torch.cat(blocks))
-    return SimpleNamespace(match_fwd=match_fwd, rank_count_thresh=kn.rank_count_thresh, topk_smallest=kn.topk_smallest)
-
-
 def _direct(kn, gallery, surface_all, shard_begin, query_chunk, k, want_ranks):
-    return _fov._direct_pass(_direct_kernels(kn), gallery, surface_all, _fov._NO_PRIOR, shard_begin, query_chunk, k, want_ranks)
+    return retrieval.sqdist_direct_pass(kn, DIRECT_ROWS, gallery, surface_all, _fov._NO_PRIOR, shard_begin, query_chunk, k, want_ranks)
 
 
 def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='gemm', _kernels=None):
@@ -736,14 +657,14 @@ def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=
 
 def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='gemm', _kernels=None, _want_ranks=True,
              _want_lists=True):
-    """Ranks and top-k lists of cvig_baseline embeddings from ONE distance pass per query chunk, name for name what
-    cvig_fov.retrieve is for the orientation search: this rank holds overhead_shard = gallery rows [shard_begin, shard_begin + n)
+    """Ranks and top-k lists of cvig_baseline embeddings from ONE distance pass per query chunk, on the exchanges and re-scorings
+    of witw_amd.retrieval that cvig_fov.retrieve runs its orientation search on: this rank holds overhead_shard = gallery rows [shard_begin, shard_begin + n)
     (any number per rank, including none), surface_all [N, E] is replicated, query q's true row is gallery row q.
     -> (ranks int64 [N] on the host = #{rows : d <= d_true}, distances f32 [N,k], gallery indices int64 [N,k] on the device,
     ordered by (distance, index)), identical on every rank. Distances are Euclidean, as ranks() returns them. 1 <= k <=
     ops.TOPK_MAX; places beyond the rows present are (+inf, -1).
     method='direct': ops.pairwise_sqdist (the difference form) over gallery blocks of at most DIRECT_ROWS rows feeding
-    ops.rank_count_thresh / ops.topk_smallest; the shards' lists are merged by cvig_fov._merge_topk.
+    ops.rank_count_thresh / ops.topk_smallest (retrieval.sqdist_direct_pass); the shards' lists are merged by retrieval._merge_topk.
     method='gemm': |g|^2 + |q|^2 - 2 g.q on the fp32 MFMA (witw_sqdist_gemm), known to band_eps only; every decision inside that
     band is re-made on witw_sqdist_pairs, whose values are the direct kernel's bit for bit: rows within eps of d_true^2 are
     re-scored and compared as rooted values; ALL k + GEMM_MARGIN candidates per shard and query are re-scored and ordered
@@ -752,8 +673,7 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     GEMM_MARGIN places come from the direct pass, the ranks still from the GEMM pass.
     method='auto': 'gemm' from GEMM_FROM queries on. `_kernels` swaps the op set (CPU tests of the host pass)."""
     kn = _kernels or _default_kernels()
-    if not 1 <= int(k) <= ops.TOPK_MAX:
-        raise _lib.WitwError('retrieve: k=%d outside [1,%d] (the longest candidate list, ops.TOPK_MAX)' % (int(k), ops.TOPK_MAX))
+    retrieval.check_k(k)
     if method not in ('auto', 'direct', 'gemm'):
         raise _lib.WitwError("retrieve: method must be 'auto', 'direct' or 'gemm', got %r" % (method,))
     if overhead_shard.dim() != 2 or surface_all.dim() != 2 or overhead_shard.shape[1] != surface_all.shape[1]:
@@ -774,7 +694,7 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     if _want_ranks or _want_lists:
         counts, dv, di = _direct(kn, gallery, surface_all, shard_begin, query_chunk, k if _want_lists else None, _want_ranks)
         if _want_ranks:
-            ranks_out = counts.cpu().numpy().astype('int64')
+            ranks_out = retrieval.host_ranks(counts)
         if _want_lists:
             v, i = dv, di
     return ranks_out, v, i
@@ -783,9 +703,7 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
 def _retrieve_gemm(kn, gallery, surface_all, k, shard_begin, query_chunk, want_ranks):
     """retrieve() on the GEMM pass (see there). k None: no lists. -> (ranks or None, values, indices), or None when some norm is
     not finite (decided on all-reduced data: the same on every rank)."""
-    import math
     import torch.distributed as dist_
-    from . import parallel
     dev = surface_all.device
     n_q, n_g, n = surface_all.shape[0], gallery.shape[0], surface_all.shape[1]
     if not want_ranks and k is None:
@@ -812,71 +730,46 @@ def _retrieve_gemm(kn, gallery, surface_all, k, shard_begin, query_chunk, want_r
         su = surface_all[q0:q1]
         D = kn.sqdist_gemm(gallery, su, gn, qn_all[q0:q1]) if n_g else None          # [n_g, nq], squared
         if want_ranks:
-            lo, hi = max(q0, shard_begin), min(q1, shard_begin + n_g)         # the queries whose true row lives in this shard
-            d_true = torch.zeros((nq,), dtype=torch.float32, device=dev)
-            if hi > lo:                                                       # the owner's EXACT distance of every true pair
-                pg = torch.arange(lo - shard_begin, hi - shard_begin, dtype=torch.int32, device=dev)
-                pq = torch.arange(lo - q0, hi - q0, dtype=torch.int32, device=dev)
-                d_true[lo - q0:hi - q0] = kn.sqdist_pairs(gallery, su, pg, pq, take_sqrt=True)
-                stats['rescored_true'] += hi - lo
-            parallel.all_reduce_sum_(d_true)
-            if n_g:
-                c, pg, pq = kn.rank_count_band(D, (d_true * d_true).contiguous(), eps)
-                if pg.numel():        # compared as ranks() compares: on the rooted exact values (sqrtf can merge neighbouring squares)
-                    d_x = kn.sqdist_pairs(gallery, su, pg, pq, take_sqrt=True)
-                    c.index_add_(0, pq.long(), (d_x <= d_true[pq.long()]).to(torch.int32))
-                    stats['rescored_rank'] += int(pg.numel())
-                counts[q0:q1] = c
+            exact = _exact_pairs(kn, gallery, su)
+            d_true = retrieval.true_distances(exact, q0, q1, shard_begin, n_g, dev, stats)
+            if n_g:   # squared thresholds; compared as ranks() compares: on the rooted exact values (sqrtf can merge neighbouring squares)
+                counts[q0:q1] = retrieval.band_rescore(kn, D, (d_true * d_true).contiguous(), eps, exact, d_true, stats)
         if kc is not None:
-            cv, ci = kn.topk_smallest(D, kc, shard_begin) if n_g else _fov._empty_topk(nq, kc, dev)
+            cv, ci = kn.topk_smallest(D, kc, shard_begin) if n_g else retrieval._empty_topk(nq, kc, dev)
             vals.append(cv)
             idxs.append(ci)
     ranks_out = v = i = None
     if want_ranks:
         parallel.all_reduce_sum_(counts)
-        ranks_out = counts.cpu().numpy().astype('int64')
+        ranks_out = retrieval.host_ranks(counts)
     if kc is not None:
         if n_q:
-            v, i = _settle_lists(kn, gallery, surface_all, k, kc, shard_begin, query_chunk, eps, torch.cat(vals), torch.cat(idxs), stats)
+            v, i = _settle_lists(kn, gallery, surface_all, k, shard_begin, query_chunk, eps, torch.cat(vals), torch.cat(idxs), stats)
         else:
-            v, i = _fov._empty_topk(0, k, dev)
-    retrieve.last_stats = stats
-    _RETRIEVE_TLS.stats = stats
+            v, i = retrieval._empty_topk(0, k, dev)
+    retrieval.publish_stats(retrieve, stats)
     return ranks_out, v, i
 
 
-def _settle_lists(kn, gallery, surface_all, k, kc, shard_begin, query_chunk, eps, v, i, stats):
+def _exact_pairs(kn, gallery, su):
+    """witw_amd.retrieval's `exact_pairs` of the GEMM pass: the rooted distances of the pairs (pg, pq) of (gallery, su) through
+    kn.sqdist_pairs -- the direct kernel's bits"""
+    return lambda pg, pq: kn.sqdist_pairs(gallery, su, pg, pq, take_sqrt=True)
+
+
+def _settle_lists(kn, gallery, surface_all, k, shard_begin, query_chunk, eps, v, i, stats):
     """The shards' candidate lists (v, i: [N, kc] by GEMM-form squared distance) -> the first k places as the direct pass lists
     them. Every gathered candidate is re-scored exactly (N kc pairs per shard: nothing next to the pass) and ordered by (exact
     distance, index). No row outside the lists has a GEMM-form value below `outsider`, the smallest last place of a full list, so
     its exact squared distance is >= outsider - eps and its rooted one >= sqrt(outsider - eps): a query whose exact k-th distance is
     strictly below that is settled, any other takes the direct pass."""
-    from . import parallel
-    dev = surface_all.device
-    n_q, n_g = surface_all.shape[0], gallery.shape[0]
-    w = parallel.world()
-    outsider = v[:, kc - 1].clone()                      # +inf where the shard has fewer than kc rows: nothing outside its list
-    if w > 1:
-        i = parallel._all_gather_cat(i.unsqueeze(0)).permute(1, 0, 2).reshape(n_q, w * kc)
-        outsider = parallel._all_gather_cat(outsider.unsqueeze(0)).min(dim=0).values
-    mine = (i >= shard_begin) & (i < shard_begin + n_g)
-    exact = torch.zeros(i.shape, dtype=torch.float32, device=dev)
-    if n_g and bool(mine.any()):
-        pg = (i - shard_begin)[mine].to(torch.int32).contiguous()
-        pq = torch.arange(n_q, device=dev)[:, None].expand_as(i)[mine].to(torch.int32).contiguous()
-        exact[mine] = kn.sqdist_pairs(gallery, surface_all, pg, pq, take_sqrt=True)
-        stats['rescored_topk'] += int(pg.numel())
-    parallel.all_reduce_sum_(exact)
-    exact = torch.where(i < 0, torch.full_like(exact, float('inf')), exact)
-    ev, ei = _fov._sort_by_value_then_index(exact, i)
+    _v, i, outsider = retrieval.gather_candidates(v, i, want_values=False)
+    ev, ei = retrieval.rescore_candidates(_exact_pairs(kn, gallery, surface_all), i, None, shard_begin, gallery.shape[0], stats)
     beyond = torch.sqrt((outsider - eps).clamp(min=0))
     safe = (ev[:, min(k, ev.shape[1]) - 1] < beyond) | torch.isinf(outsider)
     ev, ei = ev[:, :k].contiguous(), ei[:, :k].contiguous()
-    fallback = torch.nonzero(~safe).squeeze(1)           # identical on every rank: computed from gathered data
-    if fallback.numel():     # more near-ties than candidates kept: those queries take the direct pass
-        stats['fallback_queries'] = int(fallback.numel())
-        _counts, fv, fi = _direct(kn, gallery, surface_all[fallback].contiguous(), shard_begin, query_chunk, k, False)
-        ev[fallback], ei[fallback] = fv, fi
+    retrieval.fall_back(lambda q: _direct(kn, gallery, surface_all[q].contiguous(), shard_begin, query_chunk, k, False)[1:],
+                        torch.nonzero(~safe).squeeze(1), ev, ei, k, stats)
     return ev, ei
 
 
@@ -885,7 +778,6 @@ def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, meth
     rank's rows (world > 1: the queries are gathered, the gallery rows stay sharded from shard_begin on). method: 'direct',
     'gemm' (the same ranks, see retrieve) or 'auto' = 'gemm' from GEMM_FROM queries on. Unlike ranks() neither is bounded by
     65,535 gallery rows."""
-    from . import parallel
     if method not in ('auto', 'direct', 'gemm'):         # refused before the gather
         raise _lib.WitwError("evaluation_ranks: method must be 'auto', 'direct' or 'gemm', got %r" % (method,))
     surface_all = parallel.all_gather_ragged(surface_embed) if world > 1 else surface_embed

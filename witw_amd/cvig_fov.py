@@ -11,7 +11,8 @@ from types import SimpleNamespace
 
 import torch
 
-from . import _lib, build as _build, ops, synth
+from . import _lib, build as _build, ops, parallel, retrieval, slab_loss, synth
+from .retrieval import _direct_pass, _empty_topk, _merge_topk, _sort_by_value_then_index, last_retrieve_stats      # noqa: F401
 
 
 class Globals:
@@ -854,7 +855,6 @@ def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, meth
     known_shift: int64, one shift per query of the WHOLE evaluation set (orientation_shift; excludes shift_mask): the ranks of
     shift_mask = 1 << known_shift at 1/64 of the products. method 'fixed' (requires it) is retrieve()'s chunked pass on the fixed
     kernel; 'direct' / 'auto' match through it too; the spectral methods refuse it."""
-    from . import parallel
     prior = _Prior.of(shift_mask, known_shift)       # its kind; the entries below check it against the gathered queries
     _resolve_method('evaluation_ranks', method, prior, 0)      # every refusal comes before the gather, the size behind it
     surface_all = parallel.all_gather_ragged(surface_embed) if world > 1 else surface_embed
@@ -865,52 +865,6 @@ def evaluation_ranks(overhead_embed, surface_embed, shard_begin=0, world=1, meth
     if world > 1:
         return sharded_ranks(overhead_embed, surface_all, shard_begin, **prior.kw())
     return ranks(overhead_embed, surface_embed, **prior.kw())
-
-
-def _empty_topk(nq, k, device):
-    """the candidate lists of a rank without gallery rows (more ranks than rows): k places at +inf, index -1"""
-    return (torch.full((nq, k), float('inf'), dtype=torch.float32, device=device),
-            torch.full((nq, k), -1, dtype=torch.int64, device=device))
-
-
-def _direct_pass(kn, gallery, surface_all, prior, shard_begin, query_chunk, k, want_ranks):
-    """The chunked pass of sharded_ranks / retrieve(method='direct' / 'fixed') over this rank's gallery rows [shard_begin,
-    shard_begin + n): one match per query chunk under the chunk's rows of the prior; want_ranks: the owner of each true row
-    publishes its distance (all-reduce of a vector that is zero elsewhere), every rank counts d <= d_true over its shard and the
-    counts are summed behind the last chunk; k (None: no lists): the k nearest rows per query, merged over the ranks. A rank
-    without gallery rows still takes part in every exchange. -> (counts int32 [N] on the device, values [N,k], indices [N,k])."""
-    from . import parallel
-    dev = surface_all.device
-    n_q, n_g = surface_all.shape[0], gallery.shape[0]
-    counts = torch.zeros((n_q,), dtype=torch.int32, device=dev)
-    vals, idxs = [], []
-    for q0 in range(0, n_q, query_chunk):
-        q1 = min(n_q, q0 + query_chunk)
-        if n_g:
-            dist = prior.rows(q0, q1).match_fwd(kn, gallery, surface_all[q0:q1].contiguous(), want_orientation=False)[1]   # [n_g, q]
-        if want_ranks:
-            if n_g:
-                qi = torch.arange(q0, q1, device=dist.device)
-                own = (qi >= shard_begin) & (qi < shard_begin + n_g)
-                row = (qi - shard_begin).clamp(0, n_g - 1)
-                d_true = torch.where(own, dist[row, qi - q0], torch.zeros_like(dist[0]))
-            else:
-                d_true = torch.zeros((q1 - q0,), dtype=torch.float32, device=dev)
-            parallel.all_reduce_sum_(d_true)
-            if n_g:
-                counts[q0:q1] = kn.rank_count_thresh(dist, d_true.contiguous())
-        if k is not None:
-            v, i = kn.topk_smallest(dist, k, shard_begin) if n_g else _empty_topk(q1 - q0, k, dev)
-            vals.append(v)
-            idxs.append(i)
-    if want_ranks:
-        parallel.all_reduce_sum_(counts)
-    if k is None:
-        return counts, None, None
-    v, i = torch.cat(vals), torch.cat(idxs)
-    if parallel.world() > 1:
-        v, i = _merge_topk(v, i, k, kn)
-    return counts, v, i
 
 
 def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _match=None, _count=None, shift_mask=None,
@@ -927,7 +881,7 @@ def sharded_ranks(overhead_shard, surface_all, shard_begin, query_chunk=4096, _m
     fixed = ops.match_fwd_fixed if _match is None else (lambda ov, su, shift, **_kw: _match(ov, su, known_shift=shift))
     kn = SimpleNamespace(match_fwd=_match or ops.match_fwd, match_fwd_fixed=fixed, rank_count_thresh=_count or ops.rank_count_thresh)
     counts = _direct_pass(kn, overhead_shard.contiguous(), surface_all, prior, shard_begin, query_chunk, None, True)[0]
-    return counts.cpu().numpy().astype('int64')
+    return retrieval.host_ranks(counts)
 
 
 def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='direct', _kernels=None,
@@ -940,26 +894,6 @@ def retrieve_topk(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=
     retrieve()."""
     return retrieve(overhead_shard, surface_all, k, shard_begin, query_chunk, method, _kernels, _want_ranks=False,
                     shift_mask=shift_mask, known_shift=known_shift)[1:]
-
-
-def _merge_topk(v, i, k, _kernels=None):
-    """All-gather per-shard [N,k] candidate lists and merge them on (distance, global gallery index)."""
-    from . import parallel
-    kn = _kernels or ops
-    w = parallel.world()
-    n_q = v.shape[0]
-    v_all = parallel._all_gather_cat(v.unsqueeze(0))            # [w, N, k]
-    i_all = parallel._all_gather_cat(i.unsqueeze(0))
-    cand_v = v_all.permute(0, 2, 1).reshape(w * k, n_q).contiguous()   # candidates as a [w*k, N] "distance matrix"
-    cand_i = i_all.permute(0, 2, 1).reshape(w * k, n_q)
-    cand_v = torch.where(cand_i < 0, torch.full_like(cand_v, float('inf')), cand_v)
-    # order candidate rows by global index first so that the kernel's row-number tie-break equals the
-    # gallery-index tie-break
-    order = torch.argsort(torch.where(cand_i < 0, torch.full_like(cand_i, 2 ** 62), cand_i), dim=0, stable=True)
-    cand_v = torch.gather(cand_v, 0, order).contiguous()
-    cand_i = torch.gather(cand_i, 0, order)
-    v, pos = kn.topk_smallest(cand_v, k)
-    return v, torch.gather(cand_i.t(), 1, pos.clamp(min=0))
 
 
 def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096, method='direct', _kernels=None,
@@ -984,14 +918,13 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
     rank-count and top-k kernels: ranks, distances and indices equal method='direct' under shift_mask = 1 << known_shift exactly.
     'direct' / 'auto' with known_shift run the same pass; 'dft' / 'dft_masked' refuse it."""
     kn = _kernels or ops
-    if not 1 <= int(k) <= ops.TOPK_MAX:
-        raise _lib.WitwError('retrieve: k=%d outside [1,%d] (the longest candidate list, ops.TOPK_MAX)' % (int(k), ops.TOPK_MAX))
+    retrieval.check_k(k)
     prior = _Prior.of(shift_mask, known_shift, surface_all)
     resolved = _resolve_method('retrieve', method, prior)
     gallery = overhead_shard.contiguous()
     if resolved == 'direct':
         counts, v, i = _direct_pass(kn, gallery, surface_all, prior, shard_begin, query_chunk, k, _want_ranks)
-        return (counts.cpu().numpy().astype('int64') if _want_ranks else None), v, i
+        return (retrieval.host_ranks(counts) if _want_ranks else None), v, i
     if k + DFT_MARGIN > 32:                          # no room for the candidate margin in a 32-wide list: the top-k comes from the
         ranks_dft = None                              # direct pass, the rank counts (no list involved) still from the spectral one
         if _want_ranks:
@@ -999,23 +932,6 @@ def retrieve(overhead_shard, surface_all, k=10, shard_begin=0, query_chunk=4096,
         _counts, v, i = _direct_pass(kn, gallery, surface_all, prior, shard_begin, query_chunk, k, False)
         return ranks_dft, v, i
     return _retrieve_dft(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, _want_ranks, method)
-
-
-def _sort_by_value_then_index(v, i):
-    """rows of (v, i) ordered by (value, index) ascending; missing candidates (index < 0) last."""
-    big = torch.where(i < 0, torch.full_like(i, 2 ** 62), i)
-    o1 = torch.argsort(big, dim=1, stable=True)
-    v, i = torch.gather(v, 1, o1), torch.gather(i, 1, o1)
-    o2 = torch.argsort(v, dim=1, stable=True)
-    return torch.gather(v, 1, o2), torch.gather(i, 1, o2)
-
-
-_RETRIEVE_TLS = __import__('threading').local()
-
-
-def last_retrieve_stats():
-    """Re-scoring statistics of the calling thread's last retrieve(method='dft') (retrieve.last_stats is process-wide)."""
-    return dict(getattr(_RETRIEVE_TLS, 'stats', None) or {})
 
 
 DFT_MARGIN = 6      # candidates kept beyond place k by the spectral top-k (place k+1 must exist to decide place k)
@@ -1029,8 +945,8 @@ def _retrieve_dft(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, 
     mask was given. eps is derived as without a mask: at full width the distance depends on the
     largest ALLOWED score only, which both kernels know to SCORE_ROUNDING; below full width the gap that decides a re-scoring
     is taken over the allowed shifts, so what is left has its shift settled among them; and the gallery's worst window bounds
-    |ov| / |window| whatever shifts a mask leaves. method: the name the pass was asked for, for the statistics."""
-    from . import parallel
+    |ov| / |window| whatever shifts a mask leaves. method: the name the pass was asked for, for the statistics.
+    The exchanges and re-scorings themselves are witw_amd.retrieval's; what is decided on them is decided here."""
     eps = float(getattr(kn, 'DISTANCE_EPS', ops.DISTANCE_EPS))
     dev = surface_all.device
     n_q, n_g, we = surface_all.shape[0], gallery.shape[0], surface_all.shape[3]
@@ -1049,7 +965,6 @@ def _retrieve_dft(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, 
         nq = q1 - q0
         su = surface_all[q0:q1].contiguous()
         rows = prior.rows(q0, q1)
-        masked = rows.kw()
         if n_g:
             dist, ws, n_fix = _spectral_distances(kn, gallery, su, spec_g, rows, we)
             stats['rescored_orientation'] += n_fix
@@ -1070,30 +985,15 @@ def _retrieve_dft(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, 
             rounding = float(getattr(kn, 'SCORE_ROUNDING', ops.SCORE_ROUNDING))
             eps = max(eps, 1.25 * 4 * rounding * float(ratio.item()))
         if want_ranks:
-            # the queries of this chunk whose true row lives in this shard: a contiguous range, known on the host (no mask, no
-            # device round trip)
-            lo, hi = max(q0, shard_begin), min(q1, shard_begin + n_g)
-            d_true = torch.zeros((nq,), dtype=torch.float32, device=dev)
-            if n_g and hi > lo:                          # the owner's EXACT distance of every true pair
-                po = torch.arange(lo - shard_begin, hi - shard_begin, dtype=torch.int32, device=dev)
-                ps = torch.arange(lo - q0, hi - q0, dtype=torch.int32, device=dev)
-                d_true[lo - q0:hi - q0] = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **masked)[1]
-                stats['rescored_true'] += hi - lo
-            parallel.all_reduce_sum_(d_true)
-            if n_g:
-                d_true = d_true.contiguous()
-                if hasattr(kn, 'rank_count_resolved'):
-                    # band list, exact re-scoring and the count update in one stream sequence; the list's length stays on the device
-                    # and is looked at once, behind the last chunk (band_checks)
-                    c, n_band, cap = kn.rank_count_resolved(dist, d_true, eps, gallery, su, wn, sn, **masked)
-                    band_checks.append((n_band, cap, q0, q1, dist if single_chunk else None, su, d_true, sn))
-                else:
-                    c, po, ps = kn.rank_count_band(dist, d_true, eps)
-                    if po.numel():
-                        d_x = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **masked)[1]
-                        c.index_add_(0, ps.long(), (d_x <= d_true[ps.long()]).to(torch.int32))
-                        stats['rescored_rank'] += int(po.numel())
-                counts[q0:q1] = c
+            exact = _exact_pairs(kn, gallery, su, wn, sn, rows)
+            d_true = retrieval.true_distances(exact, q0, q1, shard_begin, n_g, dev, stats)
+            if n_g and hasattr(kn, 'rank_count_resolved'):
+                # band list, exact re-scoring and the count update in one stream sequence; the list's length stays on the device
+                # and is looked at once, behind the last chunk (band_checks)
+                counts[q0:q1], n_band, cap = kn.rank_count_resolved(dist, d_true, eps, gallery, su, wn, sn, **rows.kw())
+                band_checks.append((n_band, cap, q0, q1, dist if single_chunk else None, su, d_true, sn))
+            elif n_g:
+                counts[q0:q1] = retrieval.band_rescore(kn, dist, d_true, eps, exact, d_true, stats)
         v, i = kn.topk_smallest(dist, kc, shard_begin) if n_g else _empty_topk(nq, kc, dev)
         vals.append(v)
         idxs.append(i)
@@ -1104,9 +1004,14 @@ def _retrieve_dft(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, 
     v, i = _settle_topk(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, eps, torch.cat(vals), torch.cat(idxs), wn,
                         torch.cat(sns), stats)
     stats['eps'] = eps
-    retrieve.last_stats = stats
-    _RETRIEVE_TLS.stats = stats
-    return (counts.cpu().numpy().astype('int64') if want_ranks else None), v, i
+    retrieval.publish_stats(retrieve, stats)
+    return (retrieval.host_ranks(counts) if want_ranks else None), v, i
+
+
+def _exact_pairs(kn, gallery, su, wn, sn, prior):
+    """witw_amd.retrieval's `exact_pairs` of the spectral pass: the pairs (po, ps) of (gallery, su) through kn.match_pairs -- the
+    direct kernel's bits -- on the pass's workspace norms, under su's rows of the prior"""
+    return lambda po, ps: kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **prior.kw())[1]
 
 
 def _spectral_distances(kn, gallery, su, spec_g, prior, we):
@@ -1128,10 +1033,8 @@ def _redo_overflowed_bands(kn, gallery, spec_g, prior, we, eps, wn, band_checks,
             rows = prior.rows(q0, q1)
             if dist_c is None:
                 dist_c = _spectral_distances(kn, gallery, su, spec_g, rows, we)[0]
-            c, po, ps = kn.rank_count_band(dist_c, d_true, eps)
-            d_x = kn.match_pairs(gallery, su, wn, sn, po, ps, want_orientation=False, **rows.kw())[1]
-            c.index_add_(0, ps.long(), (d_x <= d_true[ps.long()]).to(torch.int32))
-            counts[q0:q1] = c
+            exact = _exact_pairs(kn, gallery, su, wn, sn, rows)
+            counts[q0:q1] = retrieval.band_rescore(kn, dist_c, d_true, eps, exact, d_true)      # its pairs are counted above
 
 
 def _settle_topk(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, eps, v, i, wn, sn_all, stats):
@@ -1139,15 +1042,9 @@ def _settle_topk(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, e
     them: the lists are gathered and ordered by (spectral distance, index); a query with a gap within rounding among its first
     k + 1 places, or with place k within rounding of the best row outside the lists, has its candidates re-scored exactly; one
     that even then cannot exclude a row outside the re-scored set takes the direct pass."""
-    from . import parallel
     dev = surface_all.device
-    n_q, n_g, kc = surface_all.shape[0], gallery.shape[0], k + DFT_MARGIN
-    w = parallel.world()
-    outsider = v[:, kc - 1].clone()                      # no row outside a shard's list has a smaller spectral distance
-    if w > 1:
-        v = parallel._all_gather_cat(v.unsqueeze(0)).permute(1, 0, 2).reshape(n_q, w * kc)
-        i = parallel._all_gather_cat(i.unsqueeze(0)).permute(1, 0, 2).reshape(n_q, w * kc)
-        outsider = parallel._all_gather_cat(outsider.unsqueeze(0)).min(dim=0).values
+    n_q, n_g = surface_all.shape[0], gallery.shape[0]
+    v, i, outsider = retrieval.gather_candidates(v, i)
     v = torch.where(i < 0, torch.full_like(v, float('inf')), v)
     v, i = _sort_by_value_then_index(v.contiguous(), i.contiguous())
     ncand = v.shape[1]
@@ -1161,28 +1058,16 @@ def _settle_topk(kn, gallery, surface_all, prior, k, shard_begin, query_chunk, e
     rows = torch.nonzero(undecided).squeeze(1)           # identical on every rank: computed from gathered data
     fallback = torch.zeros((0,), dtype=torch.int64, device=dev)
     if rows.numel():
-        ci = i[rows, :m]                                                     # [r, m] global gallery rows
-        mine = (ci >= shard_begin) & (ci < shard_begin + n_g)
-        exact = torch.zeros(ci.shape, dtype=torch.float32, device=dev)
-        if n_g and bool(mine.any()):
-            po = (ci - shard_begin)[mine].to(torch.int32).contiguous()
-            ps = rows[:, None].expand(-1, m)[mine].to(torch.int32).contiguous()
-            exact[mine] = kn.match_pairs(gallery, surface_all.contiguous(), wn, sn_all, po, ps, want_orientation=False, **prior.kw())[1]
-            stats['rescored_topk'] += int(po.numel())
-        parallel.all_reduce_sum_(exact)
-        exact = torch.where(ci < 0, torch.full_like(exact, float('inf')), exact)
-        ev, ei = _sort_by_value_then_index(exact, ci)
+        exact = _exact_pairs(kn, gallery, surface_all.contiguous(), wn, sn_all, prior)
+        ev, ei = retrieval.rescore_candidates(exact, i[rows, :m], rows, shard_begin, n_g, stats)
         # nothing outside the re-scored set can belong to the first k: its direct distance is >= its spectral one - eps
         beyond = torch.minimum(outsider[rows], vp[rows, m]) - eps
         kth = ev[:, min(k, m) - 1]
         safe = (kth < beyond) | ~torch.isfinite(beyond)
         v[rows, :m], i[rows, :m] = ev, ei
         fallback = rows[~safe]
-    if fallback.numel():     # more near-ties than candidates kept (not seen on real data): those queries take the direct pass
-        stats['fallback_queries'] = int(fallback.numel())
-        _counts, fv, fi = _direct_pass(kn, gallery, surface_all[fallback].contiguous(), prior.take(fallback), shard_begin,
-                                       query_chunk, k, False)
-        v[fallback, :k], i[fallback, :k] = fv, fi
+    retrieval.fall_back(lambda q: _direct_pass(kn, gallery, surface_all[q].contiguous(), prior.take(q), shard_begin, query_chunk, k,
+                                               False)[1:], fallback, v, i, k, stats)
     return v[:, :k].contiguous(), i[:, :k].contiguous()
 
 
@@ -1218,20 +1103,11 @@ class _ShardedMatchLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, overhead_local, surface_local, alpha, k, prior=_NO_PRIOR):
-        from . import parallel
-        b = surface_local.shape[0]
-        col0 = parallel.rank() * b
-        with parallel.phase('overhead_all_gather'):
-            ov_all = parallel._all_gather_cat(overhead_local.contiguous())
-        su = surface_local.contiguous()
+        ov_all, su, b, col0, B, _world = slab_loss.open_slab(overhead_local, surface_local, always=True)
         with parallel.phase('slab_match'):
             ori, dist, score, ws = prior.match_fwd(k, ov_all, su, want_score=True, want_workspace=True)
-        B = ov_all.shape[0]
-        with parallel.phase('diagonal_all_gather'):
-            diag = parallel._all_gather_cat(dist[col0:col0 + b].diagonal().contiguous())
-        with parallel.phase('loss_partial_all_reduce'):
-            part = k.triplet_loss_slab_fwd(dist, diag, col0, alpha)
-            parallel.all_reduce_sum_(part)
+        diag = slab_loss.gather_diagonal(dist, col0, b, True)
+        part = slab_loss.sum_partial(lambda: k.triplet_loss_slab_fwd(dist, diag, col0, alpha), True)
         ctx.save_for_backward(ov_all, su, ori, score, ws, dist, diag)
         ctx.cfg = (col0, b, float(alpha), k)
         ctx.mark_non_differentiable(ori, dist)
@@ -1239,7 +1115,6 @@ class _ShardedMatchLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g_ori, _g_dist):
-        from . import parallel
         ov_all, su, ori, score, ws, dist, diag = ctx.saved_tensors
         col0, b, alpha, k = ctx.cfg
         with parallel.phase('row_sigmoid_all_reduce'):
@@ -1248,15 +1123,13 @@ class _ShardedMatchLossFn(torch.autograd.Function):
         with parallel.phase('slab_match_backward'):
             g_dist = k.triplet_loss_slab_bwd(dist, diag, rowsig, colsig, g_loss.contiguous(), col0, alpha)
             gov_all, gsu = k.match_bwd(ov_all, su, ori, score, ws, g_dist, True, True)
-        with parallel.phase('overhead_grad_reduce_scatter'):
-            gov = parallel.reduce_scatter_rows(gov_all, b)
-        return gov, gsu, None, None, None
+        return slab_loss.scatter_overhead_grad(gov_all, b, True), gsu, None, None, None
 
 
 class _BatchHardMatchLossFn(torch.autograd.Function):
     """match + batch-hard soft-margin triplet loss over the GLOBAL batch, fused: the backward never builds a dense dL/dD. The
     mined pairs (at most 3B) go straight to the pair-list match backward (ops.match_bwd_pairs).
-    One rank: the full [B,B] matrix (ops.batch_hard_fwd). N ranks: the column slab of _ShardedMatchLossFn, and
+    One rank: the full [B,B] matrix (ops.batch_hard_fwd). N ranks: the column-slab protocol of witw_amd.slab_loss, and
     forward = all-gather of the overhead embeddings, of the diagonal (B floats) and of the per-rank row minima ([w,B] values +
     global column indices, reduced in rank order: the lowest index wins a tie), all-reduce of the loss partial (each rank: row
     terms of the anchors it owns + column terms of its columns); backward = the pairs whose column this rank owns through
@@ -1266,31 +1139,15 @@ class _BatchHardMatchLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, overhead_local, surface_local, alpha, k, prior=_NO_PRIOR):
-        from . import parallel
-        world = parallel.world()
-        b = surface_local.shape[0]
-        col0 = parallel.rank() * b if world > 1 else 0
-        su = surface_local.contiguous()
-        if world > 1:
-            with parallel.phase('overhead_all_gather'):
-                ov_all = parallel._all_gather_cat(overhead_local.contiguous())
-        else:
-            ov_all = overhead_local.contiguous()
+        ov_all, su, b, col0, B, world = slab_loss.open_slab(overhead_local, surface_local)
         with parallel.phase('slab_match'):
             ori, dist, score, ws = prior.match_fwd(k, ov_all, su, want_score=True, want_workspace=True)
-        B = ov_all.shape[0]
+        diag = slab_loss.gather_diagonal(dist, col0, b, world > 1)
         if world > 1:
-            with parallel.phase('diagonal_all_gather'):
-                diag = parallel._all_gather_cat(dist[col0:col0 + b].diagonal().contiguous())
-            with parallel.phase('row_minima_all_gather'):
-                rv_l, ri_l, cv, ci = k.batch_hard_slab_mine(dist, col0)
-                rv, ri = k.batch_hard_merge_rows(parallel._all_gather_cat(rv_l[None]), parallel._all_gather_cat(ri_l[None]))
-            with parallel.phase('loss_partial_all_reduce'):
-                part = k.batch_hard_slab_loss(dist, rv, cv, col0, alpha)
-                parallel.all_reduce_sum_(part)
+            rv, ri, cv, ci = slab_loss.mine_global(k, dist, col0, True)
+            part = slab_loss.sum_partial(lambda: k.batch_hard_slab_loss(dist, rv, cv, col0, alpha), True)
             loss = (part / (2. * B)).reshape(())
         else:
-            diag = dist.diagonal().contiguous()
             loss, rv, ri, cv, ci = k.batch_hard_fwd(dist, alpha)
             loss = loss.reshape(())
         ctx.save_for_backward(ov_all, su, ori, score, ws, diag, rv, ri, cv, ci)
@@ -1301,7 +1158,6 @@ class _BatchHardMatchLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, *_g):
-        from . import parallel
         if g_loss is None:
             return None, None, None, None, None
         ov_all, su, ori, score, ws, diag, rv, ri, cv, ci = ctx.saved_tensors
@@ -1309,10 +1165,7 @@ class _BatchHardMatchLossFn(torch.autograd.Function):
         with parallel.phase('slab_match_backward'):
             po, ps, pw = k.batch_hard_pairs(diag, rv, ri, cv, ci, g_loss.contiguous(), col0, alpha)
             gov_all, gsu = k.match_bwd_pairs(ov_all, su, ori, score, ws, po, ps, pw)
-        if world > 1:
-            with parallel.phase('overhead_grad_reduce_scatter'):
-                gov_all = parallel.reduce_scatter_rows(gov_all, b)
-        return gov_all, gsu, None, None, None
+        return slab_loss.scatter_overhead_grad(gov_all, b, world > 1), gsu, None, None, None
 
 
 def sharded_match_loss(overhead_local, surface_local, alpha=10., _kernels=None, loss='soft_margin', mined=False, known_shift=None):

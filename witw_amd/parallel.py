@@ -4,7 +4,8 @@ The encoder has no BatchNorm, so samples are independent and the minibatch shard
 (SURVEY.md §8e). The loss couples the GLOBAL batch (nn.DataParallel semantics of the reference,
 model/cvig_baseline.py:339-343; normaliser 2B(B-1) with B = global batch, model/cvig_fov.py:380):
   1. the overhead embeddings are all-gathered (2 MiB per rank at 128 pairs/rank),
-  2. every rank evaluates match + loss for its column slab [B_global, b_local] (cvig_fov.sharded_match_loss);
+  2. every rank evaluates match + loss for its column slab [B_global, b_local] (cvig_fov.sharded_match_loss, on the protocol
+     of slab_loss.py, which cvig_baseline's sharded losses share);
      the diagonal, the loss partial and the row sigmoid sums are exchanged (B floats each), the
      overhead-embedding gradients are reduce-scattered to their owners (reduce_scatter_rows);
      all_gather_embeddings keeps the simpler replicated form (every rank evaluates the full matrix, backward

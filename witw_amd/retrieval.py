@@ -1,0 +1,196 @@
+"""The model-independent part of gallery retrieval: one chunked direct pass, and the mechanics every "coarse pass, then re-make each
+rounding-level decision on exact pair distances" pass shares (cvig_fov._retrieve_dft on the spectral distances,
+cvig_baseline._retrieve_gemm on the GEMM form).
+
+The gallery is sharded by rows -- this rank holds rows [shard_begin, shard_begin + n_g), possibly none -- the queries are replicated
+and query q's true row is gallery row q. A coarse pass brings what differs as `exact_pairs(po, ps)`: the exact distances of the
+pairs (local gallery row po[j], query ps[j]) of the queries at hand, bit-identical to the direct kernel's. The two rules that
+decide which query is settled are different mathematics and stay with their models.
+
+Host logic only; op sets are injected (`kn`), every exchange goes through witw_amd.parallel.
+"""
+from types import SimpleNamespace
+import threading
+
+import torch
+
+from . import _lib, ops, parallel
+
+_TLS = threading.local()
+
+
+def last_retrieve_stats():
+    """Re-scoring statistics of the calling thread's last retrieve() on a coarse pass (cvig_fov: method 'dft' / 'dft_masked',
+    cvig_baseline: 'gemm'): method, pairs, rescored_true / _rank / _topk, fallback_queries, eps, and cvig_fov's masked /
+    rescored_orientation (retrieve.last_stats is process-wide)."""
+    return dict(getattr(_TLS, 'stats', None) or {})
+
+
+def publish_stats(retrieve, stats):
+    """`stats` as the model's retrieve.last_stats (process-wide) and the calling thread's last_retrieve_stats()"""
+    retrieve.last_stats = stats
+    _TLS.stats = stats
+
+
+def check_k(k):
+    if not 1 <= int(k) <= ops.TOPK_MAX:
+        raise _lib.WitwError('retrieve: k=%d outside [1,%d] (the longest candidate list, ops.TOPK_MAX)' % (int(k), ops.TOPK_MAX))
+
+
+def host_ranks(counts):
+    """device counts -> the int64 [N] on the host that every ranking function returns"""
+    return counts.cpu().numpy().astype('int64')
+
+
+def _empty_topk(nq, k, device):
+    """the candidate lists of a rank without gallery rows (more ranks than rows): k places at +inf, index -1"""
+    return (torch.full((nq, k), float('inf'), dtype=torch.float32, device=device),
+            torch.full((nq, k), -1, dtype=torch.int64, device=device))
+
+
+def _sort_by_value_then_index(v, i):
+    """rows of (v, i) ordered by (value, index) ascending; missing candidates (index < 0) last."""
+    big = torch.where(i < 0, torch.full_like(i, 2 ** 62), i)
+    o1 = torch.argsort(big, dim=1, stable=True)
+    v, i = torch.gather(v, 1, o1), torch.gather(i, 1, o1)
+    o2 = torch.argsort(v, dim=1, stable=True)
+    return torch.gather(v, 1, o2), torch.gather(i, 1, o2)
+
+
+def _merge_topk(v, i, k, _kernels=None):
+    """All-gather per-shard [N,k] candidate lists and merge them on (distance, global gallery index)."""
+    kn = _kernels or ops
+    w = parallel.world()
+    n_q = v.shape[0]
+    v_all = parallel._all_gather_cat(v.unsqueeze(0))            # [w, N, k]
+    i_all = parallel._all_gather_cat(i.unsqueeze(0))
+    cand_v = v_all.permute(0, 2, 1).reshape(w * k, n_q).contiguous()   # candidates as a [w*k, N] "distance matrix"
+    cand_i = i_all.permute(0, 2, 1).reshape(w * k, n_q)
+    cand_v = torch.where(cand_i < 0, torch.full_like(cand_v, float('inf')), cand_v)
+    # order candidate rows by global index first so that the kernel's row-number tie-break equals the
+    # gallery-index tie-break
+    order = torch.argsort(torch.where(cand_i < 0, torch.full_like(cand_i, 2 ** 62), cand_i), dim=0, stable=True)
+    cand_v = torch.gather(cand_v, 0, order).contiguous()
+    cand_i = torch.gather(cand_i, 0, order)
+    v, pos = kn.topk_smallest(cand_v, k)
+    return v, torch.gather(cand_i.t(), 1, pos.clamp(min=0))
+
+
+def _direct_pass(kn, gallery, surface_all, prior, shard_begin, query_chunk, k, want_ranks):
+    """The chunked pass of sharded_ranks / retrieve(method='direct' / 'fixed') over this rank's gallery rows [shard_begin,
+    shard_begin + n): one match per query chunk under the chunk's rows of the prior (a cvig_fov._Prior); want_ranks: the owner of
+    each true row publishes its distance (all-reduce of a vector that is zero elsewhere), every rank counts d <= d_true over its
+    shard and the counts are summed behind the last chunk; k (None: no lists): the k nearest rows per query, merged over the ranks.
+    A rank without gallery rows still takes part in every exchange. -> (counts int32 [N] on the device, values [N,k], indices
+    [N,k])."""
+    dev = surface_all.device
+    n_q, n_g = surface_all.shape[0], gallery.shape[0]
+    counts = torch.zeros((n_q,), dtype=torch.int32, device=dev)
+    vals, idxs = [], []
+    for q0 in range(0, n_q, query_chunk):
+        q1 = min(n_q, q0 + query_chunk)
+        if n_g:
+            dist = prior.rows(q0, q1).match_fwd(kn, gallery, surface_all[q0:q1].contiguous(), want_orientation=False)[1]   # [n_g, q]
+        if want_ranks:
+            if n_g:
+                qi = torch.arange(q0, q1, device=dist.device)
+                own = (qi >= shard_begin) & (qi < shard_begin + n_g)
+                row = (qi - shard_begin).clamp(0, n_g - 1)
+                d_true = torch.where(own, dist[row, qi - q0], torch.zeros_like(dist[0]))
+            else:
+                d_true = torch.zeros((q1 - q0,), dtype=torch.float32, device=dev)
+            parallel.all_reduce_sum_(d_true)
+            if n_g:
+                counts[q0:q1] = kn.rank_count_thresh(dist, d_true.contiguous())
+        if k is not None:
+            v, i = kn.topk_smallest(dist, k, shard_begin) if n_g else _empty_topk(q1 - q0, k, dev)
+            vals.append(v)
+            idxs.append(i)
+    if want_ranks:
+        parallel.all_reduce_sum_(counts)
+    if k is None:
+        return counts, None, None
+    v, i = torch.cat(vals), torch.cat(idxs)
+    if parallel.world() > 1:
+        v, i = _merge_topk(v, i, k, kn)
+    return counts, v, i
+
+
+def sqdist_direct_pass(kn, block_rows, gallery, surface_all, prior, shard_begin, query_chunk, k, want_ranks):
+    """_direct_pass for embeddings compared by Euclidean distance: its `match` is kn.pairwise_sqdist(take_sqrt=True) over blocks
+    of at most block_rows gallery rows (the kernel's row index is gridDim.y); prior: cvig_fov._NO_PRIOR."""
+    def match_fwd(gallery, queries, **_kw):
+        blocks = [kn.pairwise_sqdist(gallery[r0:r0 + block_rows], queries, take_sqrt=True) for r0 in range(0, gallery.shape[0], block_rows)]
+        return None, (blocks[0] if len(blocks) == 1 else torch.cat(blocks))
+    direct = SimpleNamespace(match_fwd=match_fwd, rank_count_thresh=kn.rank_count_thresh, topk_smallest=kn.topk_smallest)
+    return _direct_pass(direct, gallery, surface_all, prior, shard_begin, query_chunk, k, want_ranks)
+
+
+# ----------------------------------------------------------------------------- what the coarse passes share
+def true_distances(exact_pairs, q0, q1, shard_begin, n_g, dev, stats):
+    """d_true [q1 - q0] of the query chunk [q0, q1): the owner's EXACT distance of every true pair -- the queries whose true row
+    lives in this shard are a contiguous range, known on the host (no mask, no device round trip) -- zero elsewhere, all-reduced."""
+    lo, hi = max(q0, shard_begin), min(q1, shard_begin + n_g)
+    d_true = torch.zeros((q1 - q0,), dtype=torch.float32, device=dev)
+    if hi > lo:
+        po = torch.arange(lo - shard_begin, hi - shard_begin, dtype=torch.int32, device=dev)
+        ps = torch.arange(lo - q0, hi - q0, dtype=torch.int32, device=dev)
+        d_true[lo - q0:hi - q0] = exact_pairs(po, ps)
+        stats['rescored_true'] += hi - lo
+    parallel.all_reduce_sum_(d_true)
+    return d_true
+
+
+def band_rescore(kn, dist, thresholds, eps, exact_pairs, d_true, stats=None):
+    """Rank counts of a chunk from coarse distances: kn.rank_count_band counts the rows below thresholds - eps and lists the pairs
+    within eps of their threshold, which are decided on their exact distances, d_x <= d_true. `thresholds` is d_true in the units
+    of `dist` (the GEMM pass: squared; the comparison itself is on the rooted values). stats (None: a redo whose pairs were
+    counted already) takes the pairs re-scored. -> counts int32 [chunk]."""
+    c, po, ps = kn.rank_count_band(dist, thresholds, eps)
+    if po.numel():
+        d_x = exact_pairs(po, ps)
+        c.index_add_(0, ps.long(), (d_x <= d_true[ps.long()]).to(torch.int32))
+        if stats is not None:
+            stats['rescored_rank'] += int(po.numel())
+    return c
+
+
+def gather_candidates(v, i, want_values=True):
+    """The shards' candidate lists (v, i: [N, kc] by coarse distance) rank-major as [N, w kc] -- the values only where the caller
+    orders by them -- and `outsider` [N]: no row outside every shard's list has a smaller coarse distance (+inf where a shard has
+    fewer than kc rows: nothing outside its list). -> (v, i, outsider)"""
+    w, (n_q, kc) = parallel.world(), i.shape
+    outsider = v[:, kc - 1].clone()
+    if w > 1:
+        if want_values:
+            v = parallel._all_gather_cat(v.unsqueeze(0)).permute(1, 0, 2).reshape(n_q, w * kc)
+        i = parallel._all_gather_cat(i.unsqueeze(0)).permute(1, 0, 2).reshape(n_q, w * kc)
+        outsider = parallel._all_gather_cat(outsider.unsqueeze(0)).min(dim=0).values
+    return v, i, outsider
+
+
+def rescore_candidates(exact_pairs, ci, queries, shard_begin, n_g, stats):
+    """The candidate table ci [r, m] (global gallery rows, -1: a missing place) of the queries `queries` (int64 [r]; None: row j is
+    query j) on exact distances: every owner re-scores the candidates it holds, the table is all-reduced, missing places are +inf.
+    -> (distances, rows) ordered by (exact distance, index)."""
+    dev = ci.device
+    mine = (ci >= shard_begin) & (ci < shard_begin + n_g)
+    exact = torch.zeros(ci.shape, dtype=torch.float32, device=dev)
+    if n_g and bool(mine.any()):
+        if queries is None:
+            queries = torch.arange(ci.shape[0], device=dev)
+        po = (ci - shard_begin)[mine].to(torch.int32).contiguous()
+        ps = queries[:, None].expand_as(ci)[mine].to(torch.int32).contiguous()
+        exact[mine] = exact_pairs(po, ps)
+        stats['rescored_topk'] += int(po.numel())
+    parallel.all_reduce_sum_(exact)
+    exact = torch.where(ci < 0, torch.full_like(exact, float('inf')), exact)
+    return _sort_by_value_then_index(exact, ci)
+
+
+def fall_back(direct_lists, unsafe, v, i, k, stats):
+    """The queries `unsafe` (int64; identical on every rank: computed from gathered data) -- more near-ties than candidates kept,
+    not seen on real data -- take the direct pass: direct_lists(unsafe) -> their (values, indices) [r, k], written into v, i."""
+    if unsafe.numel():
+        stats['fallback_queries'] = int(unsafe.numel())
+        v[unsafe, :k], i[unsafe, :k] = direct_lists(unsafe)
