@@ -328,7 +328,7 @@ def test_semantic_training_step_matches_reference_golden(golden_dir):
 
 
 def _philox4x32_10_first(k0, k1, c0, c1, c2, c3):
-    """numpy restatement of csrc/loss.hip's generator (Salmon et al., SC'11): first output word."""
+    """numpy restatement of csrc/dropout2d.hip's generator (Salmon et al., SC'11): first output word."""
     c = [np.asarray(v, dtype=np.uint64) for v in (c0, c1, c2, c3)]
     k0, k1 = np.uint64(k0), np.uint64(k1)
     m32 = np.uint64(0xFFFFFFFF)

@@ -10,7 +10,7 @@
 // exhaustive minibatch triplet loss (:286-315).
 #include "common.h"
 #include "bn_sums.h"
-#include "exhaustive_terms.h"
+#include "loss_terms.h"
 #include "sqdist_row.h"
 
 namespace {
@@ -196,11 +196,7 @@ __global__ __launch_bounds__(256) void embed_normalize_kernel(float* __restrict_
     float* row = f + (size_t)blockIdx.x * n;
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += row[i] * row[i];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const float nrm = sqrtf((part[0] + part[1]) + (part[2] + part[3]));
+    const float nrm = sqrtf(block_sum_256(s, part));
     const float den = powf(nrm, 0.5f);
     for (int i = threadIdx.x; i < n; i += 256) row[i] = row[i] / den;
 }
@@ -220,35 +216,19 @@ __global__ __launch_bounds__(256) void pairwise_sqdist_kernel(const float* __res
 
 // part[i] = sum_{j != i} l(D_ii - D_ij) + l(D_ii - D_ji); D[i][j] = |e1_i - e2_j|^2
 __global__ __launch_bounds__(256) void exhaustive_partials_kernel(const float* __restrict__ D, float* __restrict__ part, int B,
-                                                                   int soft, float alpha, float margin) {
+                                                                   BaselineTerm term) {
     __shared__ float sh[4];
     const int i = blockIdx.x;
     const float dii = D[(size_t)i * B + i];
     float s = 0.f;
     for (int j = threadIdx.x; j < B; j += 256) {
         if (j == i) continue;
-        s += trip(dii - D[(size_t)i * B + j], soft, alpha, margin);
-        s += trip(dii - D[(size_t)j * B + i], soft, alpha, margin);
+        s += term.value(dii - D[(size_t)i * B + j]);
+        s += term.value(dii - D[(size_t)j * B + i]);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) part[i] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    const float tot = block_sum_256(s, sh);
+    if (threadIdx.x == 0) part[i] = tot;
 }
-
-__global__ __launch_bounds__(256) void sum_finish_kernel(const float* __restrict__ part, float* __restrict__ out, int n,
-                                                          float norm) {
-    __shared__ float sh[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = ((sh[0] + sh[1]) + (sh[2] + sh[3])) / norm;
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // Training-mode pieces (model/cvig_baseline.py:267-284 under .train(), autograd of :286-315): batch statistics of
@@ -337,7 +317,7 @@ __global__ void gem_pool_bwd_kernel(const float* __restrict__ a, const float* __
 // is recovered from the saved norm.
 __global__ __launch_bounds__(256) void embed_normalize_bwd_kernel(const float* __restrict__ g, const float* __restrict__ df,
                                                                    float* __restrict__ dg, int n) {
-    __shared__ float part[2][4];
+    __shared__ float part[4];
     const float* gr = g + (size_t)blockIdx.x * n;
     const float* dr = df + (size_t)blockIdx.x * n;
     float s0 = 0.f, s1 = 0.f;
@@ -345,18 +325,8 @@ __global__ __launch_bounds__(256) void embed_normalize_bwd_kernel(const float* _
         s0 += gr[i] * gr[i];
         s1 += gr[i] * dr[i];
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        s0 += __shfl_xor(s0, d, 64);
-        s1 += __shfl_xor(s1, d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        part[0][threadIdx.x >> 6] = s0;
-        part[1][threadIdx.x >> 6] = s1;
-    }
-    __syncthreads();
-    const float nn = (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);     // |g|^2
-    const float gd = (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
+    const float nn = block_sum_256(s0, part);     // |g|^2
+    const float gd = block_sum_256(s1, part);
     const float nrm = sqrtf(nn);
     const float c0 = 1.f / sqrtf(nrm), c1 = 0.5f * gd / (nrm * nrm * sqrtf(nrm));
     for (int i = threadIdx.x; i < n; i += 256) dg[(size_t)blockIdx.x * n + i] = dr[i] * c0 - c1 * gr[i];
@@ -364,25 +334,22 @@ __global__ __launch_bounds__(256) void embed_normalize_bwd_kernel(const float* _
 
 // G = dL/dD for the exhaustive loss; one block per row a (diagonal entry gathers the row and column terms).
 __global__ __launch_bounds__(256) void exhaustive_bwd_kernel(const float* __restrict__ D, const float* __restrict__ gloss,
-                                                              float* __restrict__ G, int B, int soft, float alpha, float margin) {
+                                                              float* __restrict__ G, int B, BaselineTerm term) {
     __shared__ float sh[4];
     const int a = blockIdx.x;
     const float daa = D[(size_t)a * B + a];
-    const float sc = gloss[0] / (2.f * B * (B - 1));
+    const float sc = term.scale(gloss[0], 2.f * B * (B - 1));
     float diag = 0.f;
     for (int j = threadIdx.x; j < B; j += 256) {
         if (j == a) continue;
         const float dab = D[(size_t)a * B + j];
-        const float t1 = trip_d(daa - dab, soft, alpha, margin);                       // anchor a in embed1, negative j
-        const float t2 = trip_d(D[(size_t)j * B + j] - dab, soft, alpha, margin);      // anchor j in embed2
+        const float t1 = term.deriv(daa - dab);                       // anchor a in embed1, negative j
+        const float t2 = term.deriv(D[(size_t)j * B + j] - dab);      // anchor j in embed2
         G[(size_t)a * B + j] = -(t1 + t2) * sc;
-        diag += t1 + trip_d(daa - D[(size_t)j * B + a], soft, alpha, margin);
+        diag += t1 + term.deriv(daa - D[(size_t)j * B + a]);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) diag += __shfl_xor(diag, d, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = diag;
-    __syncthreads();
-    if (threadIdx.x == 0) G[(size_t)a * B + a] = ((sh[0] + sh[1]) + (sh[2] + sh[3])) * sc;
+    const float tot = block_sum_256(diag, sh);
+    if (threadIdx.x == 0) G[(size_t)a * B + a] = tot * sc;
 }
 
 // D[a][b] = |e1_a - e2_b|^2: de1[a] = 2 * sum_b G[a][b] (e1_a - e2_b)   (side 0)
@@ -553,8 +520,9 @@ int witw_exhaustive_triplet_loss(const float* D, int B, int soft_margin, float a
     WITW_CHECK_ARG(D && loss && workspace, "exhaustive_triplet_loss: null pointer");
     WITW_CHECK_ARG(B >= 2, "exhaustive_triplet_loss: batch %d < 2", B);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(exhaustive_partials_kernel, dim3(B), dim3(256), 0, st, D, workspace, B, soft_margin, alpha, margin);
-    hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(256), 0, st, workspace, loss, B, 2.f * B * (B - 1));
+    hipLaunchKernelGGL(exhaustive_partials_kernel, dim3(B), dim3(256), 0, st, D, workspace, B,
+                       BaselineTerm{soft_margin, alpha, margin});
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(256), 0, st, workspace, loss, B, 2.f * B * (B - 1));
     WITW_CHECK_LAUNCH("exhaustive_triplet_loss");
     return WITW_OK;
 }
@@ -648,7 +616,8 @@ int witw_exhaustive_triplet_loss_bwd(const float* e1, const float* e2, const flo
     WITW_CHECK_ARG(e1 && e2 && D && grad_loss && de1 && de2 && workspace, "exhaustive_triplet_loss_bwd: null pointer");
     WITW_CHECK_ARG(B >= 2 && n > 0, "exhaustive_triplet_loss_bwd: bad shape");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(exhaustive_bwd_kernel, dim3(B), dim3(256), 0, st, D, grad_loss, workspace, B, soft_margin, alpha, margin);
+    hipLaunchKernelGGL(exhaustive_bwd_kernel, dim3(B), dim3(256), 0, st, D, grad_loss, workspace, B,
+                       BaselineTerm{soft_margin, alpha, margin});
     hipLaunchKernelGGL(sqdist_bwd_kernel, dim3(B), dim3(256), 0, st, e1, e2, workspace, de1, B, n, 0);
     hipLaunchKernelGGL(sqdist_bwd_kernel, dim3(B), dim3(256), 0, st, e1, e2, workspace, de2, B, n, 1);
     WITW_CHECK_LAUNCH("exhaustive_triplet_loss_bwd");

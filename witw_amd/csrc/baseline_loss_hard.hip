@@ -5,7 +5,8 @@
 //   x [B,n]  the all-gathered embeddings of one side, y [b,n] this rank's of the other, T[g][c] = |x_g - y_c|^2, column c = global
 //            column col0 + c, d_k = the global diagonal, Tm = T with the diagonal at +inf
 //   rv[i], ri[i] = min / argmin of global row i of Tm, cv[j], ci[j] = min / argmin of column j (global indices, constants for the gradient)
-//   l = trip, l' = trip_d (exhaustive_terms.h: the exhaustive kernels' own; a NaN argument stays a NaN in l)
+//   l, l' = BaselineTerm's hard_value and derivative (loss_terms.h: the exhaustive kernels' own; a NaN argument stays a NaN in l);
+//   the loss and pair-list kernels are hard_loss_kernel / hard_pairs_kernel of loss_kernels.h
 //
 //   partial = sum_c l(d_{col0+c} - rv[col0+c]) + l(d_{col0+c} - cv[c])                          (over the ranks: / 2B = the loss)
 //   sc = grad_loss / 2B,  w_r[i] = sc l'(d_i - rv_i),  w_c[j] = sc l'(d_j - cv_j)
@@ -14,75 +15,9 @@
 //
 // Every sum runs in a fixed order (a thread's strided partial, the wave shuffle tree, four wave totals; the pairs of an output row
 // in list order) and nothing is accumulated with atomics: the same call gives the same bits.
-#include "common.h"
-#include "exhaustive_terms.h"
+#include "loss_kernels.h"
 
 namespace {
-
-// fmaxf drops a NaN; a NaN embedding must show in the loss, as it does in max(x + margin, 0) of torch
-__device__ __forceinline__ float hard_term(float x, int soft, float alpha, float margin) {
-    return x != x ? x : trip(x, soft, alpha, margin);
-}
-
-// the row terms of the anchors col0 .. col0+b-1 and the column terms of the slab's columns. One workgroup.
-__global__ __launch_bounds__(256) void baseline_hard_loss_kernel(const float* __restrict__ T, const float* __restrict__ rv,
-                                                                  const float* __restrict__ cv, float* __restrict__ out, int b, int col0,
-                                                                  int soft, float alpha, float margin) {
-    __shared__ float sh[4];
-    float s = 0.f;
-    for (int j = threadIdx.x; j < b; j += 256) {
-        const int c = col0 + j;
-        const float d = T[(size_t)c * b + j];
-        s += hard_term(d - rv[c], soft, alpha, margin);
-        s += hard_term(d - cv[j], soft, alpha, margin);
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-// Pair list of the gradient restricted to the slab's columns, laid out as hard_pairs_kernel (loss_hard.hip) lays it out:
-//   [0, b)        (col0 + j, j)     +w_r[col0 + j] + w_c[j]     the diagonal of column j
-//   [b, 2b)       (ci[j], j)        -w_c[j]
-//   [2b, 2b+B)    (i, ri[i] - col0) -w_r[i] when the slab holds column ri[i], else (-1, -1, 0)
-__global__ __launch_bounds__(256) void baseline_hard_pairs_kernel(const float* __restrict__ diag, const float* __restrict__ rv,
-                                                                   const long long* __restrict__ ri, const float* __restrict__ cv,
-                                                                   const long long* __restrict__ ci, const float* __restrict__ gloss,
-                                                                   int* __restrict__ pg, int* __restrict__ pc, float* __restrict__ pw, int B,
-                                                                   int b, int col0, int soft, float alpha, float margin) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= 2 * b + B) return;
-    const float sc = gloss[0] / (2.f * B);
-    int g = -1, c = -1;
-    float w = 0.f;
-    if (t < b) {
-        const int k = col0 + t;
-        g = k;
-        c = t;
-        w = sc * trip_d(diag[k] - rv[k], soft, alpha, margin) + sc * trip_d(diag[k] - cv[t], soft, alpha, margin);
-    } else if (t < 2 * b) {
-        const int j = t - b;
-        const long long r = ci[j];
-        if (r >= 0 && r < B) {
-            g = (int)r;
-            c = j;
-            w = -(sc * trip_d(diag[col0 + j] - cv[j], soft, alpha, margin));
-        }
-    } else {
-        const int i = t - 2 * b;
-        const long long k = ri[i];
-        if (k >= col0 && k < col0 + b) {
-            g = i;
-            c = (int)(k - col0);
-            w = -(sc * trip_d(diag[i] - rv[i], soft, alpha, margin));
-        }
-    }
-    pg[t] = g;
-    pc[t] = c;
-    pw[t] = w;
-}
 
 // out[r][k] = 2 sum over the pairs of row r, in list order, of w (self[r][k] - other[q][k]). Workgroups [0, nx) own the rows of dx
 // (self = x, r = pair_g, q = pair_c), the others the rows of dy (self = y, r = pair_c, q = pair_g); blockIdx.y picks 256 columns k.
@@ -153,8 +88,8 @@ int witw_baseline_hard_slab_loss(const float* T, const float* rv, const float* c
     WITW_CHECK_ARG(T && rv && cv && partial, "baseline_hard_slab_loss: null pointer");
     WITW_CHECK_ARG(B >= 2, "baseline_hard_slab_loss: batch %d < 2 (every anchor needs a negative)", B);
     WITW_CHECK_ARG(slab_ok(B, b, col0), "baseline_hard_slab_loss: bad slab B=%d b=%d col0=%d", B, b, col0);
-    hipLaunchKernelGGL(baseline_hard_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, T, rv, cv, partial, b, col0, soft_margin,
-                       alpha, margin);
+    hipLaunchKernelGGL(hard_loss_kernel<BaselineTerm>, dim3(1), dim3(256), 0, (hipStream_t)stream, T, rv, cv, partial, b, col0,
+                       BaselineTerm{soft_margin, alpha, margin}, 1.f);
     WITW_CHECK_LAUNCH("baseline_hard_slab_loss");
     witw_note_variant("baseline_hard_loss_kernel");
     return WITW_OK;
@@ -166,8 +101,8 @@ int witw_baseline_hard_pairs(const float* diag, const float* rv, const long long
     WITW_CHECK_ARG(diag && rv && ri && cv && ci && grad_loss && pair_g && pair_c && pair_w, "baseline_hard_pairs: null pointer");
     WITW_CHECK_ARG(B >= 2, "baseline_hard_pairs: batch %d < 2 (every anchor needs a negative)", B);
     WITW_CHECK_ARG(slab_ok(B, b, col0), "baseline_hard_pairs: bad slab B=%d b=%d col0=%d", B, b, col0);
-    hipLaunchKernelGGL(baseline_hard_pairs_kernel, dim3(cdiv(2 * b + B, 256)), dim3(256), 0, (hipStream_t)stream, diag, rv, ri, cv, ci,
-                       grad_loss, pair_g, pair_c, pair_w, B, b, col0, soft_margin, alpha, margin);
+    hipLaunchKernelGGL(hard_pairs_kernel<BaselineTerm>, dim3(cdiv(2 * b + B, 256)), dim3(256), 0, (hipStream_t)stream, diag, rv, ri, cv,
+                       ci, grad_loss, pair_g, pair_c, pair_w, B, b, col0, BaselineTerm{soft_margin, alpha, margin});
     WITW_CHECK_LAUNCH("baseline_hard_pairs");
     witw_note_variant("baseline_hard_pairs_kernel");
     return WITW_OK;

@@ -5,7 +5,7 @@
 //   x [B,n]  the all-gathered embeddings of one side, y [b,n] this rank's embeddings of the other side, col0 = rank * b
 //   T [B,b]  T[g][c] = |x_g - y_c|^2 (witw_pairwise_sqdist); column c is column col0 + c of the global matrix
 //   diag [B] diag[k] = T_k[k][k - col0_k] of the rank that owns column k, all-gathered
-//   l = trip, l' = trip_d (exhaustive_terms.h: the dense kernels' own)
+//   l, l' = BaselineTerm's value and derivative (loss_terms.h: the dense kernels' own); the kernels are loss_kernels.h's
 //
 //   partial   = sum_c sum_{g != col0+c} l(diag[col0+c] - T[g][c]) + l(diag[g] - T[g][c])        (over the ranks: / 2B(B-1) = the loss)
 //   colsig[c] = sum_{g != col0+c} l'(diag[col0+c] - T[g][c])                                   (complete on this rank)
@@ -15,80 +15,9 @@
 //
 // Every sum runs in a fixed order (a thread's strided or serial partial, the wave shuffle tree, four wave totals) and nothing
 // is accumulated with atomics: the same call gives the same bits.
-#include "common.h"
-#include "exhaustive_terms.h"
+#include "loss_kernels.h"
 
 namespace {
-
-__device__ __forceinline__ float slab_block_sum(float v, float* sh) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-// part[g] = row g's share of `partial`; one block per row of the slab
-__global__ __launch_bounds__(256) void exhaustive_slab_partials_kernel(const float* __restrict__ T, const float* __restrict__ diag,
-                                                                        float* __restrict__ part, int b, int col0, int soft,
-                                                                        float alpha, float margin) {
-    __shared__ float sh[4];
-    const int g = blockIdx.x;
-    const float dgg = diag[g];
-    float s = 0.f;
-    for (int c = threadIdx.x; c < b; c += 256) {
-        if (col0 + c == g) continue;
-        const float t = T[(size_t)g * b + c];
-        s += trip(diag[col0 + c] - t, soft, alpha, margin);
-        s += trip(dgg - t, soft, alpha, margin);
-    }
-    const float tot = slab_block_sum(s, sh);
-    if (threadIdx.x == 0) part[g] = tot;
-}
-
-__global__ __launch_bounds__(256) void exhaustive_slab_sum_kernel(const float* __restrict__ part, float* __restrict__ out, int n) {
-    __shared__ float sh[4];
-    float s = 0.f;
-    for (int t = threadIdx.x; t < n; t += 256) s += part[t];
-    const float tot = slab_block_sum(s, sh);
-    if (threadIdx.x == 0) out[0] = tot;
-}
-
-// blocks [0,B): rowsig[g] over this slab's columns; blocks [B,B+b): colsig[c] over all rows
-__global__ __launch_bounds__(256) void exhaustive_slab_sig_kernel(const float* __restrict__ T, const float* __restrict__ diag,
-                                                                   float* __restrict__ rowsig, float* __restrict__ colsig, int B, int b,
-                                                                   int col0, int soft, float alpha, float margin) {
-    __shared__ float sh[4];
-    const bool is_col = blockIdx.x >= (unsigned)B;
-    const int m = is_col ? blockIdx.x - B : blockIdx.x;
-    const int own = is_col ? col0 + m : m;               // the global index whose diagonal entry is the positive distance
-    const float dm = diag[own];
-    const int cnt = is_col ? B : b;
-    float s = 0.f;
-    for (int t = threadIdx.x; t < cnt; t += 256) {
-        if ((is_col ? t : col0 + t) == own) continue;
-        const float d = is_col ? T[(size_t)t * b + m] : T[(size_t)m * b + t];
-        s += trip_d(dm - d, soft, alpha, margin);
-    }
-    const float tot = slab_block_sum(s, sh);
-    if (threadIdx.x == 0) (is_col ? colsig : rowsig)[m] = tot;
-}
-
-__global__ void exhaustive_slab_bwd_kernel(const float* __restrict__ T, const float* __restrict__ diag, const float* __restrict__ rowsig,
-                                           const float* __restrict__ colsig, const float* __restrict__ gloss, float* __restrict__ G, int B,
-                                           int b, int col0, int soft, float alpha, float margin) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)B * b) return;
-    const int g = idx / b, c = idx - (size_t)g * b;
-    const float sc = gloss[0] / (2.f * B * (B - 1));
-    if (g == col0 + c) {
-        G[idx] = (rowsig[g] + colsig[c]) * sc;
-        return;
-    }
-    const float t = T[idx];
-    G[idx] = -(trip_d(diag[col0 + c] - t, soft, alpha, margin) + trip_d(diag[g] - t, soft, alpha, margin)) * sc;
-}
 
 // out[r][k] = 2 sum_q Gm(r, q) (self[r][k] - other[q][k]), Gm(r, q) = G[r * g_row + q * g_other]: dx with (g_row, g_other) = (b, 1),
 // dy with (1, b). A workgroup owns R output rows x 256 columns k: a lane keeps its R sums and its R self values in registers, so
@@ -162,8 +91,9 @@ int witw_exhaustive_loss_slab_fwd(const float* T, const float* diag, int B, int 
     WITW_CHECK_ARG(T && diag && partial && workspace, "exhaustive_loss_slab_fwd: null pointer");
     WITW_CHECK_ARG(slab_ok(B, b, col0), "exhaustive_loss_slab_fwd: bad slab B=%d b=%d col0=%d", B, b, col0);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(exhaustive_slab_partials_kernel, dim3(B), dim3(256), 0, st, T, diag, workspace, b, col0, soft_margin, alpha, margin);
-    hipLaunchKernelGGL(exhaustive_slab_sum_kernel, dim3(1), dim3(256), 0, st, workspace, partial, B);
+    hipLaunchKernelGGL(slab_partials_kernel<BaselineTerm>, dim3(B), dim3(256), 0, st, T, diag, workspace, b, col0,
+                       BaselineTerm{soft_margin, alpha, margin});
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(256), 0, st, workspace, partial, B, 1.f);
     WITW_CHECK_LAUNCH("exhaustive_loss_slab_fwd");
     witw_note_variant("exhaustive_slab_partials_kernel");
     return WITW_OK;
@@ -173,8 +103,8 @@ int witw_exhaustive_loss_slab_sig(const float* T, const float* diag, int B, int 
                                   float* rowsig, float* colsig, void* stream) {
     WITW_CHECK_ARG(T && diag && rowsig && colsig, "exhaustive_loss_slab_sig: null pointer");
     WITW_CHECK_ARG(slab_ok(B, b, col0), "exhaustive_loss_slab_sig: bad slab B=%d b=%d col0=%d", B, b, col0);
-    hipLaunchKernelGGL(exhaustive_slab_sig_kernel, dim3(B + b), dim3(256), 0, (hipStream_t)stream, T, diag, rowsig, colsig, B, b, col0,
-                       soft_margin, alpha, margin);
+    hipLaunchKernelGGL(slab_sig_kernel<BaselineTerm>, dim3(B + b), dim3(256), 0, (hipStream_t)stream, T, diag, rowsig, colsig, B, b, col0,
+                       BaselineTerm{soft_margin, alpha, margin});
     WITW_CHECK_LAUNCH("exhaustive_loss_slab_sig");
     witw_note_variant("exhaustive_slab_sig_kernel");
     return WITW_OK;
@@ -185,8 +115,8 @@ int witw_exhaustive_loss_slab_bwd(const float* T, const float* diag, const float
     WITW_CHECK_ARG(T && diag && rowsig && colsig && grad_loss && G, "exhaustive_loss_slab_bwd: null pointer");
     WITW_CHECK_ARG(slab_ok(B, b, col0), "exhaustive_loss_slab_bwd: bad slab B=%d b=%d col0=%d", B, b, col0);
     const size_t total = (size_t)B * b;
-    hipLaunchKernelGGL(exhaustive_slab_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, T, diag, rowsig,
-                       colsig, grad_loss, G, B, b, col0, soft_margin, alpha, margin);
+    hipLaunchKernelGGL(slab_bwd_kernel<BaselineTerm>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, T, diag,
+                       rowsig, colsig, grad_loss, G, B, b, col0, BaselineTerm{soft_margin, alpha, margin});
     WITW_CHECK_LAUNCH("exhaustive_loss_slab_bwd");
     witw_note_variant("exhaustive_slab_bwd_kernel");
     return WITW_OK;

@@ -12,7 +12,7 @@
 //   +w_r[i] + w_c[i] at (i,i),  -w_r[i] at (i, ri[i]),  -w_c[j] at (ci[j], j),   w_r[i] = g a/(2B) sigmoid(a(d_i - rv_i)), w_c alike.
 // match_bwd_pairs turns such a pair list into the embedding gradients without a dense [Bo,Bs] gradient matrix.
 // Every reduction runs in a fixed order and nothing uses atomics: results are bitwise reproducible run to run.
-#include "common.h"
+#include "loss_kernels.h"
 
 namespace {
 
@@ -120,89 +120,27 @@ __global__ __launch_bounds__(256) void hard_merge_rows_kernel(const float* __res
     ri[i] = out_index(ix);
 }
 
-__device__ __forceinline__ float softplus_lit(float x) { return logf(1.f + expf(x)); }
-__device__ __forceinline__ float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+// The loss and the gradient's pair list from the mined minima are hard_loss_kernel<FovTerm> and hard_pairs_kernel<FovTerm>
+// (loss_kernels.h).
 
-// sum over the slab's columns j (global c = col0 + j, whose diagonal d_c = D[c][j] lies in the slab) of the row term of anchor c
-// and the column term of anchor j, divided by `norm` (1: the rank's partial; 2B: the loss of the full form). One workgroup.
-__global__ __launch_bounds__(256) void hard_loss_kernel(const float* __restrict__ D, const float* __restrict__ rv,
-                                                         const float* __restrict__ cv, float* __restrict__ out, int Bs, int col0,
-                                                         float alpha, float norm) {
-    __shared__ float sh[4];
-    float s = 0.f;
-    for (int j = threadIdx.x; j < Bs; j += 256) {
-        const int c = col0 + j;
-        const float d = D[(size_t)c * Bs + j];
-        s += softplus_lit(alpha * (d - rv[c]));
-        s += softplus_lit(alpha * (d - cv[j]));
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = ((sh[0] + sh[1]) + (sh[2] + sh[3])) / norm;
-}
-
-// Pair list of the gradient restricted to the slab's columns (s = local column). n = 2 Bs + B entries:
-//   [0, Bs)        (c, j)        +w_r[c] + w_c[j]      the diagonal of column j, c = col0 + j
-//   [Bs, 2Bs)      (ci[j], j)    -w_c[j]
-//   [2Bs, 2Bs+B)   (i, ri[i]-col0) -w_r[i] when the slab holds column ri[i], else (-1, -1, 0) (skipped by match_bwd_pairs)
-__global__ __launch_bounds__(256) void hard_pairs_kernel(const float* __restrict__ diag, const float* __restrict__ rv,
-                                                          const long long* __restrict__ ri, const float* __restrict__ cv,
-                                                          const long long* __restrict__ ci, const float* __restrict__ gloss,
-                                                          int* __restrict__ po, int* __restrict__ ps, float* __restrict__ pw, int B,
-                                                          int Bs, int col0, float alpha) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const int n = 2 * Bs + B;
-    if (t >= n) return;
-    const float sc = gloss[0] * alpha / (2.f * B);
-    int o = -1, s = -1;
-    float w = 0.f;
-    if (t < Bs) {
-        const int c = col0 + t;
-        o = c;
-        s = t;
-        w = sc * sigmoid(alpha * (diag[c] - rv[c])) + sc * sigmoid(alpha * (diag[c] - cv[t]));
-    } else if (t < 2 * Bs) {
-        const int j = t - Bs;
-        const long long r = ci[j];
-        if (r >= 0) {
-            o = (int)r;
-            s = j;
-            w = -(sc * sigmoid(alpha * (diag[col0 + j] - cv[j])));
-        }
-    } else {
-        const int i = t - 2 * Bs;
-        const long long c = ri[i];
-        if (c >= col0 && c < col0 + Bs) {
-            o = i;
-            s = (int)(c - col0);
-            w = -(sc * sigmoid(alpha * (diag[i] - rv[i])));
-        }
-    }
-    po[t] = o;
-    ps[t] = s;
-    pw[t] = w;
-}
-
-// Dense dL/dD of the full form (the stand-alone differentiable loss): the three kinds of non-zeros above, zero elsewhere.
+// Dense dL/dD of the full form (the stand-alone differentiable loss): the three kinds of non-zeros of the pair list, zero elsewhere.
 __global__ __launch_bounds__(256) void hard_bwd_dense_kernel(const float* __restrict__ D, const float* __restrict__ rv,
                                                               const long long* __restrict__ ri, const float* __restrict__ cv,
                                                               const long long* __restrict__ ci, const float* __restrict__ gloss,
-                                                              float* __restrict__ gD, int B, float alpha) {
+                                                              float* __restrict__ gD, int B, FovTerm term) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (size_t)B * B) return;
     const int i = (int)(idx / B), j = (int)(idx - (size_t)i * B);
-    const float sc = gloss[0] * alpha / (2.f * B);
+    const float sc = term.scale(gloss[0], 2.f * B);
     const bool on_row = ri[i] == j, on_col = ci[j] == i;
     float g = 0.f;
     if (i == j || on_row) {
-        const float wr = sc * sigmoid(alpha * (D[(size_t)i * B + i] - rv[i]));
+        const float wr = sc * term.deriv(D[(size_t)i * B + i] - rv[i]);
         if (i == j) g += wr;
         if (on_row) g -= wr;
     }
     if (i == j || on_col) {
-        const float wc = sc * sigmoid(alpha * (D[(size_t)j * B + j] - cv[j]));
+        const float wc = sc * term.deriv(D[(size_t)j * B + j] - cv[j]);
         if (i == j) g += wc;
         if (on_col) g -= wc;
     }
@@ -313,12 +251,7 @@ __global__ __launch_bounds__(256) void pairs_bwd_su_kernel(const float* __restri
                 if (tid + 256 * i < E) acc[i] += a * row[ch[i] * 64 + ((kk[i] + t) & 63)];
         }
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) self += __shfl_xor(self, m, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) part[tid >> 6] = self;
-    __syncthreads();
-    const float selfsum = (part[0] + part[1]) + (part[2] + part[3]);
+    const float selfsum = block_sum_256(self, part);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int e = tid + 256 * i;
@@ -413,7 +346,7 @@ int witw_batch_hard_fwd(const float* distance, int B, float alpha, float* rv, lo
     WITW_CHECK_ARG(B >= 2, "batch_hard_fwd: batch %d < 2 (every anchor needs a negative)", B);
     hipStream_t st = (hipStream_t)stream;
     launch_mine(distance, B, B, 0, rv, ri, cv, ci, workspace, st);
-    hipLaunchKernelGGL(hard_loss_kernel, dim3(1), dim3(256), 0, st, distance, rv, cv, loss, B, 0, alpha, 2.f * B);
+    hipLaunchKernelGGL(hard_loss_kernel<FovTerm>, dim3(1), dim3(256), 0, st, distance, rv, cv, loss, B, 0, FovTerm{alpha}, 2.f * B);
     WITW_CHECK_LAUNCH("batch_hard_fwd");
     return WITW_OK;
 }
@@ -444,7 +377,8 @@ int witw_batch_hard_slab_loss(const float* distance, const float* rv, const floa
     WITW_CHECK_ARG(distance && rv && cv && partial, "batch_hard_slab_loss: null pointer");
     WITW_CHECK_ARG(Bo >= 2, "batch_hard_slab_loss: batch %d < 2", Bo);
     WITW_CHECK_ARG(Bs >= 1 && col0 >= 0 && col0 + Bs <= Bo, "batch_hard_slab_loss: bad slab Bo=%d Bs=%d col0=%d", Bo, Bs, col0);
-    hipLaunchKernelGGL(hard_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, distance, rv, cv, partial, Bs, col0, alpha, 1.f);
+    hipLaunchKernelGGL(hard_loss_kernel<FovTerm>, dim3(1), dim3(256), 0, (hipStream_t)stream, distance, rv, cv, partial, Bs, col0,
+                       FovTerm{alpha}, 1.f);
     WITW_CHECK_LAUNCH("batch_hard_slab_loss");
     return WITW_OK;
 }
@@ -455,8 +389,8 @@ int witw_batch_hard_pairs(const float* diag, const float* rv, const long long* r
     WITW_CHECK_ARG(diag && rv && ri && cv && ci && grad_loss && pair_o && pair_s && pair_w, "batch_hard_pairs: null pointer");
     WITW_CHECK_ARG(B >= 2, "batch_hard_pairs: batch %d < 2", B);
     WITW_CHECK_ARG(Bs >= 1 && col0 >= 0 && col0 + Bs <= B, "batch_hard_pairs: bad slab B=%d Bs=%d col0=%d", B, Bs, col0);
-    hipLaunchKernelGGL(hard_pairs_kernel, dim3(cdiv(2 * Bs + B, 256)), dim3(256), 0, (hipStream_t)stream, diag, rv, ri, cv, ci,
-                       grad_loss, pair_o, pair_s, pair_w, B, Bs, col0, alpha);
+    hipLaunchKernelGGL(hard_pairs_kernel<FovTerm>, dim3(cdiv(2 * Bs + B, 256)), dim3(256), 0, (hipStream_t)stream, diag, rv, ri, cv, ci,
+                       grad_loss, pair_o, pair_s, pair_w, B, Bs, col0, FovTerm{alpha});
     WITW_CHECK_LAUNCH("batch_hard_pairs");
     return WITW_OK;
 }
@@ -468,7 +402,7 @@ int witw_batch_hard_bwd(const float* distance, const float* rv, const long long*
     const size_t total = (size_t)B * B;
     WITW_CHECK_ARG((total + 255) / 256 <= 0x7fffffffULL, "batch_hard_bwd: B=%d too large", B);
     hipLaunchKernelGGL(hard_bwd_dense_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, distance, rv,
-                       ri, cv, ci, grad_loss, grad_distance, B, alpha);
+                       ri, cv, ci, grad_loss, grad_distance, B, FovTerm{alpha});
     WITW_CHECK_LAUNCH("batch_hard_bwd");
     return WITW_OK;
 }

@@ -233,7 +233,7 @@ class FOV_DSM(torch.nn.Module):
 
     def _draw_scales(self, x, dropout_scales):
         """Dropout2d(p=0.2) scales of this call (whole channels, 1/(1-p) on the kept ones; reference :241,288): injected, or
-        drawn by the counter-based generator of csrc/loss.hip from (seed, encoder, step, rank, layer, sample, channel) in one
+        drawn by the counter-based generator of csrc/dropout2d.hip from (seed, encoder, step, rank, layer, sample, channel) in one
         launch. seed = self.dropout_seed, else torch.initial_seed() (so torch.manual_seed still names the run); the step
         counter advances per training call."""
         layers = [idx for (idx, sh, relu, pool, drop) in self.layer_specs if drop]

@@ -925,7 +925,7 @@ def rank_count_thresh(distance, threshold):
 
 
 def dropout2d_scales(seed, encoder, step, rank, layers, batch, channels, p, device):
-    """Dropout2d scales [len(layers), batch, channels] (0 or 1/(1-p)) from the counter-based generator of csrc/loss.hip."""
+    """Dropout2d scales [len(layers), batch, channels] (0 or 1/(1-p)) from the counter-based generator of csrc/dropout2d.hip."""
     import ctypes
     lib = _lib.load()
     out = torch.empty((len(layers), batch, channels), dtype=torch.float32, device=device)
