@@ -739,6 +739,18 @@ int witw_bilinear_gather(const float* x, const int* taps, const float* wts, floa
  * CHW tensor = nearest-neighbour affine grid sample, zero fill, same size). x,y [B,C,H,W] fp32, y != x; theta DEVICE
  * fp32 [B][3][2]: per image the inverse rotation matrix divided by (W/2, H/2), row k = (x, y, 1) coefficient. */
 int witw_rotate_nearest(const float* x, const float* theta, float* y, int B, int C, int H, int W, void* stream);
+/* cvig_baseline's Compose[SyncedRotation, SurfaceResize] (model/cvig_baseline.py:324-328) for a BATCH straight from the decoder's
+ * bytes, one launch per side. desc: the DEVICE table of witw_resize_bilinear_normalize_batched ([B][5] 64-bit words {address, H,
+ * W, start, channels stored per pixel}; kind 0 = float32 planar CHW, 1 = uint8 interleaved HWC; the first C stored channels
+ * are used, 1 <= C <= 8). y: fp32 [B,C,.,.] NCHW, values 0..255. A table row that does not fit the launch (see below) gives a
+ * zero image; no row is read outside its own H x W x channels.
+ * witw_baseline_rotate_batched: witw_rotate_nearest of every image (all H x W, theta as there: DEVICE fp32 [B][3][2]), bit for
+ * bit what witw_rotate_nearest gives on the image converted to float CHW. y [B,C,H,W]. A row fits when its H, W are the launch's.
+ * witw_baseline_roll_rows_batched: y[b][c][oy][ox] = image_b[c][oy / rep][(ox + start_b) mod W_b], y [B,C,Ho,Wo]: the left roll
+ * of horizontal_shift (:97-113) and, at rep = 2, SurfaceResize('cvusa')'s repeat_interleave(2, -2) (:214) in one exact copy.
+ * Ho must be a multiple of rep; a row fits when H_b == Ho / rep, W_b == Wo and 0 <= start_b < W_b. */
+int witw_baseline_rotate_batched(const void* desc, const float* theta, float* y, int B, int C, int H, int W, int kind, void* stream);
+int witw_baseline_roll_rows_batched(const void* desc, float* y, int B, int C, int Ho, int Wo, int rep, int kind, void* stream);
 
 /* Conv2d(k=4, s=2) filter [co][ci][4][4] <-> the 3x3 filter over space-to-depth(2) channels [co][cpad][3][3] the taps4 kernels take
  * (model/cvig_baseline.py:236-252; tap row 0 / column 0 zero, channel (dy*2+dx)*ci + c); the second call is the inverse gather for

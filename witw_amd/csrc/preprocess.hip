@@ -9,6 +9,7 @@
 // Compiled with -ffp-contract=off so products and sums round exactly like the reference's
 // separate elementwise torch ops (polar: wa*Ia + wb*Ib + wc*Ic + wd*Id, left to right).
 #include "common.h"
+#include "rotate_coord.h"
 #include <stdlib.h>
 #include <type_traits>
 #include <string.h>
@@ -490,14 +491,9 @@ __global__ void rotate_nearest_kernel(const float* __restrict__ x, const float* 
     size_t t = idx / W;
     const int oy = t % H;
     const int b = (int)(t / H);
-    const float* th = theta + (size_t)b * 6;
-    const float xg = (float)ox + (0.5f - 0.5f * (float)W), yg = (float)oy + (0.5f - 0.5f * (float)H);
-    const float gx = __fmaf_rn(yg, th[2], xg * th[0]) + th[4];
-    const float gy = __fmaf_rn(yg, th[3], xg * th[1]) + th[5];
-    const float fx = ((gx + 1.f) * (float)W - 1.f) / 2.f, fy = ((gy + 1.f) * (float)H - 1.f) / 2.f;
-    const float rx = nearbyintf(fx), ry = nearbyintf(fy);
-    const bool ok = rx >= 0.f && rx <= (float)(W - 1) && ry >= 0.f && ry <= (float)(H - 1);
-    const size_t src = ok ? (size_t)(int)ry * W + (int)rx : 0;
+    int sx, sy;
+    const bool ok = witw_rotate_source(theta + (size_t)b * 6, ox, oy, H, W, sx, sy);
+    const size_t src = (size_t)sy * W + sx;
     for (int c = 0; c < C; ++c) {
         const size_t plane = ((size_t)b * C + c) * H * W;
         y[plane + (size_t)oy * W + ox] = ok ? x[plane + src] : 0.f;

@@ -34,10 +34,18 @@ class Globals:
 
     train_precision = 'fp32'  # arithmetic of the training step: 'fp32', or 'bf16' (forward, data and weight gradient of blocks 2-4 on the bf16 MFMA)
     sync_bn = False           # training on N ranks: BatchNorm statistics of the global batch (True) or of every rank's own share (False, nn.DataParallel)
+    # not in the reference: how train() / test() bring images to the encoders. 'reference' = workers decode into float32 CHW tensors,
+    # GpuPreprocess turns them sample by sample; 'packed' = the data path of cvig_fov: workers only parse / entropy-decode, each side
+    # of a batch crosses PCIe as one byte block, the GPU finishes the decode and GpuPreprocess runs two launches per batch (same bits)
+    data_path = 'reference'
+    device_jpeg = True        # 'packed': as cvig_fov.Globals.device_jpeg / jpeg_progressive / jpeg_440
+    jpeg_progressive = None
+    jpeg_440 = None
 
 
 PRECISIONS = ('fp32', 'bf16', 'bf16_all')
 TRAIN_PRECISIONS = ('fp32', 'bf16')
+DATA_PATHS = ('reference', 'packed')
 
 
 # how many units make one full turn of the panorama, per first letter of the unit name; None: the shift already is in pixels
@@ -114,21 +122,114 @@ class QuantizedSyncedRotation(object):
         return data
 
 
-class GpuPreprocess(object):
+class GpuPreprocess(_fov.GpuPreprocess):
     """Compose[SyncedRotation, SurfaceResize] (model/cvig_baseline.py:324-328) over a batch of raw images, on the
-    GPU: -> {'surface' [B,3,Hs,Ws], 'overhead' [B,3,Ho,Wo]} (values stay 0..255, the encoders rescale)."""
+    GPU: -> {'surface' [B,3,Hs,Ws], 'overhead' [B,3,Ho,Wo]} (values stay 0..255, the encoders rescale).
+    A collate_raw batch of tensors takes the reference's route sample by sample (SyncedRotation, SurfaceResize: 2-3 launches and a
+    copy per sample). Everything else -- a collate_packed batch (ring-backed or not) or a list of such parts, raw lists of uint8 HWC
+    arrays / JpegCoef / JpegFile objects, a StagedBatch -- is staged as cvig_fov.GpuPreprocess stages it (one copy per side, the
+    device JPEG decode, descriptor tables) and preprocessed in TWO launches whatever the batch size: baseline_data.roll_rows_batched
+    (cvusa: roll + row doubling) or ops.resize_batched (witw: 500 x 500) on the surface side, baseline_data.rotate_batched on the
+    overhead side. Both routes give the same bits for the same angles. One angle per sample, in sample order, from
+    torch.rand(()).item() * 360. (what SyncedRotation draws), or `angles`."""
 
-    def __init__(self, dataset):
+    def __init__(self, dataset, device=None, ring=None):
+        # cvig_fov.GpuPreprocess.__init__ is NOT run (its Resize / ImageNormalization / PolarTransform are cvig_fov's model). What is
+        # inherited is its staging -- stage(), _copy_side, _table_side, _stage_side -- which reads only `channels`, `ring`, _dev() and
+        # _stage_tail() of the object: a base-class stage() that starts to read anything else must be given it here
+        self.dataset = dataset
         self.rotation = SyncedRotation(dataset)
         self.resize = SurfaceResize(dataset)
+        self.panorama = Globals.path_formats[dataset]['panorama']
+        self.device = device      # where host images go; None = cvig_baseline.device
+        self.ring = ring          # ring.PinnedRing the loader's collate_packed builds its batch blocks in (None: ordinary blocks)
 
-    def __call__(self, batch):
+    def _dev(self):      # as the base class, with THIS module's default device
+        dev = self.device if self.device is not None else device
+        if dev.type != 'cuda':
+            raise _lib.WitwError('no gfx950 device: the WITW transforms run on the GPU only')
+        return dev
+
+    @staticmethod
+    def _one_size(tab, what):
+        """(H, W) shared by every row of a host table, else a WitwError naming two sizes that differ"""
+        hw = tab[:, 1:3]
+        odd = (hw != hw[0]).any(dim=1).nonzero()
+        if odd.numel():
+            h, w = hw[int(odd[0])].tolist()
+            raise _lib.WitwError('the %s images of a batch differ in size: %dx%d and %dx%d' % (what, int(hw[0, 0]), int(hw[0, 1]), h, w))
+        return int(hw[0, 0]), int(hw[0, 1])
+
+    def _stage_tail(self, st, s_tab, o_tab, angles):
+        """the rotation angles of the batch: theta of the overhead side, the roll starts of a panoramic surface side (column 3)"""
+        from . import baseline_data
+        s_tab = s_tab.cpu() if s_tab.is_cuda else s_tab
+        o_tab = o_tab.cpu() if o_tab.is_cuda else o_tab
+        few = int(min(s_tab[:, 4].min(), o_tab[:, 4].min()))
+        if few < self.channels:
+            raise _lib.WitwError('an image of the batch has %d channels, the model takes %d' % (few, self.channels))
+        if angles is None:
+            angles = [torch.rand(()).item() * 360. for _ in range(st.n)]
+        angles = [float(a) for a in angles]
+        if len(angles) != st.n:
+            raise _lib.WitwError('GpuPreprocess: %d angles for a batch of %d' % (len(angles), st.n))
+        st.angles = angles
+        st.o_size = self._one_size(o_tab, 'overhead')
+        st.s_size = None
+        if self.panorama:
+            st.s_size = self._one_size(s_tab, 'surface')
+            s_tab[:, 3] = torch.tensor([baseline_data.roll_start(a, st.s_size[1]) for a in angles], dtype=torch.int64)
+        theta = ops.rotation_theta(angles, *st.o_size).reshape(st.n, 6)
+        st.theta = theta.pin_memory().to(self._dev(), non_blocking=True)
+        st.keep.append(st.theta)
+        return s_tab, o_tab
+
+    def stage(self, batch, angles=None):
+        """cvig_fov.GpuPreprocess.stage plus the draws of _stage_tail; an empty collate_raw batch (a rank's empty share) gives a
+        StagedBatch with n == 0. A StagedBatch comes back as it is: its angles were drawn when it was staged, so `angles` with one
+        is refused"""
+        if isinstance(batch, _fov.StagedBatch):
+            if angles is not None:
+                raise _lib.WitwError('GpuPreprocess: a StagedBatch carries the angles it was staged with; pass `angles` to stage()')
+            return batch
+        if isinstance(batch, dict) and not batch.get('packed') and not batch['surface']:
+            return _fov.StagedBatch()
+        return _fov.GpuPreprocess.stage(self, batch, angles)
+
+    def _per_sample(self, batch, angles):
         s, o = [], []
-        for su, ov in zip(batch['surface'], batch['overhead']):
-            d = self.resize(self.rotation({'surface': _on_device(su[:3]), 'overhead': ov[:3]}))
+        for i, (su, ov) in enumerate(zip(batch['surface'], batch['overhead'])):
+            data = {'surface': _on_device(su[:3]), 'overhead': ov[:3]}
+            d = self.resize(self.rotation(data) if angles is None else self.rotation(data, angles[i]))
             s.append(d['surface'])
             o.append(d['overhead'])
         return {'surface': torch.stack(s), 'overhead': torch.stack(o)}
+
+    def __call__(self, batch, angles=None):
+        from . import baseline_data
+        if isinstance(batch, dict) and not batch.get('packed') and all(isinstance(t, torch.Tensor) for t in batch['surface'] + batch['overhead']):
+            return self._per_sample(batch, angles)
+        st = self.stage(batch, angles)
+        if st.n == 0:
+            raise _lib.WitwError('GpuPreprocess: an empty batch')
+        st.wait()
+        c = self.channels
+        if self.dataset == 'cvusa':
+            surface = baseline_data.roll_rows_batched(st.s_desc, st.n, c, (2 * st.s_size[0], st.s_size[1]), rep=2, kind=st.s_kind)
+        elif self.dataset == 'witw':
+            surface = ops.resize_batched(st.s_desc, st.n, c, (500, 500), kind=st.s_kind)
+        else:
+            raise Exception('! Invalid dataset type in ' + type(self).__name__ + '().')
+        overhead = baseline_data.rotate_batched(st.o_desc, None, st.n, c, st.o_size, kind=st.o_kind, theta=st.theta)
+        return {'surface': surface, 'overhead': overhead}
+
+
+def collate_packed(samples, ring=None):
+    """cvig_fov.collate_packed for the 'packed' data path; an empty sample list (GlobalBatchShares: more ranks than rows) stays
+    collate_raw's empty batch, which _embed_share and GpuPreprocess.stage know"""
+    if not samples:
+        return {'surface': [], 'overhead': []}
+    return _fov.collate_packed(samples, ring)
 
 
 class SurfaceResize(object):
@@ -806,7 +907,7 @@ class GlobalBatchShares(object):
 
 def _embed_share(prep, surface_encoder, overhead_encoder, raw):
     """eval-mode embeddings of this rank's share of a batch; an empty share gives [0, 1536] tensors"""
-    if not raw['surface']:
+    if (raw.n == 0) if isinstance(raw, _fov.StagedBatch) else (not raw.get('packed') and not raw['surface']):
         return torch.zeros((0, 1536), dtype=torch.float32, device=device), torch.zeros((0, 1536), dtype=torch.float32, device=device)
     data = prep(raw)
     with torch.no_grad():
@@ -817,8 +918,35 @@ def _bn_modules(*encoders):
     return [getattr(e, 'bn%d' % i) for e in encoders for i in range(1, 8)]
 
 
+def _data_path(who, data_path):
+    data_path = Globals.data_path if data_path is None else data_path
+    if data_path not in DATA_PATHS:
+        raise _lib.WitwError("%s: data_path must be 'reference' or 'packed', got %r" % (who, data_path))
+    return data_path
+
+
+def _open_dataset(dataset, csv_path, packed):
+    """'reference': the reference's float32 CHW tensors; 'packed': entropy-decoded JPEG files (Globals.device_jpeg) or the decoder's bytes"""
+    if not packed:
+        return ImagePairDataset(dataset=dataset, csv_path=csv_path)
+    return ImagePairDataset(dataset=dataset, csv_path=csv_path, raw='jpeg' if Globals.device_jpeg else True,
+                            jpeg_progressive=Globals.jpeg_progressive, jpeg_440=Globals.jpeg_440)
+
+
+def _staging(dataset, data_set, loader_batch, num_workers, packed, n_loaders=1):
+    """-> (GpuPreprocess, the DataLoaders' collate / pinning keywords, feed: loader -> what the driver iterates). 'packed': batches
+    are built by collate_packed, in a pinned ring when there are workers (cvig_fov.make_staging), and staged one batch ahead on a
+    copy stream (cvig_fov.DevicePrefetcher)"""
+    if not packed:
+        return GpuPreprocess(dataset), {'collate_fn': _fov.collate_raw}, lambda loader: loader
+    import functools
+    ring, _collate, pin = _fov.make_staging(data_set, loader_batch, num_workers, n_loaders=n_loaders)
+    prep = GpuPreprocess(dataset, device=device, ring=ring)
+    return prep, {'collate_fn': functools.partial(collate_packed, ring=ring), 'pin_memory': pin}, lambda loader: _fov.DevicePrefetcher(loader, prep)
+
+
 def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_epochs=999999, csv_path=None, seed=0, loss='exhaustive',
-          train_precision=None, sync_bn=None):
+          train_precision=None, sync_bn=None, data_path=None):
     """model/cvig_baseline.py:318-404 on the HIP kernels: same flow, prints and checkpoint names; Adam with torch's
     defaults (lr 1e-3) over every encoder parameter.
     Under an initialised process group (N ranks, one per GPU) it is the reference's nn.DataParallel run (:339-343) with a rank in
@@ -836,7 +964,8 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
     True = the BatchNorm layers of the training step normalise with the statistics of the GLOBAL batch instead (SurfaceEncoder(sync_bn=True):
     two all-reduces of 2C floats per layer and direction), so that the N-rank step is the one-process step at the same batch_size; the
     running statistics are then the same on every rank and "rank 0's are kept" holds trivially. On one rank it changes the summation
-    order only."""
+    order only. data_path: None = Globals.data_path; 'reference', or 'packed' = the loaders hand over packed byte blocks (device JPEG decode,
+    pinned ring, DevicePrefetcher one batch ahead) and GpuPreprocess runs two launches per batch; the same images for the same torch seed."""
     import pathlib
     import time
     from . import parallel
@@ -846,6 +975,7 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
     if train_precision not in TRAIN_PRECISIONS:
         raise _lib.WitwError("train: train_precision must be 'fp32' or 'bf16', got %r" % (train_precision,))
     sync_bn = bool(Globals.sync_bn if sync_bn is None else sync_bn)
+    packed = _data_path('train', data_path) == 'packed'
     world, rank = parallel.world(), parallel.rank()
     if world > 1 and batch_size % world:
         raise _lib.WitwError('train: the global batch_size %d is not a multiple of the %d ranks' % (batch_size, world))
@@ -853,89 +983,95 @@ def train(dataset='cvusa', val_quantity=1000, batch_size=16, num_workers=4, num_
         torch.cuda.set_device(device)
     pathlib.Path('./weights').mkdir(parents=True, exist_ok=True)
     csv_path = csv_path or Globals.dataset_paths[dataset]['train']
-    prep = GpuPreprocess(dataset)
-    trainval_set = ImagePairDataset(dataset=dataset, csv_path=csv_path)
-    split_gen = torch.Generator().manual_seed(seed) if world > 1 else None      # every rank must draw the same split
-    train_set, val_set = torch.utils.data.random_split(trainval_set, [len(trainval_set) - val_quantity, val_quantity],
-                                                       generator=split_gen)
-    if world > 1:
-        train_sampler = torch.utils.data.distributed.DistributedSampler(train_set, shuffle=True, drop_last=True)
-        train_loader = torch.utils.data.DataLoader(train_set, batch_size=batch_size // world, sampler=train_sampler, drop_last=True,
-                                                   num_workers=num_workers, collate_fn=_fov.collate_raw)
-        val_loader = torch.utils.data.DataLoader(val_set, batch_sampler=GlobalBatchShares(len(val_set), batch_size, rank, world),
-                                                 num_workers=num_workers, collate_fn=_fov.collate_raw)
-    else:
-        train_sampler = None
-        train_loader = torch.utils.data.DataLoader(train_set, batch_size=batch_size, shuffle=True, drop_last=True,
-                                                   num_workers=num_workers, collate_fn=_fov.collate_raw)
-        val_loader = torch.utils.data.DataLoader(val_set, batch_size=batch_size, shuffle=False, drop_last=False,
-                                                 num_workers=num_workers, collate_fn=_fov.collate_raw)
-    enc_kw = {'precision': 'bf16', 'train_precision': 'bf16'} if train_precision == 'bf16' else {'train_precision': 'fp32'}
-    enc_kw['sync_bn'] = sync_bn
-    surface_encoder = SurfaceEncoder(**enc_kw).to(device)
-    overhead_encoder = OverheadEncoder(**enc_kw).to(device)
-    encoders = [surface_encoder, overhead_encoder]
-    parallel.broadcast_parameters(encoders)
-    dense_loss, sharded_loss = {'exhaustive': (exhaustive_minibatch_triplet_loss, sharded_exhaustive_loss),
-                                'batch_hard': (batch_hard_triplet_loss, sharded_batch_hard_loss)}[loss]
-    loss_func = sharded_loss if world > 1 else dense_loss
-    optimizer = Adam(list(surface_encoder.parameters()) + list(overhead_encoder.parameters()))
-    reducer = parallel.OverlappedGradReducer(encoders) if world > 1 else None      # SUM: the loss is normalised by the global batch
+    trainval_set = _open_dataset(dataset, csv_path, packed)
+    prep, loader_kw, feed = _staging(dataset, trainval_set, -(-batch_size // world), num_workers, packed, n_loaders=2)
+    train_loader = val_loader = loader = None
+    try:
+        split_gen = torch.Generator().manual_seed(seed) if world > 1 else None      # every rank must draw the same split
+        train_set, val_set = torch.utils.data.random_split(trainval_set, [len(trainval_set) - val_quantity, val_quantity],
+                                                           generator=split_gen)
+        if world > 1:
+            train_sampler = torch.utils.data.distributed.DistributedSampler(train_set, shuffle=True, drop_last=True)
+            train_loader = torch.utils.data.DataLoader(train_set, batch_size=batch_size // world, sampler=train_sampler, drop_last=True,
+                                                       num_workers=num_workers, **loader_kw)
+            val_loader = torch.utils.data.DataLoader(val_set, batch_sampler=GlobalBatchShares(len(val_set), batch_size, rank, world),
+                                                     num_workers=num_workers, **loader_kw)
+        else:
+            train_sampler = None
+            train_loader = torch.utils.data.DataLoader(train_set, batch_size=batch_size, shuffle=True, drop_last=True,
+                                                       num_workers=num_workers, **loader_kw)
+            val_loader = torch.utils.data.DataLoader(val_set, batch_size=batch_size, shuffle=False, drop_last=False,
+                                                     num_workers=num_workers, **loader_kw)
+        enc_kw = {'precision': 'bf16', 'train_precision': 'bf16'} if train_precision == 'bf16' else {'train_precision': 'fp32'}
+        enc_kw['sync_bn'] = sync_bn
+        surface_encoder = SurfaceEncoder(**enc_kw).to(device)
+        overhead_encoder = OverheadEncoder(**enc_kw).to(device)
+        encoders = [surface_encoder, overhead_encoder]
+        parallel.broadcast_parameters(encoders)
+        dense_loss, sharded_loss = {'exhaustive': (exhaustive_minibatch_triplet_loss, sharded_exhaustive_loss),
+                                    'batch_hard': (batch_hard_triplet_loss, sharded_batch_hard_loss)}[loss]
+        loss_func = sharded_loss if world > 1 else dense_loss
+        optimizer = Adam(list(surface_encoder.parameters()) + list(overhead_encoder.parameters()))
+        reducer = parallel.OverlappedGradReducer(encoders) if world > 1 else None      # SUM: the loss is normalised by the global batch
 
-    def say(*a):
-        if rank == 0:
-            print(*a)
+        def say(*a):
+            if rank == 0:
+                print(*a)
 
-    best_loss = None
-    for epoch in range(num_epochs):
-        say('Epoch %d, %s' % (epoch + 1, time.ctime(time.time())))
-        if train_sampler is not None:
-            train_sampler.set_epoch(epoch)
-        for phase in ['train', 'val']:
-            running_count = 0
-            running_loss = 0.
-            loader = train_loader if phase == 'train' else val_loader
-            surface_encoder.train(phase == 'train')
-            overhead_encoder.train(phase == 'train')
-            if phase == 'val':
-                parallel.broadcast_buffers(_bn_modules(*encoders))      # the first replica's running statistics
-            for batch, raw in enumerate(loader):
-                if phase == 'val' and world > 1:
-                    su, ov = _embed_share(prep, surface_encoder, overhead_encoder, raw)
-                    surface_embed, overhead_embed = parallel.all_gather_ragged(su), parallel.all_gather_ragged(ov)
-                    with torch.no_grad():
-                        loss = dense_loss(surface_embed, overhead_embed)
-                    count = surface_embed.size(0)
-                else:
-                    data = prep(raw)
-                    with torch.set_grad_enabled(phase == 'train'):
-                        surface_embed = surface_encoder(data['surface'])
-                        overhead_embed = overhead_encoder(data['overhead'])
-                        loss = loss_func(surface_embed, overhead_embed)
-                        if phase == 'train':
-                            optimizer.zero_grad()
-                            loss.backward()
-                            if reducer is not None:
-                                reducer.wait()
-                            optimizer.step()
-                    count = surface_embed.size(0) * (world if phase == 'train' else 1)
-                running_count += count
-                running_loss += loss.item() * count
-                say('epoch = {} {}, iter = {}, count = {}, loss = {:.4f}'.format(epoch + 1, phase, batch, running_count,
-                                                                                loss.item()))
-            say('  %5s: avg loss = %f' % (phase, running_loss / max(1, running_count)))
-        if running_count and (best_loss is None or running_loss / running_count < best_loss):
-            say('-------> new best')
-            best_loss = running_loss / running_count
-            if rank == 0:      # the running statistics are rank 0's own: nothing has trained since the broadcast before validation
-                torch.save(surface_encoder.state_dict(), './weights/surface_best.pth')
-                torch.save(overhead_encoder.state_dict(), './weights/overhead_best.pth')
-    if reducer is not None:
-        reducer.close()
-    return best_loss
+        best_loss = None
+        for epoch in range(num_epochs):
+            say('Epoch %d, %s' % (epoch + 1, time.ctime(time.time())))
+            if train_sampler is not None:
+                train_sampler.set_epoch(epoch)
+            for phase in ['train', 'val']:
+                running_count = 0
+                running_loss = 0.
+                loader = train_loader if phase == 'train' else val_loader
+                surface_encoder.train(phase == 'train')
+                overhead_encoder.train(phase == 'train')
+                if phase == 'val':
+                    parallel.broadcast_buffers(_bn_modules(*encoders))      # the first replica's running statistics
+                for batch, raw in enumerate(feed(loader)):
+                    if phase == 'val' and world > 1:
+                        su, ov = _embed_share(prep, surface_encoder, overhead_encoder, raw)
+                        surface_embed, overhead_embed = parallel.all_gather_ragged(su), parallel.all_gather_ragged(ov)
+                        with torch.no_grad():
+                            loss = dense_loss(surface_embed, overhead_embed)
+                        count = surface_embed.size(0)
+                    else:
+                        data = prep(raw)
+                        with torch.set_grad_enabled(phase == 'train'):
+                            surface_embed = surface_encoder(data['surface'])
+                            overhead_embed = overhead_encoder(data['overhead'])
+                            loss = loss_func(surface_embed, overhead_embed)
+                            if phase == 'train':
+                                optimizer.zero_grad()
+                                loss.backward()
+                                if reducer is not None:
+                                    reducer.wait()
+                                optimizer.step()
+                        count = surface_embed.size(0) * (world if phase == 'train' else 1)
+                    running_count += count
+                    running_loss += loss.item() * count
+                    say('epoch = {} {}, iter = {}, count = {}, loss = {:.4f}'.format(epoch + 1, phase, batch, running_count,
+                                                                                    loss.item()))
+                say('  %5s: avg loss = %f' % (phase, running_loss / max(1, running_count)))
+            if running_count and (best_loss is None or running_loss / running_count < best_loss):
+                say('-------> new best')
+                best_loss = running_loss / running_count
+                if rank == 0:      # the running statistics are rank 0's own: nothing has trained since the broadcast before validation
+                    torch.save(surface_encoder.state_dict(), './weights/surface_best.pth')
+                    torch.save(overhead_encoder.state_dict(), './weights/overhead_best.pth')
+        if reducer is not None:
+            reducer.close()
+        return best_loss
+    finally:
+        if prep.ring is not None:      # also when the loop raises: the workers go before the ring they build their batches in
+            train_loader = val_loader = loader = None
+            prep.ring.close()
 
 
-def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_method=None, precision=None):
+def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_method=None, precision=None, data_path=None):
     """model/cvig_baseline.py:405-475: embed the test set (SyncedRotation stays on, as in the reference :410-414),
     rank every query against the whole gallery on the GPU, print the recall table. match_method: None = ranks() (one dense
     matrix, at most 65,535 pairs); 'direct', 'gemm' or 'auto' = evaluation_ranks(method=...): the same ranks from the chunked
@@ -943,29 +1079,36 @@ def test(dataset='cvusa', batch_size=16, num_workers=4, csv_path=None, match_met
     Globals.precision), see SurfaceEncoder.
     Under an initialised process group every rank embeds a contiguous share of the test set and keeps its gallery rows; the
     queries are gathered and the rank counts summed inside evaluation_ranks, rank 0 prints. None then means 'auto': the dense
-    ranks() cannot be sharded."""
+    ranks() cannot be sharded. data_path: as in train()."""
     from . import parallel
+    packed = _data_path('test', data_path) == 'packed'
     world, rank = parallel.world(), parallel.rank()
     if world > 1 and device.type == 'cuda':
         torch.cuda.set_device(device)
     csv_path = csv_path or Globals.dataset_paths[dataset]['test']
-    prep = GpuPreprocess(dataset)
-    test_set = ImagePairDataset(dataset=dataset, csv_path=csv_path)
-    shard_begin, shard_end = parallel.shard_range(len(test_set))
-    shard = torch.utils.data.Subset(test_set, range(shard_begin, shard_end)) if world > 1 else test_set
-    test_loader = torch.utils.data.DataLoader(shard, batch_size=batch_size, shuffle=False, drop_last=False,
-                                              num_workers=num_workers, collate_fn=_fov.collate_raw)
-    surface_encoder = SurfaceEncoder(precision=precision).to(device)
-    overhead_encoder = OverheadEncoder(precision=precision).to(device)
-    surface_encoder.load_state_dict(torch.load('./weights/surface_best.pth', map_location='cpu'))
-    overhead_encoder.load_state_dict(torch.load('./weights/overhead_best.pth', map_location='cpu'))
-    surface_encoder.eval()
-    overhead_encoder.eval()
-    su_parts, ov_parts = [], []
-    for raw in test_loader:
-        su, ov = _embed_share(prep, surface_encoder, overhead_encoder, raw)
-        su_parts.append(su)
-        ov_parts.append(ov)
+    test_set = _open_dataset(dataset, csv_path, packed)
+    prep, loader_kw, feed = _staging(dataset, test_set, batch_size, num_workers, packed)
+    test_loader = None
+    try:
+        shard_begin, shard_end = parallel.shard_range(len(test_set))
+        shard = torch.utils.data.Subset(test_set, range(shard_begin, shard_end)) if world > 1 else test_set
+        test_loader = torch.utils.data.DataLoader(shard, batch_size=batch_size, shuffle=False, drop_last=False,
+                                                  num_workers=num_workers, **loader_kw)
+        surface_encoder = SurfaceEncoder(precision=precision).to(device)
+        overhead_encoder = OverheadEncoder(precision=precision).to(device)
+        surface_encoder.load_state_dict(torch.load('./weights/surface_best.pth', map_location='cpu'))
+        overhead_encoder.load_state_dict(torch.load('./weights/overhead_best.pth', map_location='cpu'))
+        surface_encoder.eval()
+        overhead_encoder.eval()
+        su_parts, ov_parts = [], []
+        for raw in feed(test_loader):
+            su, ov = _embed_share(prep, surface_encoder, overhead_encoder, raw)
+            su_parts.append(su)
+            ov_parts.append(ov)
+    finally:
+        if prep.ring is not None:      # also when the loop raises
+            test_loader = None
+            prep.ring.close()
     if world > 1 and not su_parts:      # a rank without rows (more ranks than items) still joins the collectives
         su, ov = _embed_share(prep, surface_encoder, overhead_encoder, {'surface': []})
         su_parts.append(su)
@@ -1015,6 +1158,10 @@ def main(argv=None):
                         help='Train mode on N ranks: BatchNorm statistics of the global batch (two small all-reduces per layer and '
                              'direction) instead of every rank normalising its own share as an nn.DataParallel replica does. '
                              '[Default = off]')
+    parser.add_argument('--data-path', default=None, choices=list(DATA_PATHS),
+                        help='How images reach the encoders: reference = workers decode into float32 tensors, one rotation per sample; '
+                             'packed = workers only parse / entropy-decode, one byte block per side crosses PCIe, the GPU finishes the '
+                             'decode and rotates / rolls the batch in two launches (the same images). [Default = reference]')
     args = parser.parse_args(argv)
     if args.mode != 'train' and args.train_precision is not None:
         parser.error("--train-precision belongs to --mode train")
@@ -1023,13 +1170,14 @@ def main(argv=None):
     if args.mode == 'train' and args.precision != 'fp32':
         parser.error("--precision %s is inference only: --mode train runs in fp32 (use it with --mode test)" % args.precision)
     _fov.init_distributed()       # under `python -m torch.distributed.run --nproc-per-node N`: one process per GPU; else nothing
+    path = {} if args.data_path is None else {'data_path': args.data_path}      # only when the flag was given
     if args.mode == 'train':
         extra = {} if args.train_precision is None else {'train_precision': args.train_precision}      # only when the flag was given
         if args.sync_bn:
             extra['sync_bn'] = True
-        train(dataset=args.dataset, loss=args.loss, **extra)
+        train(dataset=args.dataset, loss=args.loss, **extra, **path)
     elif args.mode == 'test':
-        test(dataset=args.dataset, match_method=args.match_method, precision=args.precision)
+        test(dataset=args.dataset, match_method=args.match_method, precision=args.precision, **path)
 
 
 if __name__ == '__main__':

@@ -1578,6 +1578,16 @@ class GpuPreprocess(object):
         packed = _pack_side([t.cpu() if isinstance(t, torch.Tensor) else t for t in images])
         return self._table_side(st, [self._copy_side(st, dev, packed)])
 
+    def _stage_tail(self, st, s_tab, o_tab, starts):
+        """the model's own per-sample draws, written into the finished tables (host or device) -> (surface table, overhead table);
+        cvig_baseline.GpuPreprocess draws its rotation angles here"""
+        if self.resize.panorama:      # random FoV crop offset per sample (reference: torch.randint per call, :121)
+            if starts is None:
+                starts = torch.randint(0, Globals.surface_width_max, (st.n,)) if self.resize.random_orientation else torch.zeros(st.n, dtype=torch.int64)
+            s_tab = s_tab.cpu() if s_tab.is_cuda else s_tab
+            s_tab[:, 3] = torch.as_tensor(starts, dtype=torch.int64)
+        return s_tab, o_tab
+
     def stage(self, batch, starts=None):
         """batch: one raw / packed batch, or a LIST of them that become ONE staged batch (DevicePrefetcher(group=g): the loader
         hands out batch_size/g samples at a time so that the first full batch is ready after 1/g of the decode time; every
@@ -1640,11 +1650,7 @@ class GpuPreprocess(object):
         else:
             s_tab, o_tab = torch.cat(s_tabs), torch.cat(o_tabs)
         st.n = s_tab.shape[0]
-        if self.resize.panorama:      # random FoV crop offset per sample (reference: torch.randint per call, :121)
-            if starts is None:
-                starts = torch.randint(0, Globals.surface_width_max, (st.n,)) if self.resize.random_orientation else torch.zeros(st.n, dtype=torch.int64)
-            s_tab = s_tab.cpu() if s_tab.is_cuda else s_tab
-            s_tab[:, 3] = torch.as_tensor(starts, dtype=torch.int64)
+        s_tab, o_tab = self._stage_tail(st, s_tab, o_tab, starts)
         st.s_desc = s_tab if s_tab.is_cuda else s_tab.pin_memory().to(dev, non_blocking=True)
         st.o_desc = o_tab if o_tab.is_cuda else o_tab.pin_memory().to(dev, non_blocking=True)
         st.keep += [st.s_desc, st.o_desc]
