@@ -776,7 +776,8 @@ int witw_jpeg_to_rgb(const void* planes, const void* images, int n_images, long 
 /* Entropy decoding ON THE DEVICE for files that carry restart markers (the reference decodes in its loader workers,
  * model/cvig_fov.py:88-89, :402): one GPU thread per restart interval. files: DEVICE int64 [n_files][4] = {address of the file bytes
  * (8-byte aligned, 24 readable bytes behind the end), address of the file's plan (host side: witw_jpeg_entropy_plan in
- * libwitw_jpeg.so -- header fields, Huffman tables, byte offset of every interval; a byte scan, no Huffman decoding), address of the
+ * libwitw_jpeg.so -- header fields, Huffman tables, byte offset of every interval; a byte scan, no Huffman decoding; its layout, and that
+ * of the info ints of witw_jpeg_info, is defined in witw_amd/csrc/jpeg_layout.h and nowhere else), address of the
  * file's coefficient area int16 [blocks][64] (zero-filled by the caller), file length}; the MCU geometry (blocks per MCU and where each
  * lies in its component's grid: 4:4:4, 4:2:2, 4:2:0, grey, and 4:4:0 = Y, Y below it, Cb, Cr) comes from the plan's per-component
  * (h, v); max_intervals: the largest interval count of a

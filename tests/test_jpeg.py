@@ -440,3 +440,24 @@ def test_pack_ships_file_bytes_for_device_entropy_decoding(monkeypatch):
     d2 = desc2.numpy()
     assert list(d2[:, 26]) == [0, 0]
     np.testing.assert_array_equal(b2.numpy()[d2[1, 0]:d2[1, 0] + int(d2[1, 7]) * 128].view(np.int16).reshape(-1, 64), jpeg.read_coef(plain).coef)
+
+
+def test_layout_names_of_jpeg_py_are_those_of_the_header():
+    """witw_amd/csrc/jpeg_layout.h is the one definition of the entropy plan and of the info ints; jpeg.py repeats the names it uses
+    (INFO_* / PLAN_* for WITW_JPEG_INFO_* / WITW_JPEG_PLAN_*). The header is read as text: every `NAME = value` pair."""
+    import re
+    path = os.path.join(os.path.dirname(os.path.abspath(jpeg.__file__)), 'csrc', 'jpeg_layout.h')
+    with open(path) as f:
+        text = re.sub(r'//[^\n]*', '', f.read())
+    pairs = re.findall(r'\b(WITW_JPEG_\w+)\s*=\s*(0[xX][0-9a-fA-F]+|\d+)\b', text)
+    header = {name: int(value, 0) for name, value in pairs}
+    assert len(header) == len(pairs) and len(header) >= 30          # no name twice
+    mine = {n: v for n, v in vars(jpeg).items() if re.match(r'(INFO|PLAN)_[A-Z0-9_]+$', n)}
+    assert {'INFO_H', 'INFO_W', 'INFO_NCOMP', 'INFO_HMAX', 'INFO_VMAX', 'INFO_BLOCKS', 'INFO_COMP', 'INFO_COMP_STRIDE', 'INFO_COMP_H',
+            'INFO_COMP_V', 'INFO_COMP_BW', 'INFO_COMP_BH', 'INFO_INTS', 'PLAN_INTERVALS'} <= set(mine)
+    for n, v in mine.items():
+        assert header.get('WITW_JPEG_' + n) == v, n
+    # the descriptor carries the info ints whole, between its own columns
+    assert jpeg.COL_INFO + jpeg.INFO_INTS == jpeg.COL_RAW and jpeg.COL_INTERVALS + 1 == jpeg.DESC_COLS
+    assert (jpeg.COL_H, jpeg.COL_W) == (jpeg.COL_INFO + jpeg.INFO_H, jpeg.COL_INFO + jpeg.INFO_W)
+    assert header['WITW_JPEG_PLAN_FIXED'] == 736 and header['WITW_JPEG_PLAN_MAGIC'] == 0x3157504A

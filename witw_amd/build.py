@@ -147,20 +147,25 @@ def _build_locked(verbose):
 
 
 HOST_SRC = os.path.join(HERE, 'csrc_host', 'jpeg_coef.cpp')
+HOST_DEPS = [HOST_SRC, os.path.join(CSRC, 'jpeg_layout.h')]      # the plan / info layouts, shared with csrc/jpeg.hip
 HOST_LIB = os.path.join(HERE, 'libwitw_jpeg.so')
+
+
+def host_stale():
+    return not os.path.exists(HOST_LIB) or any(os.path.getmtime(d) > os.path.getmtime(HOST_LIB) for d in HOST_DEPS)
 
 
 def build_host(force=False, verbose=True):
     """libwitw_jpeg.so: the host-only part of the data path (JPEG entropy decoding, csrc_host/jpeg_coef.cpp), plain g++ --
     DataLoader workers load it without ever mapping the HIP runtime."""
-    if not force and os.path.exists(HOST_LIB) and os.path.getmtime(HOST_LIB) >= os.path.getmtime(HOST_SRC):
+    if not force and not host_stale():
         return HOST_LIB
     import fcntl
     os.makedirs(os.path.join(HERE, 'build'), exist_ok=True)
     with open(os.path.join(HERE, 'build', '.lock_host'), 'w') as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            if force or not os.path.exists(HOST_LIB) or os.path.getmtime(HOST_LIB) < os.path.getmtime(HOST_SRC):
+            if force or host_stale():
                 tmp = HOST_LIB + '.tmp.%d' % os.getpid()
                 cmd = [os.environ.get('CXX', 'g++'), '-O3', '-fPIC', '-shared', '-std=c++17', '-Wall', '-o', tmp, HOST_SRC]
                 if verbose:

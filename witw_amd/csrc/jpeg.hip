@@ -9,6 +9,7 @@
 // the byte layout PIL hands the reference (and witw_resize_bilinear_normalize_batched kind 1 / witw_polar_from_raw read).
 // Byte-identical to Pillow's decode: tests/test_jpeg*.py (fixtures under tests/golden/jpeg/ + files written at test time).
 #include "common.h"
+#include "jpeg_layout.h"      // the entropy plan: every plan index below is one of its names
 #include <stdlib.h>
 #include <type_traits>
 
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(256) void jpeg_to_rgb_kernel(const unsigned char* _
 // MARKERS. A restart interval starts byte-aligned with the DC predictors reset, so intervals decode independently: ONE THREAD PER
 // INTERVAL (a 512 x 512 4:2:0 file written with a marker per MCU row has 32 of them, with one per 2 MCUs 512), one workgroup per 256
 // intervals of a file. The host's share shrinks to a byte scan for the markers (csrc_host/jpeg_coef.cpp, witw_jpeg_entropy_plan: the plan layout is
-// described there) and the FILE BYTES cross PCIe instead of the coefficient blocks (~80 KB instead of 786 KB per overhead image).
+// described in jpeg_layout.h) and the FILE BYTES cross PCIe instead of the coefficient blocks (~80 KB instead of 786 KB per overhead image).
 // Integer / byte work, latency-bound per thread (a table look-up and a few shifts per symbol); nothing here is MFMA- or
 // HBM-shaped. A wave pays for every path ANY of its 64 lanes takes, so the rare paths are kept short: four input bytes at a time while
 // no FF is among them, codes longer than the look-up by seven compares instead of a loop, the zig-zag order from the LDS. Same coefficients, bit for bit, as witw_jpeg_decode_coef (tests/test_jpeg_gpu.py).
@@ -200,9 +201,6 @@ __constant__ unsigned char kZigZag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24
 
 // Addresses that arrive as integers (descriptor rows) carry no address space: dereferenced as plain pointers they become FLAT accesses,
 // which count on the LDS counter as well as on the memory counter. The Huffman kernels name the space of everything they touch.
-#ifndef WITW_SS_DIAG
-#define WITW_SS_DIAG 0          // 1: jpeg_selfsync_kernel stops behind its rounds and reports (rounds << 20 | re-decoded subsequences) per file in `errors`
-#endif
 #define WITW_AS_GLOBAL __attribute__((address_space(1)))
 #define WITW_AS_LDS __attribute__((address_space(3)))
 typedef const WITW_AS_GLOBAL unsigned long long* GlobalWords;
@@ -340,10 +338,11 @@ template <typename PP>      // PP: pointer to the plan's bytes
 __device__ __forceinline__ void build_huff_tables(HuffLds (&tab)[4], PP plan, int lane, int nthreads) {
     for (int e = lane; e < 4 * 256; e += nthreads) {      // the symbols (a DC table has at most 16; nothing past a table's count is ever indexed)
         const int t = e >> 8, i = e & 255;
-        tab[t].sym[i] = t < 2 ? (i < 16 ? plan[128 + 32 * t + 16 + i] : 0) : plan[192 + 272 * (t - 2) + 16 + i];
+        tab[t].sym[i] = t < 2 ? (i < 16 ? plan[WITW_JPEG_PLAN_DC + WITW_JPEG_PLAN_DC_STRIDE * t + WITW_JPEG_PLAN_TABLE_SYMS + i] : 0)
+                              : plan[WITW_JPEG_PLAN_AC + WITW_JPEG_PLAN_AC_STRIDE * (t - 2) + WITW_JPEG_PLAN_TABLE_SYMS + i];
     }
     if (lane < 4) {
-        const PP d = lane < 2 ? plan + 128 + 32 * lane : plan + 192 + 272 * (lane - 2);
+        const PP d = lane < 2 ? plan + WITW_JPEG_PLAN_DC + WITW_JPEG_PLAN_DC_STRIDE * lane : plan + WITW_JPEG_PLAN_AC + WITW_JPEG_PLAN_AC_STRIDE * (lane - 2);
         HuffLds& h = tab[lane];
         int code = 0, k = 0;
         h.lim[0] = 0u;
@@ -393,12 +392,12 @@ __device__ __forceinline__ bool huff_interval(BitReaderT<true, WP>& b, const Huf
     int my = (int)(m0 / x.mcux), mx = (int)(m0 - (long long)my * x.mcux);
     for (long long m = m0; m < m1; ++m) {
         for (int k = 0; k < x.ncomp; ++k) {
-            const int c = x.hdr[28 + k];
-            const WITW_AS_LDS int* q = x.hdr + 6 + 7 * c;
-            const int ch = q[0], cv = q[1], cbw = q[2];
-            const long long coff = q[4];
-            const WITW_AS_LDS HuffLds* hd = x.tab + (q[5] & 1);
-            const WITW_AS_LDS HuffLds* ha = x.tab + 2 + (q[6] & 1);
+            const int c = x.hdr[WITW_JPEG_PLAN_SCAN_COMP + k];
+            const WITW_AS_LDS int* q = x.hdr + WITW_JPEG_PLAN_COMP + WITW_JPEG_PLAN_COMP_STRIDE * c;
+            const int ch = q[WITW_JPEG_PLAN_COMP_H], cv = q[WITW_JPEG_PLAN_COMP_V], cbw = q[WITW_JPEG_PLAN_COMP_BW];
+            const long long coff = q[WITW_JPEG_PLAN_COMP_FIRST];
+            const WITW_AS_LDS HuffLds* hd = x.tab + (q[WITW_JPEG_PLAN_COMP_DC] & 1);
+            const WITW_AS_LDS HuffLds* ha = x.tab + 2 + (q[WITW_JPEG_PLAN_COMP_AC] & 1);
             for (int v = 0; v < cv; ++v)
                 for (int hh = 0; hh < ch; ++hh) {
                     WITW_AS_GLOBAL short* blk = x.coef + (coff + (long long)(my * cv + v) * cbw + (mx * ch + hh)) * 64;
@@ -434,7 +433,7 @@ __device__ __forceinline__ bool huff_interval(BitReaderT<true, WP>& b, const Huf
 
 __global__ __launch_bounds__(HUFF_T) void jpeg_huffman_kernel(const JpegFileDev* __restrict__ files, int* __restrict__ errors) {
     __shared__ HuffLds tab[4];                    // DC slot 0, 1, AC slot 0, 1
-    __shared__ int hdr[32];
+    __shared__ int hdr[WITW_JPEG_PLAN_HEADER_INTS];
     __shared__ unsigned char zz[64];
     __shared__ __attribute__((aligned(16))) unsigned long long stage[HUFF_T / 64][HUFF_STAGE / 8];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -442,21 +441,22 @@ __global__ __launch_bounds__(HUFF_T) void jpeg_huffman_kernel(const JpegFileDev*
     const WITW_AS_GLOBAL unsigned char* plan = (const WITW_AS_GLOBAL unsigned char*)f.plan;
     // blockIdx.y: which 256 intervals of the file this workgroup decodes (a thread's chain of symbols is what bounds the kernel: files
     // with short intervals spread over several workgroups); workgroups past the file's last interval leave before building tables
-    if ((int)blockIdx.y * HUFF_T >= ((const WITW_AS_GLOBAL int*)plan)[1] && ((const WITW_AS_GLOBAL int*)plan)[0] == 0x3157504A) return;
-    if (tid < 32) hdr[tid] = ((const WITW_AS_GLOBAL int*)plan)[tid];
+    if ((int)blockIdx.y * HUFF_T >= ((const WITW_AS_GLOBAL int*)plan)[WITW_JPEG_PLAN_INTERVALS] &&
+        ((const WITW_AS_GLOBAL int*)plan)[WITW_JPEG_PLAN_MAGIC_AT] == WITW_JPEG_PLAN_MAGIC) return;
+    if (tid < WITW_JPEG_PLAN_HEADER_INTS) hdr[tid] = ((const WITW_AS_GLOBAL int*)plan)[tid];
     if (tid >= 64 && tid < 128) zz[tid - 64] = kZigZag[tid - 64];
     build_huff_tables(tab, plan, tid, HUFF_T);
-    if (hdr[0] != 0x3157504A) {
+    if (hdr[WITW_JPEG_PLAN_MAGIC_AT] != WITW_JPEG_PLAN_MAGIC) {
         if (tid == 0 && blockIdx.y == 0) errors[blockIdx.x] = 2;
         return;
     }
-    const int n_int = hdr[1], restart = hdr[2], mcuy = hdr[4];
+    const int n_int = hdr[WITW_JPEG_PLAN_INTERVALS], restart = hdr[WITW_JPEG_PLAN_INTERVAL_MCUS], mcuy = hdr[WITW_JPEG_PLAN_MCUY];
     const unsigned n_bytes = (unsigned)f.n_bytes;
-    const unsigned end_all = min((unsigned)hdr[27], n_bytes);
-    const WITW_AS_GLOBAL unsigned* ioff = (const WITW_AS_GLOBAL unsigned*)(plan + 736);
+    const unsigned end_all = min((unsigned)hdr[WITW_JPEG_PLAN_DATA_END], n_bytes);
+    const WITW_AS_GLOBAL unsigned* ioff = (const WITW_AS_GLOBAL unsigned*)(plan + WITW_JPEG_PLAN_FIXED);
     HuffCtx x;
     x.tab = (const WITW_AS_LDS HuffLds*)tab; x.hdr = (const WITW_AS_LDS int*)hdr; x.zz = (const WITW_AS_LDS unsigned char*)zz;
-    x.coef = (WITW_AS_GLOBAL short*)f.coef; x.mcux = hdr[3]; x.ncomp = hdr[5];
+    x.coef = (WITW_AS_GLOBAL short*)f.coef; x.mcux = hdr[WITW_JPEG_PLAN_MCUX]; x.ncomp = hdr[WITW_JPEG_PLAN_NCOMP];
     const long long mcus = (long long)x.mcux * mcuy;
     bool bad = false;
     for (int base = (int)blockIdx.y * HUFF_T; base < n_int; base += HUFF_T * (int)gridDim.y) {      // (one pass unless the file has > 16,384 intervals)
@@ -552,36 +552,34 @@ __device__ __forceinline__ int block_scan_excl(int v, int* wave_tot, int tid, in
 template <int SS_T>      // threads per file: 256 (a workgroup that fits beside others on a CU; a thread's subsequence is 4 x longer) .. 1024
 __global__ __launch_bounds__(SS_T) void jpeg_selfsync_kernel(const JpegSyncDev* __restrict__ files, int* __restrict__ errors) {
     __shared__ HuffLds tab[4];
-    __shared__ int hdr[32];
+    __shared__ int hdr[WITW_JPEG_PLAN_HEADER_INTS];
     __shared__ SyncState exit_s[SS_T];      // (SS_T is the template parameter here)
     __shared__ unsigned short nblk_s[SS_T];
     __shared__ int wave_tot[SS_T / 64];
     __shared__ int changed;
-#if WITW_SS_DIAG == 1
-    __shared__ int diag_rounds, diag_changed;
-    if (threadIdx.x == 0) { diag_rounds = 0; diag_changed = 0; }
-#endif
     __shared__ unsigned char mcu_comp[16], mcu_v[16], mcu_h[16];      // block j of an MCU: component, row / column inside the MCU
     __shared__ unsigned char zz[64];
     const int tid = threadIdx.x;
     const JpegSyncDev f = files[blockIdx.x];
     const WITW_AS_GLOBAL unsigned char* plan = (const WITW_AS_GLOBAL unsigned char*)f.plan;
-    if (tid < 32) hdr[tid] = ((const WITW_AS_GLOBAL int*)plan)[tid];
+    if (tid < WITW_JPEG_PLAN_HEADER_INTS) hdr[tid] = ((const WITW_AS_GLOBAL int*)plan)[tid];
     if (tid >= 64 && tid < 128) zz[tid - 64] = kZigZag[tid - 64];
     build_huff_tables(tab, plan, tid, SS_T);
-    if (hdr[0] != 0x3157504A || hdr[1] != 1) {
+    if (hdr[WITW_JPEG_PLAN_MAGIC_AT] != WITW_JPEG_PLAN_MAGIC || hdr[WITW_JPEG_PLAN_INTERVALS] != 1) {
         if (tid == 0) errors[blockIdx.x] = 2;
         return;
     }
-    const int mcux = hdr[3], mcuy = hdr[4], ncomp = hdr[5];
+    const int mcux = hdr[WITW_JPEG_PLAN_MCUX], mcuy = hdr[WITW_JPEG_PLAN_MCUY], ncomp = hdr[WITW_JPEG_PLAN_NCOMP];
+    constexpr int COMP_H = WITW_JPEG_PLAN_COMP + WITW_JPEG_PLAN_COMP_H, COMP_V = WITW_JPEG_PLAN_COMP + WITW_JPEG_PLAN_COMP_V;      // of component 0: + COMP_STRIDE * c
     int nb = 0;                                    // blocks per MCU
-    for (int k = 0; k < ncomp; ++k) nb += hdr[6 + 7 * hdr[28 + k]] * hdr[7 + 7 * hdr[28 + k]];
+    for (int k = 0; k < ncomp; ++k)
+        nb += hdr[COMP_H + WITW_JPEG_PLAN_COMP_STRIDE * hdr[WITW_JPEG_PLAN_SCAN_COMP + k]] * hdr[COMP_V + WITW_JPEG_PLAN_COMP_STRIDE * hdr[WITW_JPEG_PLAN_SCAN_COMP + k]];
     if (tid == 0) {
         int j = 0;
         for (int k = 0; k < ncomp; ++k) {
-            const int c = hdr[28 + k];
-            for (int v = 0; v < hdr[7 + 7 * c]; ++v)
-                for (int h = 0; h < hdr[6 + 7 * c]; ++h, ++j)
+            const int c = hdr[WITW_JPEG_PLAN_SCAN_COMP + k];
+            for (int v = 0; v < hdr[COMP_V + WITW_JPEG_PLAN_COMP_STRIDE * c]; ++v)
+                for (int h = 0; h < hdr[COMP_H + WITW_JPEG_PLAN_COMP_STRIDE * c]; ++h, ++j)
                     if (j < 16) { mcu_comp[j] = (unsigned char)c; mcu_v[j] = (unsigned char)v; mcu_h[j] = (unsigned char)h; }
         }
     }
@@ -592,8 +590,8 @@ __global__ __launch_bounds__(SS_T) void jpeg_selfsync_kernel(const JpegSyncDev* 
     // ---- 1: unstuff [start, end) -> clean
     const WITW_AS_GLOBAL unsigned char* src = (const WITW_AS_GLOBAL unsigned char*)f.bytes;
     WITW_AS_GLOBAL unsigned char* clean = (WITW_AS_GLOBAL unsigned char*)f.clean;
-    const unsigned s0 = ((const WITW_AS_GLOBAL unsigned*)(plan + 736))[0];
-    unsigned s1 = (unsigned)hdr[27];
+    const unsigned s0 = ((const WITW_AS_GLOBAL unsigned*)(plan + WITW_JPEG_PLAN_FIXED))[0];
+    unsigned s1 = (unsigned)hdr[WITW_JPEG_PLAN_DATA_END];
     if (s1 > (unsigned)f.n_bytes) s1 = (unsigned)f.n_bytes;
     const unsigned len = s1 > s0 ? s1 - s0 : 0u;
     // a thread's piece is a whole number of 8-byte words: read -- and, where no stuffed zero sits in them, written -- as ONE unaligned access
@@ -649,9 +647,6 @@ __global__ __launch_bounds__(SS_T) void jpeg_selfsync_kernel(const JpegSyncDev* 
     }
     if (tid < 32) clean[n_clean + tid] = 0;      // the reader runs up to two 8-byte words ahead
     __syncthreads();
-#if WITW_SS_DIAG == 2
-    return;                                       // DIAGNOSTIC BUILD: the unstuffing step alone
-#endif
     const unsigned total_bits = (unsigned)n_clean * 8u;
     // subsequence length in bits: equal parts, at least 64 (a symbol with its value bits is at most 32)
     unsigned L = (total_bits + SS_T - 1) / SS_T;
@@ -679,18 +674,19 @@ __global__ __launch_bounds__(SS_T) void jpeg_selfsync_kernel(const JpegSyncDev* 
             const long long m = bi / nb;
             const int j = (int)(bi - m * nb);
             const int c = mcu_comp[j];
-            const int* q = hdr + 6 + 7 * c;
+            const int* q = hdr + WITW_JPEG_PLAN_COMP + WITW_JPEG_PLAN_COMP_STRIDE * c;
             const int my = (int)(m / mcux), mx = (int)(m - (long long)my * mcux);
-            return coef + ((long long)q[4] + (long long)(my * q[1] + mcu_v[j]) * q[2] + (mx * q[0] + mcu_h[j])) * 64;
+            return coef + ((long long)q[WITW_JPEG_PLAN_COMP_FIRST] + (long long)(my * q[WITW_JPEG_PLAN_COMP_V] + mcu_v[j]) * q[WITW_JPEG_PLAN_COMP_BW] +
+                           (mx * q[WITW_JPEG_PLAN_COMP_H] + mcu_h[j])) * 64;
         };
         if (WRITE) blk = locate(blk0);
         // the two tables of the block at hand, looked up when the block changes (not per symbol: component -> header -> table is a chain
         // of LDS reads in front of every look-up otherwise)
         int tdc = 0, tac = 2;
         auto tables_of = [&](unsigned j) {
-            const int* q = hdr + 6 + 7 * mcu_comp[j];
-            tdc = q[5] & 1;
-            tac = 2 + (q[6] & 1);
+            const int* q = hdr + WITW_JPEG_PLAN_COMP + WITW_JPEG_PLAN_COMP_STRIDE * mcu_comp[j];
+            tdc = q[WITW_JPEG_PLAN_COMP_DC] & 1;
+            tac = 2 + (q[WITW_JPEG_PLAN_COMP_AC] & 1);
         };
         tables_of(bq);
         // ONE decode site and one straight line for the DC symbol and the three kinds of AC symbol (coefficient, ZRL, EOB): the 64 lanes of
@@ -741,18 +737,9 @@ __global__ __launch_bounds__(SS_T) void jpeg_selfsync_kernel(const JpegSyncDev* 
             changed = 1;
         }
         __syncthreads();
-#if WITW_SS_DIAG == 1
-        if (differs) atomicAdd(&diag_changed, 1);
-        if (tid == 0) ++diag_rounds;
-#endif
         if (!changed) break;
         __syncthreads();
     }
-#if WITW_SS_DIAG == 1
-    __syncthreads();
-    if (tid == 0) errors[blockIdx.x] = (diag_rounds << 20) | diag_changed;      // DIAGNOSTIC BUILD: rounds, re-decoded subsequences in all
-    return;
-#endif
     // ---- 3: number the blocks, decode once more and write
     int total_done = 0;
     const int first = block_scan_excl<SS_T>((int)nblk_s[tid], wave_tot, tid, total_done);
@@ -764,17 +751,18 @@ __global__ __launch_bounds__(SS_T) void jpeg_selfsync_kernel(const JpegSyncDev* 
     // ---- 4: DC differences -> DC values, per component over its blocks in scan order
     WITW_AS_GLOBAL short* coef = (WITW_AS_GLOBAL short*)f.coef;
     for (int k = 0; k < ncomp; ++k) {
-        const int c = hdr[28 + k];
-        const int* q = hdr + 6 + 7 * c;
-        const int per_mcu = q[0] * q[1];
+        const int c = hdr[WITW_JPEG_PLAN_SCAN_COMP + k];
+        const int* q = hdr + WITW_JPEG_PLAN_COMP + WITW_JPEG_PLAN_COMP_STRIDE * c;
+        const int per_mcu = q[WITW_JPEG_PLAN_COMP_H] * q[WITW_JPEG_PLAN_COMP_V];
         const long long n_c = (long long)mcux * mcuy * per_mcu;
         const long long per_t = (n_c + SS_T - 1) / SS_T;
         const long long i0 = min(n_c, (long long)tid * per_t), i1 = min(n_c, ((long long)tid + 1) * per_t);
         auto at = [&](long long i) -> WITW_AS_GLOBAL short* {      // i-th block of the component in scan order
             const long long m = i / per_mcu;
-            const int j = (int)(i - m * per_mcu), v = j / q[0], h = j - v * q[0];
+            const int j = (int)(i - m * per_mcu), v = j / q[WITW_JPEG_PLAN_COMP_H], h = j - v * q[WITW_JPEG_PLAN_COMP_H];
             const int my = (int)(m / mcux), mx = (int)(m - (long long)my * mcux);
-            return coef + ((long long)q[4] + (long long)(my * q[1] + v) * q[2] + (mx * q[0] + h)) * 64;
+            return coef + ((long long)q[WITW_JPEG_PLAN_COMP_FIRST] + (long long)(my * q[WITW_JPEG_PLAN_COMP_V] + v) * q[WITW_JPEG_PLAN_COMP_BW] +
+                           (mx * q[WITW_JPEG_PLAN_COMP_H] + h)) * 64;
         };
         int sum = 0;
         for (long long i = i0; i < i1; ++i) sum += *at(i);

@@ -15,6 +15,8 @@
 #include <stddef.h>
 #include <string.h>
 
+#include "../csrc/jpeg_layout.h"      // the entropy plan and the `info` ints: every index below is one of its names
+
 namespace {
 
 const uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -299,15 +301,17 @@ Unstuffed& unstuffed() {
 }
 
 void fill_info(const Parsed& P, int32_t* info) {
-    info[0] = P.H; info[1] = P.W; info[2] = P.ncomp; info[3] = P.hmax; info[4] = P.vmax;
+    info[WITW_JPEG_INFO_H] = P.H; info[WITW_JPEG_INFO_W] = P.W; info[WITW_JPEG_INFO_NCOMP] = P.ncomp;
+    info[WITW_JPEG_INFO_HMAX] = P.hmax; info[WITW_JPEG_INFO_VMAX] = P.vmax;
     int64_t total = 0;
     for (int c = 0; c < 4; ++c) {
         const bool on = c < P.ncomp;
-        info[6 + 4 * c] = on ? P.c[c].h : 0; info[7 + 4 * c] = on ? P.c[c].v : 0;
-        info[8 + 4 * c] = on ? P.c[c].bw : 0; info[9 + 4 * c] = on ? P.c[c].bh : 0;
+        int32_t* q = info + WITW_JPEG_INFO_COMP + WITW_JPEG_INFO_COMP_STRIDE * c;
+        q[WITW_JPEG_INFO_COMP_H] = on ? P.c[c].h : 0; q[WITW_JPEG_INFO_COMP_V] = on ? P.c[c].v : 0;
+        q[WITW_JPEG_INFO_COMP_BW] = on ? P.c[c].bw : 0; q[WITW_JPEG_INFO_COMP_BH] = on ? P.c[c].bh : 0;
         if (on) total += (int64_t)P.c[c].bw * P.c[c].bh;
     }
-    info[5] = (int32_t)total;
+    info[WITW_JPEG_INFO_BLOCKS] = (int32_t)total;
 }
 
 // the one interleaved scan of a sequential file (P: parse() == 0) -> 0 / -3
@@ -615,34 +619,17 @@ int decode_progressive(Parsed& P, const uint8_t* d, size_t n, int16_t* coef, uin
 
 extern "C" {
 
-// info[0..]: H, W, ncomp, hmax, vmax, total blocks, then per component (4 slots): h, v, blocks wide, blocks high.
-// Returns 0; -1 = not a decodable JPEG stream; -2 = a JPEG this decoder leaves to the host library (progressive, arithmetic,
-// 12-bit, CMYK, non-interleaved scans, sampling other than 4:4:4 / 4:2:2 (h2v1) / 4:2:0 / grey (4:4:0 on request: _ex), RGB-colourspace files: Adobe
-// transform 0 or component ids 'R','G','B' without a JFIF marker).
-int witw_jpeg_info(const uint8_t* data, size_t n, int32_t* info /* 22 */) {
-    Parsed& P = parsed();
-    const int rc = parse(data, n, P);
-    if (rc) return rc;
-    fill_info(P, info);
-    return 0;
-}
-
-// coef: total blocks x 64 int16 (zero-filled here); qt: ncomp x 64 uint16. Returns 0 or a negative code as above; -3 = the
-// entropy-coded data ended early or holds an invalid code (the blocks decoded so far are kept, the rest stay zero).
-int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t* qt) {
-    Parsed& P = parsed();
-    const int rc = parse(data, n, P);
-    if (rc) return rc;
-    return decode_sequential(P, data, n, coef, qt);
-}
-
-// flags bit 0 = accept progressive files (SOF2) that meet the constraints above (8-bit, 1 or 3 components, the same samplings and
-// colour spaces); bit 1 = accept 4:4:0 sampling (h1v2: luma (h, v) = (1, 2), both chroma (1, 1)) beside the samplings above -- a
+// flags bit 0 = accept progressive files (SOF2) that meet the constraints below (8-bit, 1 or 3 components, the same samplings and
+// colour spaces); bit 1 = accept 4:4:0 sampling (h1v2: luma (h, v) = (1, 2), both chroma (1, 1)) beside the samplings below -- a
 // progressive 4:4:0 file needs both bits; every other bit is reserved (0). With flags == 0 the entries are their plain namesakes.
 enum { WITW_JPEG_ACCEPT_PROGRESSIVE = 1, WITW_JPEG_ACCEPT_H1V2 = 2 };
 
-// As witw_jpeg_info, and 1 = a progressive file this decoder takes (only the header has been looked at: witw_jpeg_decode_coef_ex
-// says whether its scans are legal and complete).
+// info: the WITW_JPEG_INFO_INTS ints of csrc/jpeg_layout.h (H, W, ncomp, hmax, vmax, total blocks, then per component (4 slots): h, v,
+// blocks wide, blocks high).
+// Returns 0; 1 = a progressive file this decoder takes (only the header has been looked at: witw_jpeg_decode_coef_ex says whether its
+// scans are legal and complete); -1 = not a decodable JPEG stream; -2 = a JPEG this decoder leaves to the host library (progressive
+// without bit 0, arithmetic, 12-bit, CMYK, non-interleaved scans, sampling other than 4:4:4 / 4:2:2 (h2v1) / 4:2:0 / grey (4:4:0: bit 1),
+// RGB-colourspace files: Adobe transform 0 or component ids 'R','G','B' without a JFIF marker).
 int witw_jpeg_info_ex(const uint8_t* data, size_t n, int32_t* info /* 22 */, int flags) {
     Parsed& P = parsed();
     const int rc = parse(data, n, P, (flags & WITW_JPEG_ACCEPT_PROGRESSIVE) != 0, (flags & WITW_JPEG_ACCEPT_H1V2) != 0);
@@ -651,9 +638,13 @@ int witw_jpeg_info_ex(const uint8_t* data, size_t n, int32_t* info /* 22 */, int
     return P.progressive ? 1 : 0;
 }
 
-// As witw_jpeg_decode_coef (same layout: a progressive file gives the blocks its sequential twin would); for a progressive file
-// -3 also = a scan the earlier scans do not allow (Ss / Se / Ah / Al), and -2 = the file ends before every coefficient of every
-// component has been refined down to bit 0 (the host library smooths such a file: leave it there).
+int witw_jpeg_info(const uint8_t* data, size_t n, int32_t* info /* 22 */) { return witw_jpeg_info_ex(data, n, info, 0); }
+
+// coef: total blocks x 64 int16 (zero-filled here); qt: ncomp x 64 uint16. Returns 0 or a negative code as above; -3 = the
+// entropy-coded data ended early or holds an invalid code (the blocks decoded so far are kept, the rest stay zero). A progressive
+// file gives the blocks its sequential twin would; for it -3 also = a scan the earlier scans do not allow (Ss / Se / Ah / Al), and
+// -2 = the file ends before every coefficient of every component has been refined down to bit 0 (the host library smooths such a
+// file: leave it there).
 int witw_jpeg_decode_coef_ex(const uint8_t* data, size_t n, int16_t* coef, uint16_t* qt, int flags) {
     Parsed& P = parsed();
     const int rc = parse(data, n, P, (flags & WITW_JPEG_ACCEPT_PROGRESSIVE) != 0, (flags & WITW_JPEG_ACCEPT_H1V2) != 0);
@@ -661,19 +652,12 @@ int witw_jpeg_decode_coef_ex(const uint8_t* data, size_t n, int16_t* coef, uint1
     return P.progressive ? decode_progressive(P, data, n, coef, qt) : decode_sequential(P, data, n, coef, qt);
 }
 
+int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t* qt) { return witw_jpeg_decode_coef_ex(data, n, coef, qt, 0); }
+
 // ---- entropy decoding ON THE DEVICE for files that carry restart markers (csrc/jpeg.hip, jpeg_huffman_kernel: one GPU thread per
 // restart interval). What is left for the host is a byte scan: the header, and the positions of the RSTn markers in the entropy-coded
 // segment (memchr over ~80 KB per 512 x 512 image instead of decoding ~60 k Huffman symbols). The plan written here is what the
-// kernel reads beside the FILE BYTES themselves (it unstuffs FF 00 on the fly):
-//   int32[0] magic 'JPW1', [1] intervals, [2] MCUs per interval, [3] MCUs per row, [4] MCU rows, [5] components,
-//   [6 + 7c ..] component c < 3: h, v, blocks wide, blocks high, first block (within the file's coefficient area), DC slot, AC slot,
-//   [27] end of the entropy-coded data (byte offset in the file), [28..30] component of scan position k, [31] 0;
-//   byte 128: DC tables of slots 0, 1 (16 counts + 16 symbols each), byte 192: AC tables of slots 0, 1 (16 counts + 256 symbols each);
-//   byte 736: uint32 [intervals]: byte offset in the file of each interval's first entropy-coded byte.
-// A file without restart markers gets a plan of ONE interval (the whole scan): the device decodes it with the self-synchronising
-// kernel. Files with more than two DC or AC tables in use, or whose markers are out of sequence, return -2 / -3 and take the host
-// path (witw_jpeg_decode_coef) as before.
-enum { WITW_JPEG_PLAN_FIXED = 736 };
+// kernel reads beside the FILE BYTES themselves; its layout is described, and named, in csrc/jpeg_layout.h.
 
 // (flags: bit 1 as above; a progressive file has no plan whatever bit 0 says: its scans refine one another)
 long long witw_jpeg_entropy_plan_bytes_ex(const uint8_t* data, size_t n, int flags) {      // 0: not a file for this decoder
@@ -705,31 +689,33 @@ long long witw_jpeg_entropy_plan_ex(const uint8_t* data, size_t n, uint8_t* plan
     if ((long long)plan_cap < need || n_int > 0x7fffffff) return -1;
     memset(plan, 0, (size_t)need);
     int32_t* h = reinterpret_cast<int32_t*>(plan);
-    h[0] = 0x3157504A;      // 'JPW1'
-    h[1] = (int32_t)n_int; h[2] = P.restart; h[3] = P.mcux; h[4] = P.mcuy; h[5] = P.ncomp;
+    h[WITW_JPEG_PLAN_MAGIC_AT] = WITW_JPEG_PLAN_MAGIC;
+    h[WITW_JPEG_PLAN_INTERVALS] = (int32_t)n_int; h[WITW_JPEG_PLAN_INTERVAL_MCUS] = P.restart;
+    h[WITW_JPEG_PLAN_MCUX] = P.mcux; h[WITW_JPEG_PLAN_MCUY] = P.mcuy; h[WITW_JPEG_PLAN_NCOMP] = P.ncomp;
     int dc_slot[4] = {-1, -1, -1, -1}, ac_slot[4] = {-1, -1, -1, -1}, n_dc = 0, n_ac = 0;
     for (int c = 0; c < P.ncomp; ++c) {
         if (dc_slot[P.c[c].td] < 0) { if (n_dc == 2) return -2; dc_slot[P.c[c].td] = n_dc++; }
         if (ac_slot[P.c[c].ta] < 0) { if (n_ac == 2) return -2; ac_slot[P.c[c].ta] = n_ac++; }
-        int32_t* q = h + 6 + 7 * c;
-        q[0] = P.c[c].h; q[1] = P.c[c].v; q[2] = P.c[c].bw; q[3] = P.c[c].bh; q[4] = (int32_t)P.c[c].off;
-        q[5] = dc_slot[P.c[c].td]; q[6] = ac_slot[P.c[c].ta];
+        int32_t* q = h + WITW_JPEG_PLAN_COMP + WITW_JPEG_PLAN_COMP_STRIDE * c;
+        q[WITW_JPEG_PLAN_COMP_H] = P.c[c].h; q[WITW_JPEG_PLAN_COMP_V] = P.c[c].v;
+        q[WITW_JPEG_PLAN_COMP_BW] = P.c[c].bw; q[WITW_JPEG_PLAN_COMP_BH] = P.c[c].bh; q[WITW_JPEG_PLAN_COMP_FIRST] = (int32_t)P.c[c].off;
+        q[WITW_JPEG_PLAN_COMP_DC] = dc_slot[P.c[c].td]; q[WITW_JPEG_PLAN_COMP_AC] = ac_slot[P.c[c].ta];
         memcpy(qt + 64 * c, P.qt[P.c[c].tq], 128);
     }
-    for (int k = 0; k < P.scan_ncomp && k < 3; ++k) h[28 + k] = P.scan_comp[k];
+    for (int k = 0; k < P.scan_ncomp && k < 3; ++k) h[WITW_JPEG_PLAN_SCAN_COMP + k] = P.scan_comp[k];
     for (int t = 0; t < 4; ++t) {
         if (dc_slot[t] >= 0) {
             const Huff& hf = P.dc[t];
             if (hf.nsym > 16) return -2;                              // a DC table holds at most 12 categories (16 leaves room)
-            uint8_t* d = plan + 128 + 32 * dc_slot[t];
+            uint8_t* d = plan + WITW_JPEG_PLAN_DC + WITW_JPEG_PLAN_DC_STRIDE * dc_slot[t];
             memcpy(d, hf.counts, 16);
-            memcpy(d + 16, hf.sym, (size_t)hf.nsym);
+            memcpy(d + WITW_JPEG_PLAN_TABLE_SYMS, hf.sym, (size_t)hf.nsym);
         }
         if (ac_slot[t] >= 0) {
             const Huff& hf = P.ac[t];
-            uint8_t* d = plan + 192 + 272 * ac_slot[t];
+            uint8_t* d = plan + WITW_JPEG_PLAN_AC + WITW_JPEG_PLAN_AC_STRIDE * ac_slot[t];
             memcpy(d, hf.counts, 16);
-            memcpy(d + 16, hf.sym, (size_t)hf.nsym);
+            memcpy(d + WITW_JPEG_PLAN_TABLE_SYMS, hf.sym, (size_t)hf.nsym);
         }
     }
     uint32_t* off = reinterpret_cast<uint32_t*>(plan + WITW_JPEG_PLAN_FIXED);
@@ -756,7 +742,7 @@ long long witw_jpeg_entropy_plan_ex(const uint8_t* data, size_t n, uint8_t* plan
         break;
     }
     if (found != n_int - 1) return -3;
-    h[27] = (int32_t)(end - data);
+    h[WITW_JPEG_PLAN_DATA_END] = (int32_t)(end - data);
     return need;
 }
 

@@ -1413,9 +1413,14 @@ def collate_raw(samples):
     return out
 
 
+# image kinds of a packed block and of the staged tables (the `kind` of ops.resize_batched / ops.polar_from_raw); jpeg.KIND_JPEG (2) is
+# the third: a block jpeg.pack built, decoded on the device into KIND_U8_HWC images
+KIND_F32_CHW, KIND_U8_HWC = 0, 1
+
+
 def _pack_side(images, alloc=None):
     """A batch of differently sized images -> ONE contiguous byte buffer + [B,4] int64 {byte offset, H, W, channels stored per
-    pixel}. All uint8 HWC (decoder output) -> kind 1, bytes as they are; anything else -> float32 planar CHW, kind 0.
+    pixel}. All uint8 HWC (decoder output) -> KIND_U8_HWC, bytes as they are; anything else -> float32 planar CHW, KIND_F32_CHW.
     alloc: build the block in caller-provided memory (ring.PinnedRing.allocator); the first result is then (offset, nbytes),
     or the whole result None when the memory is too small."""
     import numpy as np
@@ -1448,7 +1453,7 @@ def _pack_side(images, alloc=None):
         buf = t.numpy()
     for (o, _h, _w, _c), f in zip(desc, parts):
         buf[o:o + f.size] = f
-    return t, torch.tensor(desc, dtype=torch.int64), 1 if raw else 0
+    return t, torch.tensor(desc, dtype=torch.int64), KIND_U8_HWC if raw else KIND_F32_CHW
 
 
 def collate_packed(samples, ring=None):
@@ -1544,14 +1549,14 @@ class GpuPreprocess(object):
         JPEG parts (jpeg.KIND_JPEG: file bytes or coefficient blocks -> [Huffman decoding,] dequantise, inverse DCT, upsample,
         colour-convert on the device) are decoded by launches that cover every part; finish (None or a callable) must run before the
         table is used: it reads the device decoder's damage flags and patches the rows of re-decoded files."""
+        from . import jpeg
         kinds = set(c[2] for c in copied)
-        if kinds == {2}:
-            from . import jpeg
+        if kinds == {jpeg.KIND_JPEG}:
             keep, table, finish = jpeg.decode_packed_multi([(dbuf, desc, buf) for dbuf, desc, _k, buf in copied], defer=True)
             st.keep += keep
             if int(table[:, 4].min()) < self.channels:
                 raise _lib.WitwError('an image of the batch has %d channels, the model takes %d' % (int(table[:, 4].min()), self.channels))
-            return table, 1, finish      # from here on: uint8 HWC images on the device
+            return table, KIND_U8_HWC, finish      # from here on: uint8 HWC images on the device
         if len(kinds) > 1:
             raise _lib.WitwError('the parts of a grouped batch hold different image kinds (fp32 CHW / u8 HWC)')
         tables = []
@@ -1574,7 +1579,7 @@ class GpuPreprocess(object):
                 t = t.to(torch.float32).contiguous()
                 st.keep.append(t)
                 rows.append((t.data_ptr(), t.shape[1], t.shape[2], 0, t.shape[0]))
-            return torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True), 0, None
+            return torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True), KIND_F32_CHW, None
         packed = _pack_side([t.cpu() if isinstance(t, torch.Tensor) else t for t in images])
         return self._table_side(st, [self._copy_side(st, dev, packed)])
 
@@ -1625,13 +1630,14 @@ class GpuPreprocess(object):
         if s_copied:
             if s_tabs:
                 raise _lib.WitwError('the parts of a grouped batch are packed and unpacked')
-            if all(c[2] == 2 for c in s_copied + o_copied):
+            from . import jpeg
+            if all(c[2] == jpeg.KIND_JPEG for c in s_copied + o_copied):
                 # JPEG on both sides: ONE set of decode launches for the ground and the overhead files of every part (the device
                 # Huffman decoders are bound by a thread's chain of symbols, not by how many files a launch holds)
                 both, _kind, f1 = self._table_side(st, s_copied + o_copied)
                 n_s = sum(int(c[1].shape[0]) for c in s_copied)
                 s_tab, o_tab, f2 = both[:n_s], both[n_s:], None      # (views: a re-decoded file's row is patched in place)
-                st.s_kind = st.o_kind = 1
+                st.s_kind = st.o_kind = KIND_U8_HWC
             else:
                 s_tab, st.s_kind, f1 = self._table_side(st, s_copied)
                 o_tab, st.o_kind, f2 = self._table_side(st, o_copied)

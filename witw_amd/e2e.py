@@ -89,9 +89,9 @@ def _decode_worker(args):
         for pair in blobs:
             for b in pair:
                 f = jpeg.open_file(b.tobytes())
-                k = int(f.info[5])
+                k = int(f.info[jpeg.INFO_BLOCKS])
                 if k not in bufs:
-                    bufs[k] = (np.empty((k, 64), np.int16), np.empty((int(f.info[2]), 64), np.uint16))
+                    bufs[k] = (np.empty((k, 64), np.int16), np.empty((int(f.info[jpeg.INFO_NCOMP]), 64), np.uint16))
                 f.decode_into(*bufs[k])
             n += 1
     return n / (time.perf_counter() - t0)

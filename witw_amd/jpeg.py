@@ -20,9 +20,26 @@ from . import build as _build
 
 _HOST = None
 KIND_JPEG = 2          # packed-batch kind: coefficient blocks (+ raw uint8 images for the files left to Pillow)
-DESC_COLS = 30         # per image: coefficient byte offset, quantisation-table byte offset, 22 info ints, is_raw, channels,
-#                        entropy decoding on the device (1: column 0 is then the offset of the FILE BYTES), plan byte offset, file length,
-#                        restart intervals
+# The packed descriptor, one int64 row per image (pack() writes it, decode_tables / decode_packed_multi read it):
+#   COL_OFFSET     0       byte offset of the entry in the block: coefficient blocks, FILE BYTES (COL_ON_DEVICE) or raw pixels (COL_RAW)
+#   COL_QT         1       byte offset of the quantisation tables (64 uint16 per component)
+#   COL_INFO       2..23   the INFO_INTS ints of witw_jpeg_info_ex (INFO_* below); a raw entry fills COL_H and COL_W only
+#   COL_RAW        24      1: uint8 HWC pixels of a file left to Pillow
+#   COL_CHANNELS   25      ... and their channels
+#   COL_ON_DEVICE  26      1: entropy decoding on the device, the file bytes travelled
+#   COL_PLAN       27      ... byte offset of the entropy plan
+#   COL_FILE_LEN   28      ... file length
+#   COL_INTERVALS  29      ... restart intervals (grid sizing of the device decoder)
+COL_OFFSET, COL_QT, COL_INFO = 0, 1, 2
+COL_RAW, COL_CHANNELS, COL_ON_DEVICE, COL_PLAN, COL_FILE_LEN, COL_INTERVALS = 24, 25, 26, 27, 28, 29
+DESC_COLS = 30
+# the info ints and the plan header as csrc/jpeg_layout.h names them (WITW_JPEG_INFO_* / WITW_JPEG_PLAN_*: tests/test_jpeg.py compares)
+INFO_H, INFO_W, INFO_NCOMP, INFO_HMAX, INFO_VMAX, INFO_BLOCKS = 0, 1, 2, 3, 4, 5
+INFO_COMP, INFO_COMP_STRIDE = 6, 4            # component c: INFO_COMP + INFO_COMP_STRIDE * c + ...
+INFO_COMP_H, INFO_COMP_V, INFO_COMP_BW, INFO_COMP_BH = 0, 1, 2, 3
+INFO_INTS = 22
+PLAN_INTERVALS = 1
+COL_H, COL_W = COL_INFO + INFO_H, COL_INFO + INFO_W
 # Baseline / extended-sequential Huffman files are entropy-decoded ON THE DEVICE (round 6; csrc/jpeg.hip): with restart markers one GPU
 # thread per restart interval (jpeg_huffman_kernel), without them a self-synchronising decode, one workgroup per file
 # (jpeg_selfsync_kernel). The worker only parses the header and scans for markers; the file bytes cross PCIe instead of the
@@ -59,22 +76,14 @@ def host_lib():
     if _HOST is None:
         path = _build.build_host(verbose=False)
         lib = ctypes.CDLL(path)
-        lib.witw_jpeg_info.restype = ctypes.c_int
-        lib.witw_jpeg_info.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib.witw_jpeg_decode_coef.restype = ctypes.c_int
-        lib.witw_jpeg_decode_coef.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
-        lib.witw_jpeg_info_ex.restype = ctypes.c_int
-        lib.witw_jpeg_info_ex.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
-        lib.witw_jpeg_decode_coef_ex.restype = ctypes.c_int
-        lib.witw_jpeg_decode_coef_ex.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        lib.witw_jpeg_entropy_plan_bytes.restype = ctypes.c_longlong
-        lib.witw_jpeg_entropy_plan_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-        lib.witw_jpeg_entropy_plan.restype = ctypes.c_longlong
-        lib.witw_jpeg_entropy_plan.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib.witw_jpeg_entropy_plan_bytes_ex.restype = ctypes.c_longlong
-        lib.witw_jpeg_entropy_plan_bytes_ex.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        lib.witw_jpeg_entropy_plan_ex.restype = ctypes.c_longlong
-        lib.witw_jpeg_entropy_plan_ex.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
+        ptr, size = ctypes.c_void_p, ctypes.c_size_t
+        # every entry has an _ex twin that takes the flags (ACCEPT_*) as one more int; this module calls the twins only
+        for name, res, args in (('witw_jpeg_info', ctypes.c_int, [ptr, size, ptr]),
+                                ('witw_jpeg_decode_coef', ctypes.c_int, [ptr, size, ptr, ptr]),
+                                ('witw_jpeg_entropy_plan_bytes', ctypes.c_longlong, [ptr, size]),
+                                ('witw_jpeg_entropy_plan', ctypes.c_longlong, [ptr, size, ptr, size, ptr])):
+            for fn, a in ((getattr(lib, name), args), (getattr(lib, name + '_ex'), args + [ctypes.c_int])):
+                fn.restype, fn.argtypes = res, a
         _HOST = lib
     return _HOST
 
@@ -89,7 +98,7 @@ class JpegCoef(object):
 
     @property
     def shape(self):          # of the decoded image, HWC
-        return (int(self.info[0]), int(self.info[1]), int(self.info[2]))
+        return (int(self.info[INFO_H]), int(self.info[INFO_W]), int(self.info[INFO_NCOMP]))
 
 
 class JpegFile(JpegCoef):
@@ -105,10 +114,7 @@ class JpegFile(JpegCoef):
     def decode_into(self, coef, qt):
         """coef int16 [blocks, 64], qt uint16 [components, 64]: views of the destination. -> False if the entropy data is bad (or,
         progressive, its scans are illegal or stop short of full precision)."""
-        if self.flags:
-            return host_lib().witw_jpeg_decode_coef_ex(self.data.ctypes.data, self.data.size, coef.ctypes.data, qt.ctypes.data,
-                                                       self.flags) == 0
-        return host_lib().witw_jpeg_decode_coef(self.data.ctypes.data, self.data.size, coef.ctypes.data, qt.ctypes.data) == 0
+        return host_lib().witw_jpeg_decode_coef_ex(self.data.ctypes.data, self.data.size, coef.ctypes.data, qt.ctypes.data, self.flags) == 0
 
     def entropy_plan(self):
         """What the DEVICE needs to entropy-decode this file itself (csrc_host/jpeg_coef.cpp witw_jpeg_entropy_plan: header fields,
@@ -122,7 +128,7 @@ class JpegFile(JpegCoef):
         if n <= 0:
             return None
         plan = np.empty((n,), dtype=np.uint8)
-        qt = np.empty((int(self.info[2]), 64), dtype=np.uint16)
+        qt = np.empty((int(self.info[INFO_NCOMP]), 64), dtype=np.uint16)
         if lib.witw_jpeg_entropy_plan_ex(self.data.ctypes.data, self.data.size, plan.ctypes.data, n, qt.ctypes.data, self.flags) != n:
             return None
         return plan, qt
@@ -136,8 +142,8 @@ class JpegFile(JpegCoef):
         return a[:, :, None] if a.ndim == 2 else a
 
     def _decoded(self):
-        coef = np.empty((int(self.info[5]), 64), dtype=np.int16)
-        qt = np.empty((int(self.info[2]), 64), dtype=np.uint16)
+        coef = np.empty((int(self.info[INFO_BLOCKS]), 64), dtype=np.int16)
+        qt = np.empty((int(self.info[INFO_NCOMP]), 64), dtype=np.uint16)
         if not self.decode_into(coef, qt):
             raise ValueError('corrupt JPEG entropy data')
         return coef, qt
@@ -151,15 +157,11 @@ def open_file(src, progressive=None, h1v2=None):
     file is left to the host decoder. progressive: take progressive files too (None: the module flag PROGRESSIVE); h1v2: take 4:4:0
     files too (None: the module flag SAMPLING_440)."""
     data = np.fromfile(src, dtype=np.uint8) if isinstance(src, (str, os.PathLike)) else np.frombuffer(src, dtype=np.uint8)
-    info = np.zeros(22, dtype=np.int32)
+    info = np.zeros(INFO_INTS, dtype=np.int32)
     flags = (ACCEPT_PROGRESSIVE if (PROGRESSIVE if progressive is None else progressive) else 0) | \
         (ACCEPT_H1V2 if (SAMPLING_440 if h1v2 is None else h1v2) else 0)
-    if flags:
-        rc = host_lib().witw_jpeg_info_ex(data.ctypes.data, data.size, info.ctypes.data, flags)
-        return JpegFile(info, data, progressive=rc == 1, flags=flags) if rc in (0, 1) else None
-    if host_lib().witw_jpeg_info(data.ctypes.data, data.size, info.ctypes.data) != 0:
-        return None
-    return JpegFile(info, data)
+    rc = host_lib().witw_jpeg_info_ex(data.ctypes.data, data.size, info.ctypes.data, flags)      # (1: a progressive file, only under its flag)
+    return JpegFile(info, data, progressive=rc == 1, flags=flags) if rc in (0, 1) else None
 
 
 def read_coef(src, progressive=None, h1v2=None):
@@ -168,11 +170,17 @@ def read_coef(src, progressive=None, h1v2=None):
     f = open_file(src, progressive, h1v2)
     if f is None:
         return None
-    coef = np.empty((int(f.info[5]), 64), dtype=np.int16)
-    qt = np.empty((int(f.info[2]), 64), dtype=np.uint16)
+    coef = np.empty((int(f.info[INFO_BLOCKS]), 64), dtype=np.int16)
+    qt = np.empty((int(f.info[INFO_NCOMP]), 64), dtype=np.uint16)
     if not f.decode_into(coef, qt):
         return None               # truncated / corrupt entropy data: let the host decoder say what it thinks of the file
     return JpegCoef(f.info, coef, qt)
+
+
+def plan_intervals(plan):
+    """The restart intervals of an entropy plan (uint8 array, JpegFile.entropy_plan): header int PLAN_INTERVALS; 1 = a file without
+    restart markers."""
+    return int(plan[4 * PLAN_INTERVALS:4 * PLAN_INTERVALS + 4].view(np.int32)[0])
 
 
 def _shared_bytes(n):
@@ -193,25 +201,25 @@ def pack(images, shared=False, alloc=None):
         if DEVICE_ENTROPY and isinstance(a, JpegFile):
             pl = a.entropy_plan()
             # (a plan of ONE interval = a file without restart markers: the self-synchronising kernel, mode 'all' only)
-            if pl is not None and (DEVICE_ENTROPY in ('all', True) or int(pl[0][4:8].view(np.int32)[0]) > 1):
+            if pl is not None and (DEVICE_ENTROPY in ('all', True) or plan_intervals(pl[0]) > 1):
                 plans[i] = pl
         if i in plans:
             # entropy decoding on the device: the FILE BYTES travel (24 readable bytes behind the end: the kernel reads aligned 8-byte
             # words one ahead of the one it decodes)
             nbytes = int(a.data.size) + 24
-            desc[i, 2:24] = a.info
-            desc[i, 26], desc[i, 28] = 1, int(a.data.size)
-            desc[i, 29] = int(plans[i][0][4:8].view(np.int32)[0])      # restart intervals of the file (grid sizing of the device decoder)
+            desc[i, COL_INFO:COL_RAW] = a.info
+            desc[i, COL_ON_DEVICE], desc[i, COL_FILE_LEN] = 1, int(a.data.size)
+            desc[i, COL_INTERVALS] = plan_intervals(plans[i][0])
         elif isinstance(a, JpegCoef):
-            nbytes = int(a.info[5]) * 128
-            desc[i, 2:24] = a.info
+            nbytes = int(a.info[INFO_BLOCKS]) * 128
+            desc[i, COL_INFO:COL_RAW] = a.info
         else:
             a = np.ascontiguousarray(a)
             if a.dtype != np.uint8 or a.ndim != 3:
                 raise ValueError('jpeg.pack takes JpegCoef / JpegFile objects and uint8 HWC arrays')
             nbytes = a.size
-            desc[i, 2], desc[i, 3], desc[i, 24], desc[i, 25] = a.shape[0], a.shape[1], 1, a.shape[2]
-        desc[i, 0] = off
+            desc[i, COL_H], desc[i, COL_W], desc[i, COL_RAW], desc[i, COL_CHANNELS] = a.shape[0], a.shape[1], 1, a.shape[2]
+        desc[i, COL_OFFSET] = off
         spans.append((off, nbytes))
         # every entry starts on a 128-byte boundary: the device back end addresses coefficient data in 128-byte BLOCKS from the start
         # of the buffer (decode_tables: first block = offset // 128), so a raw image of a file left to Pillow in front of a JPEG
@@ -220,10 +228,10 @@ def pack(images, shared=False, alloc=None):
         off += (nbytes + 127) // 128 * 128
     for i, a in enumerate(images):
         if isinstance(a, JpegCoef):
-            desc[i, 1] = off
-            off += (int(a.info[2]) * 128 + 15) // 16 * 16
+            desc[i, COL_QT] = off
+            off += (int(a.info[INFO_NCOMP]) * 128 + 15) // 16 * 16
     for i in plans:
-        desc[i, 27] = off
+        desc[i, COL_PLAN] = off
         off += (plans[i][0].size + 15) // 16 * 16
     if alloc is not None:
         got = alloc(off)
@@ -235,15 +243,16 @@ def pack(images, shared=False, alloc=None):
         buf = t.numpy()
     for i, a in enumerate(images):
         o, nbytes = spans[i]
+        qt_at = int(desc[i, COL_QT])
         if i in plans:
             plan, qt = plans[i]
             buf[o:o + a.data.size] = a.data
             buf[o + a.data.size:o + nbytes] = 0
-            buf[int(desc[i, 27]):int(desc[i, 27]) + plan.size] = plan
-            buf[int(desc[i, 1]):int(desc[i, 1]) + qt.size * 2] = qt.reshape(-1).view(np.uint8)
+            buf[int(desc[i, COL_PLAN]):int(desc[i, COL_PLAN]) + plan.size] = plan
+            buf[qt_at:qt_at + qt.size * 2] = qt.reshape(-1).view(np.uint8)
         elif isinstance(a, JpegFile):
             coef = buf[o:o + nbytes].view(np.int16).reshape(-1, 64)
-            qt = buf[int(desc[i, 1]):int(desc[i, 1]) + int(a.info[2]) * 128].view(np.uint16).reshape(-1, 64)
+            qt = buf[qt_at:qt_at + int(a.info[INFO_NCOMP]) * 128].view(np.uint16).reshape(-1, 64)
             if not a.decode_into(coef, qt):
                 # damaged entropy data: the file goes to Pillow after all (as the reference and raw=True read it) and rides in the
                 # same span as a raw uint8 image -- the coefficient blocks of an image are never smaller than its pixels
@@ -252,11 +261,11 @@ def pack(images, shared=False, alloc=None):
                     raise ValueError('image %d of the batch: JPEG entropy data is corrupt and the host decoder returned %s %s'
                                      % (i, px.dtype, px.shape))
                 buf[o:o + px.size] = px.reshape(-1)
-                desc[i, 2:24] = 0
-                desc[i, 2], desc[i, 3], desc[i, 24], desc[i, 25] = px.shape[0], px.shape[1], 1, px.shape[2]
+                desc[i, COL_INFO:COL_RAW] = 0
+                desc[i, COL_H], desc[i, COL_W], desc[i, COL_RAW], desc[i, COL_CHANNELS] = px.shape[0], px.shape[1], 1, px.shape[2]
         elif isinstance(a, JpegCoef):
             buf[o:o + nbytes] = a.coef.reshape(-1).view(np.uint8)
-            buf[int(desc[i, 1]):int(desc[i, 1]) + a.qt.size * 2] = a.qt.reshape(-1).view(np.uint8)
+            buf[qt_at:qt_at + a.qt.size * 2] = a.qt.reshape(-1).view(np.uint8)
         else:
             buf[o:o + nbytes] = np.ascontiguousarray(a).reshape(-1)
     return t, torch.from_numpy(desc), KIND_JPEG
@@ -270,23 +279,24 @@ def decode_tables(d):
     offset}, blocks in all, component bytes, output bytes, byte offset of the first quantisation table). Whole-array numpy: a
     per-image Python loop here cost 8 ms per 128 pairs, as much as the bf16 encoders take for them."""
     n = d.shape[0]
-    if (d[:, 0] % 128).any():
+    if (d[:, COL_OFFSET] % 128).any():
         raise ValueError('jpeg: a coefficient entry does not start on a 128-byte boundary of the packed block')
-    H, W, ncomp, hmax, vmax = (d[:, k] for k in range(2, 7))
-    qt_base = int(d[:, 1].min())
-    bw, bh = d[:, [10, 14, 18]], d[:, [11, 15, 19]]
+    H, W, ncomp, hmax, vmax = (d[:, COL_INFO + k] for k in (INFO_H, INFO_W, INFO_NCOMP, INFO_HMAX, INFO_VMAX))
+    qt_base = int(d[:, COL_QT].min())
+    comp = COL_INFO + INFO_COMP + INFO_COMP_STRIDE * np.arange(3)      # first column of each component's record
+    bw, bh = d[:, comp + INFO_COMP_BW], d[:, comp + INFO_COMP_BH]
     valid = np.arange(3)[None, :] < ncomp[:, None]
     nb = bw * bh * valid                                                  # blocks per (image, component)
-    cb = (d[:, 0] // 128)[:, None] + np.cumsum(nb, axis=1) - nb             # coefficient blocks are 128 bytes
+    cb = (d[:, COL_OFFSET] // 128)[:, None] + np.cumsum(nb, axis=1) - nb             # coefficient blocks are 128 bytes
     flat = nb[valid]
     blk_off = np.cumsum(flat) - flat                                      # image-major, component-minor
     plane_first = np.zeros((n, 3), dtype=np.int64)
     plane_first[valid] = blk_off
-    qti = ((d[:, 1] - qt_base) // 128)[:, None] + np.arange(3)[None, :]
+    qti = ((d[:, COL_QT] - qt_base) // 128)[:, None] + np.arange(3)[None, :]
     planes = np.stack([cb[valid], qti[valid], blk_off * 64, bw[valid], bh[valid], blk_off], axis=1).astype(np.int64)
-    # (1, 2) = 4:4:0, taken only as the host parser describes such a file -- the luma component itself sampled 1 x 2 (info[6:8]); a row
+    # (1, 2) = 4:4:0, taken only as the host parser describes such a file -- the luma component itself sampled 1 x 2 (its INFO_COMP_H, INFO_COMP_V); a row
     # that claims the sampling without it was not written by witw_jpeg_info_ex
-    is_440 = (hmax == 1) & (vmax == 2) & (d[:, 8] == 1) & (d[:, 9] == 2)
+    is_440 = (hmax == 1) & (vmax == 2) & (d[:, comp[0] + INFO_COMP_H] == 1) & (d[:, comp[0] + INFO_COMP_V] == 2)
     mode = np.where((hmax == 1) & (vmax == 1), 0, np.where((hmax == 2) & (vmax == 1), 1, np.where((hmax == 2) & (vmax == 2), 2,
                                                                                                   np.where(is_440, 5, -1))))
     if (mode < 0).any():
@@ -308,8 +318,8 @@ def decode_tables(d):
 
 
 def _decode_group(dev, d, coef_ptr, qt_ptr):
-    """dequantisation + inverse DCT + upsampling + colour conversion of the JPEG entries d (descriptor rows whose column 0 is the
-    byte offset of their coefficient blocks from coef_ptr, column 1 that of their quantisation tables from qt_ptr) -> (tensors to keep
+    """dequantisation + inverse DCT + upsampling + colour conversion of the JPEG entries d (descriptor rows whose COL_OFFSET is the
+    byte offset of their coefficient blocks from coef_ptr, COL_QT that of their quantisation tables from qt_ptr) -> (tensors to keep
     alive, device address of every decoded image, components per image). Two launches."""
     from . import _lib, ops
     try:
@@ -328,6 +338,101 @@ def _decode_group(dev, d, coef_ptr, qt_ptr):
     return [plane_t, image_t, comp, rgb], rgb.data_ptr() + images[:, 11], images[:, 2]
 
 
+def _rebase(parts):
+    """The descriptor rows of all parts as one table whose byte offsets (COL_OFFSET, COL_QT, COL_PLAN) count from the LOWEST block
+    (allocations are 512-byte aligned) -> (address of that block, rows int64 [sum B, DESC_COLS], part of each row, each row's
+    COL_OFFSET within its own part)."""
+    from . import _lib
+    ref = min(int(p[0].data_ptr()) for p in parts)
+    ds, part_of, off0 = [], [], []
+    for k, (dbuf, desc, _hb) in enumerate(parts):
+        dk = np.array(desc.numpy() if isinstance(desc, torch.Tensor) else desc, dtype=np.int64, copy=True)
+        delta = int(dbuf.data_ptr()) - ref
+        if delta % 128:
+            # the back end addresses coefficient blocks and quantisation tables on a 128-byte grid from the lowest block
+            # (decode_tables): a part off that grid would decode with another file's tables
+            raise _lib.WitwError('jpeg: part %d of the batch sits %d bytes from the lowest, not a multiple of 128' % (k, delta))
+        off0.append(dk[:, COL_OFFSET].copy())
+        for c in (COL_OFFSET, COL_QT, COL_PLAN):
+            dk[:, c] += delta
+        ds.append(dk)
+        part_of.append(np.full((dk.shape[0],), k, dtype=np.int64))
+    return ref, np.concatenate(ds), np.concatenate(part_of), np.concatenate(off0)
+
+
+def _entropy_launch(dev, rows, launch, errors, at, keep):
+    """One launch of a device entropy decoder: rows (int64, one per file) go up through pinned memory, launch(address of the row table,
+    files, address of their int32 damage flags) runs the kernel, and the flags land at positions `at` of `errors` -- written there
+    directly when the launch holds every file of `errors`."""
+    files_t = torch.from_numpy(np.ascontiguousarray(rows)).pin_memory().to(dev, non_blocking=True)
+    e = errors if at.size == errors.numel() else torch.zeros((int(at.size),), dtype=torch.int32, device=dev)
+    launch(files_t.data_ptr(), int(at.size), e.data_ptr())
+    if e is not errors:
+        errors[torch.from_numpy(at).to(dev)] = e
+    keep += [files_t, e]
+
+
+def _entropy_decode(dev, d, ref, keep):
+    """Entropy decoding on the device of the entries d that travelled as file bytes (offsets from ref) -> (coef int16: the files'
+    coefficient blocks one after another, first block of each file, errors int32 per file). Files with restart markers: one thread
+    per interval; files without (ONE interval of more than SELFSYNC_MIN_BLOCKS blocks): the self-synchronising kernel, one workgroup
+    per file."""
+    from . import _lib, ops
+    lib, st = _lib.load(), ops._stream()
+    blocks = d[:, COL_INFO + INFO_BLOCKS]
+    first = np.cumsum(blocks) - blocks
+    coef = torch.zeros((int(blocks.sum()) * 64,), dtype=torch.int16, device=dev)
+    errors = torch.zeros((d.shape[0],), dtype=torch.int32, device=dev)
+    sync = (d[:, COL_INTERVALS] == 1) & (blocks > SELFSYNC_MIN_BLOCKS)
+    rows = np.stack([ref + d[:, COL_OFFSET], ref + d[:, COL_PLAN], coef.data_ptr() + first * 128, d[:, COL_FILE_LEN]], axis=1).astype(np.int64)
+    ir, isy = np.nonzero(~sync)[0], np.nonzero(sync)[0]
+    if ir.size:
+        most = int(d[ir, COL_INTERVALS].max())
+        _entropy_launch(dev, rows[ir], lambda files, n, err: _lib.check(lib.witw_jpeg_huffman(files, n, most, err, st), 'witw_jpeg_huffman'),
+                        errors, ir, keep)
+    if isy.size:
+        sizes = (d[isy, COL_FILE_LEN] + 32 + 7) // 8 * 8
+        soff = np.cumsum(sizes) - sizes
+        scratch = torch.empty((int(sizes.sum()),), dtype=torch.uint8, device=dev)
+        srows = np.concatenate([rows[isy], (scratch.data_ptr() + soff)[:, None], np.zeros((isy.size, 1), np.int64)], axis=1).astype(np.int64)
+        # threads per file: 1024 when the launch holds a large file (shorter subsequences: 113 KB files 1.3 against 1.4 ms per 128 at
+        # 512 threads), 512 otherwise (22 KB files: 0.76 against 0.89 ms -- more rounds than the shorter subsequences save)
+        env_t = os.environ.get('WITW_SELFSYNC_THREADS')
+        threads = (1024 if int(env_t) >= 1024 else 512 if int(env_t) >= 512 else 256) if env_t else \
+            (1024 if int(d[isy, COL_FILE_LEN].max()) >= SELFSYNC_WIDE_BYTES else 512)
+        _entropy_launch(dev, srows, lambda files, n, err: _lib.check(lib.witw_jpeg_huffman_selfsync_threads(files, n, threads, err, st),
+                                                                     'witw_jpeg_huffman_selfsync_threads'), errors, isy, keep)
+        keep.append(scratch)
+    return coef, first, errors
+
+
+def _deferred_repair(dev, parts, d, part_of, off0, dv, errors, table, keep):
+    """A file whose entropy-coded data is damaged is read by the reference through libjpeg, which recovers what it can (with a
+    warning); the host path hands such a file to Pillow inside pack(). On the device the damage shows only once the kernel has run:
+    queue a copy of the flags (4 bytes per file; it waits for THIS stream's staging work, which the drivers run on the copy stream one
+    batch ahead of the encoders) -> finish(): waits for it -- the one host wait -- and lets Pillow decode the flagged files from the
+    bytes that are still in the host block -- the same image, by the same decoder, as on the host path -- patching `table` in place."""
+    flags_host = torch.empty((int(dv.size),), dtype=torch.int32).pin_memory()
+    flags_host.copy_(errors, non_blocking=True)
+    flags_ready = torch.cuda.Event()
+    flags_ready.record(torch.cuda.current_stream(dev))
+
+    def finish():
+        flags_ready.synchronize()
+        for j in np.nonzero(flags_host.numpy())[0]:
+            i = int(dv[j])
+            hb = parts[int(part_of[i])][2]
+            if hb is None:
+                continue
+            hb = hb.numpy() if isinstance(hb, torch.Tensor) else np.asarray(hb)
+            px = np.array(JpegFile(None, hb[int(off0[i]):int(off0[i]) + int(d[i, COL_FILE_LEN])]).pillow())      # a writable copy (from_numpy warns on Pillow's read-only view)
+            t = torch.from_numpy(px).to(dev)
+            keep.append(t)
+            table[i] = (t.data_ptr(), px.shape[0], px.shape[1], 0, px.shape[2])
+            REPAIRED[0] += 1
+    return finish
+
+
 def decode_packed_multi(parts, defer=False):
     """parts: [(dbuf, desc, host_buf or None), ...] = the packed blocks of ONE side of a batch, each on the GPU with its HOST descriptor
     table (a batch arrives in pieces when the loader hands out quarter batches: DevicePrefetcher(group=4)) -> (tensors to keep alive,
@@ -340,34 +445,15 @@ def decode_packed_multi(parts, defer=False):
     finish: None, or (defer=True, some part came with its host block) a callable that reads the damage flags of the device decoder --
     the one host wait of the call -- and lets Pillow re-decode flagged files, patching `table` in place; with defer=False that has
     happened on return."""
-    from . import _lib, ops
     dev = parts[0][0].device
-    ref = min(int(p[0].data_ptr()) for p in parts)      # offsets of every part are re-based to the lowest block (allocations are 512-byte aligned)
-    ds, part_of, off0 = [], [], []
-    for k, (dbuf, desc, _hb) in enumerate(parts):
-        dk = np.array(desc.numpy() if isinstance(desc, torch.Tensor) else desc, dtype=np.int64, copy=True)
-        delta = int(dbuf.data_ptr()) - ref
-        if delta % 128:
-            # the back end addresses coefficient blocks and quantisation tables on a 128-byte grid from the lowest block
-            # (decode_tables): a part off that grid would decode with another file's tables
-            raise _lib.WitwError('jpeg: part %d of the batch sits %d bytes from the lowest, not a multiple of 128' % (k, delta))
-        off0.append(dk[:, 0].copy())
-        dk[:, 0] += delta
-        dk[:, 1] += delta
-        if dk.shape[1] > 27:
-            dk[:, 27] += delta
-        ds.append(dk)
-        part_of.append(np.full((dk.shape[0],), k, dtype=np.int64))
-    d, part_of, off0 = np.concatenate(ds), np.concatenate(part_of), np.concatenate(off0)
-    B = d.shape[0]
-    table = np.zeros((B, 5), dtype=np.int64)
-    keep = []
-    finish = None
-    is_raw = d[:, 24] != 0
-    on_dev = (d[:, 26] != 0) & ~is_raw if d.shape[1] > 26 else np.zeros((B,), dtype=bool)
-    table[:, 1], table[:, 2] = d[:, 2], d[:, 3]
-    table[is_raw, 0] = ref + d[is_raw, 0]
-    table[is_raw, 4] = d[is_raw, 25]
+    ref, d, part_of, off0 = _rebase(parts)
+    table = np.zeros((d.shape[0], 5), dtype=np.int64)
+    keep, finish = [], None
+    is_raw = d[:, COL_RAW] != 0
+    on_dev = (d[:, COL_ON_DEVICE] != 0) & ~is_raw
+    table[:, 1], table[:, 2] = d[:, COL_H], d[:, COL_W]
+    table[is_raw, 0] = ref + d[is_raw, COL_OFFSET]
+    table[is_raw, 4] = d[is_raw, COL_CHANNELS]
     jp = np.nonzero(~is_raw & ~on_dev)[0]
     if jp.size:
         k, addr, ncomp = _decode_group(dev, d[jp], ref, ref)
@@ -375,72 +461,16 @@ def decode_packed_multi(parts, defer=False):
         table[jp, 0], table[jp, 4] = addr, ncomp
     dv = np.nonzero(on_dev)[0]
     if dv.size:
-        blocks = d[dv, 7]                                        # info[5]: coefficient blocks of the file
-        first = np.cumsum(blocks) - blocks
-        coef = torch.zeros((int(blocks.sum()) * 64,), dtype=torch.int16, device=dev)
-        errors = torch.zeros((int(dv.size),), dtype=torch.int32, device=dev)
-        # files with restart markers: one thread per interval; files without (ONE interval of more than SELFSYNC_MIN_BLOCKS blocks):
-        # the self-synchronising kernel, one workgroup per file
-        sync = (d[dv, 29] == 1) & (blocks > SELFSYNC_MIN_BLOCKS)
-        rows = np.stack([ref + d[dv, 0], ref + d[dv, 27], coef.data_ptr() + first * 128, d[dv, 28]], axis=1).astype(np.int64)
-        ir = np.nonzero(~sync)[0]
-        if ir.size:
-            files_t = torch.from_numpy(np.ascontiguousarray(rows[ir])).pin_memory().to(dev, non_blocking=True)
-            e_r = errors if ir.size == dv.size else torch.zeros((int(ir.size),), dtype=torch.int32, device=dev)
-            _lib.check(_lib.load().witw_jpeg_huffman(files_t.data_ptr(), int(ir.size), int(d[dv[ir], 29].max()), e_r.data_ptr(), ops._stream()),
-                       'witw_jpeg_huffman')
-            if e_r is not errors:
-                errors[torch.from_numpy(ir).to(dev)] = e_r
-            keep += [files_t, e_r]
-        isy = np.nonzero(sync)[0]
-        if isy.size:
-            sizes = (d[dv[isy], 28] + 32 + 7) // 8 * 8
-            soff = np.cumsum(sizes) - sizes
-            scratch = torch.empty((int(sizes.sum()),), dtype=torch.uint8, device=dev)
-            srows = np.concatenate([rows[isy], (scratch.data_ptr() + soff)[:, None], np.zeros((isy.size, 1), np.int64)], axis=1).astype(np.int64)
-            files_s = torch.from_numpy(np.ascontiguousarray(srows)).pin_memory().to(dev, non_blocking=True)
-            e_s = errors if isy.size == dv.size else torch.zeros((int(isy.size),), dtype=torch.int32, device=dev)
-            # threads per file: 1024 when the launch holds a large file (shorter subsequences: 113 KB files 1.3 against 1.4 ms per 128 at
-            # 512 threads), 512 otherwise (22 KB files: 0.76 against 0.89 ms -- more rounds than the shorter subsequences save)
-            env_t = os.environ.get('WITW_SELFSYNC_THREADS')
-            threads = (1024 if int(env_t) >= 1024 else 512 if int(env_t) >= 512 else 256) if env_t else \
-                (1024 if int(d[dv[isy], 28].max()) >= SELFSYNC_WIDE_BYTES else 512)
-            _lib.check(_lib.load().witw_jpeg_huffman_selfsync_threads(files_s.data_ptr(), int(isy.size), threads, e_s.data_ptr(), ops._stream()),
-                       'witw_jpeg_huffman_selfsync_threads')
-            if e_s is not errors:
-                errors[torch.from_numpy(isy).to(dev)] = e_s
-            keep += [files_s, e_s, scratch]
-        dd = d[dv].copy()
-        dd[:, 0] = first * 128                                   # where each file's coefficient blocks sit in `coef`
+        dd = d[dv]
+        coef, first, errors = _entropy_decode(dev, dd, ref, keep)
+        dd[:, COL_OFFSET] = first * 128                          # where each file's coefficient blocks sit in `coef`
         k, addr, ncomp = _decode_group(dev, dd, coef.data_ptr(), ref)
         keep += k + [coef, errors]
         table[dv, 0], table[dv, 4] = addr, ncomp
         _ERRORS.append(errors)
         del _ERRORS[:-64]
         if CHECK_ERRORS and any(p[2] is not None for p in parts):
-            # A file whose entropy-coded data is damaged is read by the reference through libjpeg, which recovers what it can (with
-            # a warning); the host path hands such a file to Pillow inside pack(). Here the damage shows only once the kernel has
-            # run: look at the flags (a 4-byte-per-file copy; it waits for THIS stream's staging work, which the drivers run on the
-            # copy stream one batch ahead of the encoders) and let Pillow decode the flagged files from the bytes that are still in
-            # the host block -- the same image, by the same decoder, as on the host path.
-            flags_host = torch.empty((int(dv.size),), dtype=torch.int32).pin_memory()
-            flags_host.copy_(errors, non_blocking=True)
-            flags_ready = torch.cuda.Event()
-            flags_ready.record(torch.cuda.current_stream(dev))
-
-            def finish():
-                flags_ready.synchronize()
-                for j in np.nonzero(flags_host.numpy())[0]:
-                    i = int(dv[j])
-                    hb = parts[int(part_of[i])][2]
-                    if hb is None:
-                        continue
-                    hb = hb.numpy() if isinstance(hb, torch.Tensor) else np.asarray(hb)
-                    px = np.array(JpegFile(None, hb[int(off0[i]):int(off0[i]) + int(d[i, 28])]).pillow())      # a writable copy (from_numpy warns on Pillow's read-only view)
-                    t = torch.from_numpy(px).to(dev)
-                    keep.append(t)
-                    table[i] = (t.data_ptr(), px.shape[0], px.shape[1], 0, px.shape[2])
-                    REPAIRED[0] += 1
+            finish = _deferred_repair(dev, parts, d, part_of, off0, dv, errors, table, keep)
     if finish is not None and not defer:
         finish()
         finish = None
@@ -472,7 +502,7 @@ def decode(images, device):
     for i in range(len(images)):
         H, W, C = int(table[i, 1]), int(table[i, 2]), int(table[i, 4])
         src = next(t for t in [dbuf] + keep if t.dtype == torch.uint8 and t.data_ptr() <= int(table[i, 0]) < t.data_ptr() + max(1, t.numel())
-                   and int(table[i, 0]) + H * W * C <= t.data_ptr() + t.numel() and (t is dbuf) == bool(desc[i, 24]))
+                   and int(table[i, 0]) + H * W * C <= t.data_ptr() + t.numel() and (t is dbuf) == bool(desc[i, COL_RAW]))
         o = int(table[i, 0]) - src.data_ptr()
         out.append(src.reshape(-1)[o:o + H * W * C].reshape(H, W, C).clone())      # (a repaired image is an H x W x C tensor)
     return out
