@@ -797,6 +797,27 @@ int witw_jpeg_huffman_selfsync(const void* files, int n_files, int* errors, void
 /* The same with the threads per file chosen by the caller (256, 512 or 1024; jpeg.decode_packed_multi: 1024 when the launch holds a file
  * of 48 KB or more, else 512 -- larger files gain from shorter subsequences, smaller ones lose to the extra rounds). */
 int witw_jpeg_huffman_selfsync_threads(const void* files, int n_files, int threads, int* errors, void* stream);
+/* The scans of PROGRESSIVE files on the device (opt-in: jpeg.PROGRESSIVE_DEVICE; off, such files are Huffman-decoded by the loader
+ * worker or left to Pillow as before): ONE STAGE of every file of the launch. A scan depends on exactly the earlier scans that coded
+ * the same (component, coefficient) cells; the host's scan plan (witw_jpeg_scan_plan_ex in libwitw_jpeg.so: a byte scan, every check
+ * that needs no Huffman decoding; layout 'JPW2' in witw_amd/csrc/jpeg_layout.h) gives each scan its stage = 0 where no earlier scan
+ * coded one of its cells, else 1 + the largest stage among those that did (at most 14 stages; libjpeg's usual ten scans: three). The
+ * caller launches stage 0, 1, ... up to the largest stage of the batch ON ONE STREAM: the order of the launches is the only
+ * synchronisation between stages. files: DEVICE int64 [n_files][4] as witw_jpeg_huffman takes them = {file bytes (8-byte aligned, 24
+ * readable bytes behind the end), scan plan (4-byte aligned), coefficient area int16 [blocks][64], zero-filled by the caller BEFORE
+ * stage 0 and left alone between the stages, file length}; max_scans (1..64) / max_segments: the largest scan count of a file and
+ * the largest segment count (restart intervals) of a scan in the launch -- grid sizing: a workgroup per (file, scan slot, 128
+ * segments); a workgroup whose scan is of another stage, or past the file's last, leaves at once. One thread decodes one segment
+ * (a file without restart markers: one thread per scan), coefficients are read and written as 16-bit cells only. errors: DEVICE int32
+ * [n_files], zeroed by the caller before stage 0: 1 where the entropy-coded data of a scan is damaged (an invalid code, a DC size
+ * above 15, a run past Se, a refinement symbol of size other than 1, bits taken from behind a segment's data: what
+ * witw_jpeg_decode_coef_ex refuses with -3), 2 for a plan without the magic or with a scan record that cannot be walked. Every loop
+ * bound and block index comes from the plan and is held under the plan's block count; nothing read from the entropy-coded data
+ * indexes memory unchecked. After the last stage an unflagged file holds the coefficients witw_jpeg_decode_coef_ex writes, bit for
+ * bit. Measured (profiles/jpeg_progressive_device.json): 128 files of 512 x 512 without restart markers, three stages,
+ * 166 ms of device time against 1.16 ms for witw_jpeg_huffman_selfsync_threads on their sequential twins -- one thread walks a whole
+ * scan; end to end slower than decoding the scans in the loader workers, hence opt-in. Files with restart markers were not measured. */
+int witw_jpeg_progressive_stage(const void* files, int n_files, int stage, int max_scans, int max_segments, int* errors, void* stream);
 
 #ifdef __cplusplus
 }

@@ -185,6 +185,7 @@ SIGNATURES = {
     'witw_jpeg_huffman': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'witw_jpeg_huffman_selfsync': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     'witw_jpeg_huffman_selfsync_threads': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'witw_jpeg_progressive_stage': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'witw_rotate_nearest': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     'witw_baseline_rotate_batched': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     'witw_baseline_roll_rows_batched': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),

@@ -10,6 +10,7 @@
 // Byte-identical to Pillow's decode: tests/test_jpeg*.py (fixtures under tests/golden/jpeg/ + files written at test time).
 #include "common.h"
 #include "jpeg_layout.h"      // the entropy plan: every plan index below is one of its names
+#include "jpeg_entropy.h"     // the bit reader, the tables in the LDS and the Huffman look-up (shared with jpeg_progressive.hip and a host build)
 #include <stdlib.h>
 #include <type_traits>
 
@@ -178,16 +179,6 @@ __global__ __launch_bounds__(256) void jpeg_to_rgb_kernel(const unsigned char* _
 // Integer / byte work, latency-bound per thread (a table look-up and a few shifts per symbol); nothing here is MFMA- or
 // HBM-shaped. A wave pays for every path ANY of its 64 lanes takes, so the rare paths are kept short: four input bytes at a time while
 // no FF is among them, codes longer than the look-up by seven compares instead of a loop, the zig-zag order from the LDS. Same coefficients, bit for bit, as witw_jpeg_decode_coef (tests/test_jpeg_gpu.py).
-constexpr int HUFF_LOOK = 11;       // bits of the first-step look-up: 4 KB per table. Codes longer than that are a fraction of a per cent of the
-                                    // symbols of a photograph -- with 9 bits (2-3 %) one of a wave's 64 lanes needed the second step on most symbols
-struct HuffLds {
-    unsigned short look[1 << HUFF_LOOK];      // prefix -> (code length << 8) | symbol; 0: the code is longer than HUFF_LOOK bits
-    int valoff[17];                // symbol index of the first code of a length minus that code
-    unsigned lim[17];              // lim[L] = the first 16-bit left-aligned value ABOVE every code of length <= L (non-decreasing; a length
-                                   // without codes repeats its predecessor's; lim[0] = 0): a code's length is 1 + the number of limits it reaches
-    unsigned char sym[256];
-};
-
 struct JpegFileDev {               // int64 x 4 per file
     long long bytes;               // address of the file bytes (8-byte aligned, at least 24 readable bytes behind the end)
     long long plan;                // address of the plan (witw_jpeg_entropy_plan)
@@ -198,139 +189,6 @@ struct JpegFileDev {               // int64 x 4 per file
 __constant__ unsigned char kZigZag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// Addresses that arrive as integers (descriptor rows) carry no address space: dereferenced as plain pointers they become FLAT accesses,
-// which count on the LDS counter as well as on the memory counter. The Huffman kernels name the space of everything they touch.
-#define WITW_AS_GLOBAL __attribute__((address_space(1)))
-#define WITW_AS_LDS __attribute__((address_space(3)))
-typedef const WITW_AS_GLOBAL unsigned long long* GlobalWords;
-typedef const WITW_AS_LDS unsigned long long* LdsWords;      // a copy of the bytes in the LDS (jpeg_huffman_kernel)
-
-template <bool STUFFED, typename WP = GlobalWords>
-struct BitReaderT {                // STUFFED: over the file's bytes of one restart interval: FF 00 -> FF on the fly, any other FF xx ends the
-                                   // data; !STUFFED: over an unstuffed copy (jpeg_selfsync_kernel), positions are plain bit indices
-    WP words;
-    unsigned pos, end;             // byte offsets from `words`
-    unsigned long long cache;      // the aligned 8 bytes that hold byte `pos`
-    unsigned long long ahead;      // ... and the 8 bytes behind them, requested when `cache` was taken (the stream is read in order:
-                                   // the load's round trip runs under the decoding of the current word instead of in front of the next)
-    unsigned cidx;                 // which 8-byte word `cache` is (0xffffffff: none)
-    unsigned long long buf;        // bits, left-aligned
-    int n;                         // valid bits in buf
-    int starved;                   // zero bytes fed behind the end of the data
-
-    __device__ __forceinline__ unsigned raw(unsigned p) {
-        if ((p >> 3) != cidx) {
-            const unsigned w = p >> 3;
-            cache = (w == cidx + 1u) ? ahead : words[w];
-            cidx = w;
-            ahead = words[w + 1u];
-        }
-        return (unsigned)(cache >> (8 * (p & 7))) & 0xffu;
-    }
-    __device__ __forceinline__ unsigned window32() {      // the four bytes at `pos`, first byte lowest
-        const unsigned w = pos >> 3;
-        if (w != cidx) {
-            cache = (w == cidx + 1u) ? ahead : words[w];
-            cidx = w;
-            ahead = words[w + 1u];
-        }
-        const unsigned s = (pos & 7u) * 8u;
-        unsigned w32 = (unsigned)(cache >> s);
-        if (s > 32u) w32 |= (unsigned)(ahead << (64u - s));
-        return w32;
-    }
-    // Called with fewer than 32 valid bits, tops up to at least 32. In a wave of 64 readers every path ANY lane takes is paid by all, on
-    // nearly every symbol, so the common step is short and branch-free: up to FOUR bytes at once.
-    //   !STUFFED: always four (behind the end of the copy lie zero bytes; the position simply runs on);
-    //   STUFFED: the bytes in front of the first FF of the four (all four when there is none), never past `end`; only an FF at the very
-    //   position -- a stuffed FF 00 or a marker -- and the end of the data go byte by byte.
-    __device__ __forceinline__ void fill() {
-        if (!STUFFED) {
-            buf |= (unsigned long long)__builtin_bswap32(window32()) << (32 - n);
-            n += 32;
-            pos += 4u;
-            return;
-        }
-        if (pos < end) {
-            const unsigned w32 = window32();
-            const unsigned ff = ((~w32 - 0x01010101u) & w32) & 0x80808080u;      // bit 7 of every FF byte (exact for the lowest one)
-            unsigned k = ff ? (unsigned)__builtin_ctz(ff) >> 3 : 4u;
-            k = min(k, end - pos);
-            if (k) {
-                const unsigned v = __builtin_bswap32(w32) >> (32u - 8u * k);
-                buf |= (unsigned long long)v << (64 - n - 8 * (int)k);
-                n += 8 * (int)k;
-                pos += k;
-            }
-        }
-        while (n < 32) {
-            unsigned b = 0;
-            if (pos < end) {
-                b = raw(pos);
-                if (b == 0xffu) {
-                    const unsigned b2 = pos + 1 < end ? raw(pos + 1) : 0xd9u;
-                    if (b2 == 0u) pos += 2;                    // a stuffed FF
-                    else { end = pos; b = 0; ++starved; }      // a marker (the next interval's RSTn, or EOI): the data ends here
-                } else {
-                    ++pos;
-                }
-            } else {
-                ++starved;
-            }
-            buf |= (unsigned long long)b << (56 - n);
-            n += 8;
-        }
-    }
-    __device__ __forceinline__ int take(int k) {   // k in 0..16 (0: nothing, returns 0), caller has >= 32 valid bits
-        const int v = (int)((buf >> 1) >> (63 - k));
-        buf <<= k;
-        n -= k;
-        return v;
-    }
-    __device__ __forceinline__ int get(int k) {    // k in 1..16, caller has >= 32 valid bits
-        const int v = (int)(buf >> (64 - k));
-        buf <<= k;
-        n -= k;
-        return v;
-    }
-    __device__ __forceinline__ void start(WP base, unsigned byte_pos, unsigned byte_end) {
-        words = base;
-        pos = byte_pos; end = byte_end;
-        cidx = 0xfffffff0u; cache = 0; ahead = 0; buf = 0; n = 0; starved = 0;
-    }
-    // !STUFFED: index of the next unread bit (zero bytes fed behind the end of the data count as read: the position keeps advancing)
-    __device__ __forceinline__ unsigned bit_pos() const { return (pos + (unsigned)starved) * 8u - (unsigned)n; }
-};
-
-template <typename BR, typename HP>      // HP: pointer to a HuffLds (jpeg_huffman_kernel: typed as an LDS pointer -- a pointer the compiler cannot place becomes a flat access)
-__device__ __forceinline__ int huff_decode(BR& b, HP hp) {      // caller has >= 32 valid bits; -1: invalid code
-    auto& h = *hp;
-    const unsigned e = h.look[(unsigned)(b.buf >> (64 - HUFF_LOOK))];
-    if (e) {
-        const int len = (int)(e >> 8);
-        b.buf <<= len;
-        b.n -= len;
-        return (int)(e & 255u);
-    }
-    // longer than the look-up: the length by comparing against the limits of the remaining lengths, no loop
-    const unsigned c16 = (unsigned)(b.buf >> 48);
-    int len = HUFF_LOOK + 1, vo = h.valoff[HUFF_LOOK + 1];
-#pragma unroll
-    for (int L = HUFF_LOOK + 1; L < 16; ++L) {
-        const bool above = c16 >= h.lim[L];
-        len += above ? 1 : 0;
-        vo = above ? h.valoff[L + 1] : vo;
-    }
-    if (c16 >= h.lim[16]) return -1;
-    const int code = (int)(c16 >> (16 - len));
-    b.buf <<= len;
-    b.n -= len;
-    return h.sym[(code + vo) & 255];
-}
-
-__device__ __forceinline__ int jpeg_extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
-__device__ __forceinline__ int jpeg_extend0(int v, int s) { return v < ((1 << s) >> 1) ? v - (1 << s) + 1 : v; }      // the same, and 0 for s = 0 (v = 0)
 
 // The four decoding tables (DC slot 0, 1, AC slot 0, 1) from the DHT counts / symbols of the plan: threads 0-3 assign the canonical codes
 // of one table each (16 lengths), then all threads fill the 9-bit look-ups. Ends with a workgroup barrier.

@@ -1,4 +1,4 @@
-// The two binary layouts the JPEG data path shares between the host parser (csrc_host/jpeg_coef.cpp), the device entropy decoders
+// The binary layouts the JPEG data path shares between the host parser (csrc_host/jpeg_coef.cpp), the device entropy decoders
 // (csrc/jpeg.hip) and the Python side (witw_amd/jpeg.py, which repeats the names it uses; tests/test_jpeg.py holds them to this file).
 // Constants only: plain C++ for host and device. Every value is written out as a number (`NAME = value`): the test reads them as text.
 #pragma once
@@ -41,6 +41,55 @@ enum {
     WITW_JPEG_PLAN_AC_STRIDE = 272,
     WITW_JPEG_PLAN_TABLE_SYMS = 16,             // a table's symbols sit behind its 16 counts
     WITW_JPEG_PLAN_FIXED = 736                  // the interval offsets (uint32 each); a plan is FIXED + 4 * intervals bytes
+};
+
+// ---- the scan plan of a PROGRESSIVE file (witw_jpeg_scan_plan_ex writes it, jpeg_progressive_kernel reads it beside the file bytes).
+// A magic of its own; the frame part of the header (MCU grid, components, per component h, v, blocks wide, blocks high, first block)
+// sits where the 'JPW1' header has it (WITW_JPEG_PLAN_MCUX .. WITW_JPEG_PLAN_COMP records; the two table-slot fields stay 0):
+//   int32[0] magic 'JPW2', [1] scans, [2] segments of all scans, [3..26] as 'JPW1', [27] stages, [28] the largest segment count of a scan,
+//   [29] coefficient blocks of the file (every block index is held under it), [30] the plan's size in bytes, [31] 0;
+//   byte 128: PROG_MAX_SCANS scan records of PROG_SCAN_INTS int32 each (scans past the file's last: zero):
+//     components in the scan, their indices (4 slots), Ss, Se, Ah, Al, the walk -- units per row and rows of units (an interleaved scan:
+//     the MCU grid; a scan of one component: that component's own ceil(w_c / 8) x ceil(h_c / 8) blocks over its pitch `blocks wide`) --,
+//     units per restart interval (0: none, one segment), stage, byte offset in the plan of the scan's Huffman tables (a first DC scan: one
+//     DC table per scan component, PLAN_DC_STRIDE bytes each; an AC scan: one AC table of PLAN_AC_STRIDE bytes; a DC refinement: none,
+//     0), byte offset in the plan of its segment records, their number, end of its entropy-coded data (byte offset in the file);
+//   behind the scan records, scan by scan: the tables in force at that scan (16 counts + symbols, as in 'JPW1'), then a record of
+//     PROG_SEG_INTS uint32 per segment = (scan, restart interval): byte offset in the file of its first entropy-coded byte, first unit,
+//     units. A segment's data ends at the next marker.
+// stage(scan) = 0 if no earlier scan coded any of its (component, coefficient) cells, else 1 + the largest stage among them: scans of
+// one stage touch disjoint cells and are decoded in one launch. Files of more than PROG_MAX_SCANS scans get no plan.
+enum {
+    WITW_JPEG_PLAN_PROG_MAGIC = 0x3257504A,     // 'JPW2'
+    WITW_JPEG_PLAN_PROG_SCANS = 1,
+    WITW_JPEG_PLAN_PROG_SEGMENTS = 2,
+    WITW_JPEG_PLAN_PROG_STAGES = 27,
+    WITW_JPEG_PLAN_PROG_MAX_SEGMENTS = 28,      // the largest segment count of a scan
+    WITW_JPEG_PLAN_PROG_BLOCKS = 29,
+    WITW_JPEG_PLAN_PROG_BYTES = 30,
+    WITW_JPEG_PLAN_PROG_MAX_SCANS = 64,
+    WITW_JPEG_PLAN_PROG_MAX_STAGES = 14,        // Al <= 13
+    WITW_JPEG_PLAN_PROG_SCAN_AT = 128,          // byte offset of scan record 0; record s at SCAN_AT + 4 * SCAN_INTS * s
+    WITW_JPEG_PLAN_PROG_SCAN_INTS = 20,
+    WITW_JPEG_PLAN_PROG_SCAN_NS = 0,            // the fields of a scan record
+    WITW_JPEG_PLAN_PROG_SCAN_COMPS = 1,         // + k: component of scan position k < 4
+    WITW_JPEG_PLAN_PROG_SCAN_SS = 5,
+    WITW_JPEG_PLAN_PROG_SCAN_SE = 6,
+    WITW_JPEG_PLAN_PROG_SCAN_AH = 7,
+    WITW_JPEG_PLAN_PROG_SCAN_AL = 8,
+    WITW_JPEG_PLAN_PROG_SCAN_COLS = 9,          // units per row of the walk
+    WITW_JPEG_PLAN_PROG_SCAN_ROWS = 10,
+    WITW_JPEG_PLAN_PROG_SCAN_RESTART = 11,      // units per restart interval (0: none)
+    WITW_JPEG_PLAN_PROG_SCAN_STAGE = 12,
+    WITW_JPEG_PLAN_PROG_SCAN_TABLES = 13,       // byte offset in the plan
+    WITW_JPEG_PLAN_PROG_SCAN_SEGS_AT = 14,      // byte offset in the plan
+    WITW_JPEG_PLAN_PROG_SCAN_SEGS = 15,
+    WITW_JPEG_PLAN_PROG_SCAN_DATA_END = 16,     // byte offset in the file
+    WITW_JPEG_PLAN_PROG_SEG_INTS = 3,
+    WITW_JPEG_PLAN_PROG_SEG_BYTE = 0,           // the fields of a segment record
+    WITW_JPEG_PLAN_PROG_SEG_UNIT = 1,
+    WITW_JPEG_PLAN_PROG_SEG_UNITS = 2,
+    WITW_JPEG_PLAN_PROG_FIXED = 5248            // SCAN_AT + 4 * SCAN_INTS * MAX_SCANS: tables and segment records start here
 };
 
 // ---- the `info` ints of witw_jpeg_info / witw_jpeg_info_ex (columns COL_INFO .. of the packed descriptor of witw_amd/jpeg.py):

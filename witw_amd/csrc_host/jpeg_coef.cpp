@@ -615,6 +615,200 @@ int decode_progressive(Parsed& P, const uint8_t* d, size_t n, int16_t* coef, uin
     return 0;
 }
 
+// ---- the scan plan of a progressive file (csrc/jpeg_layout.h, 'JPW2'): what the DEVICE needs to decode the scans itself
+// (csrc/jpeg_progressive.hip). The walk of decode_progressive with every check that needs no Huffman decoding; where that one loads and
+// decodes a scan's data, this one only looks for the markers in it. A byte scan: no Huffman decoding, no pass over coefficients.
+
+struct PlanOut {                      // base == nullptr: count the bytes only
+    uint8_t* base;
+    size_t cap, at;
+    bool put(const void* src, size_t len) {
+        if (base) {
+            if (at + len > cap) return false;
+            memcpy(base + at, src, len);
+        }
+        at += len;
+        return true;
+    }
+};
+
+// P: parse(accept_progressive) == 0 and P.progressive -> the plan's size in bytes; -1 = plan_cap is too small; -2 = a file left to the
+// host route (more than PROG_MAX_SCANS scans, a DC table of more than 16 symbols, scans that stop short of bit 0); -3 = a scan, a
+// segment or the restart markers are not what decode_progressive accepts
+long long scan_plan(Parsed& P, const uint8_t* d, size_t n, uint8_t* plan, size_t plan_cap, uint16_t* qt) {
+    PlanOut out = {plan, plan_cap, (size_t)WITW_JPEG_PLAN_PROG_FIXED};
+    if (plan) {
+        if (plan_cap < (size_t)WITW_JPEG_PLAN_PROG_FIXED) return -1;
+        memset(plan, 0, (size_t)WITW_JPEG_PLAN_PROG_FIXED);
+    }
+    int32_t* const h = reinterpret_cast<int32_t*>(plan);
+    int64_t total = 0;
+    for (int c = 0; c < P.ncomp; ++c) {
+        total += (int64_t)P.c[c].bw * P.c[c].bh;
+        if (qt) memcpy(qt + 64 * c, P.qt[P.c[c].tq], 128);
+    }
+    if (total > 0x7fffffff) return -2;
+    int8_t bits[4][64], cell_stage[4][64];
+    memset(bits, -1, sizeof(bits));
+    memset(cell_stage, -1, sizeof(cell_stage));
+    bool latched[4] = {false, false, false, false};
+    int n_scans = 0, stages = 0;
+    long long n_segments = 0, max_segments = 0;
+    size_t i = (size_t)(P.scan - d);
+    for (int m = 0xDA; m != 0xD9;) {
+        if (i + 2 > n) return -3;
+        const int len = be16(d + i);
+        if (len < 2 || i + len > n) return -3;
+        const uint8_t* s = d + i + 2;
+        const int sl = len - 2;
+        i += len;
+        if (m == 0xDB) {
+            if (!read_dqt(P, s, sl)) return -3;
+        } else if (m == 0xC4) {
+            if (!read_dht(P, s, sl)) return -3;
+        } else if (m == 0xDD) {
+            if (sl < 2) return -3;
+            P.restart = be16(s);
+        } else if (m == 0xDA) {
+            ScanHeader S;
+            S.ns = sl ? s[0] : 0;
+            if (S.ns < 1 || S.ns > P.ncomp || sl < 1 + 2 * S.ns + 3) return -3;
+            S.Ss = s[1 + 2 * S.ns]; S.Se = s[2 + 2 * S.ns]; S.Ah = s[3 + 2 * S.ns] >> 4; S.Al = s[3 + 2 * S.ns] & 15;
+            if (S.Ss == 0 ? S.Se != 0 : (S.Ss > S.Se || S.Se > 63 || S.ns != 1)) return -3;
+            if (S.Al > 13 || (S.Ah && S.Ah != S.Al + 1)) return -3;
+            int stage = 0;
+            for (int k = 0; k < S.ns; ++k) {
+                int ci = -1;
+                for (int c = 0; c < P.ncomp; ++c) if (P.c[c].id == s[1 + 2 * k]) ci = c;
+                for (int j = 0; j < k; ++j) if (S.comp[j] == ci) ci = -1;
+                if (ci < 0) return -3;
+                S.comp[k] = ci;
+                Comp& C = P.c[ci];
+                C.td = s[2 + 2 * k] >> 4; C.ta = s[2 + 2 * k] & 15;
+                if (C.td > 3 || C.ta > 3) return -3;
+                if (S.Ss == 0 ? (S.Ah == 0 && !P.dc[C.td].present) : !P.ac[C.ta].present) return -3;
+                if (S.Ss && bits[ci][0] < 0) return -3;
+                for (int kk = S.Ss; kk <= S.Se; ++kk) {
+                    if (bits[ci][kk] != (S.Ah ? S.Ah : -1)) return -3;
+                    bits[ci][kk] = (int8_t)S.Al;
+                    if (cell_stage[ci][kk] + 1 > stage) stage = cell_stage[ci][kk] + 1;
+                }
+                if (!latched[ci]) {
+                    if (!P.qt_present[C.tq]) return -3;
+                    if (qt) memcpy(qt + 64 * ci, P.qt[C.tq], 128);
+                    latched[ci] = true;
+                }
+            }
+            for (int k = 0; k < S.ns; ++k)
+                for (int kk = S.Ss; kk <= S.Se; ++kk) cell_stage[S.comp[k]][kk] = (int8_t)stage;
+            if (n_scans == WITW_JPEG_PLAN_PROG_MAX_SCANS) return -2;
+            const Comp& C0 = P.c[S.comp[0]];
+            long long cols = P.mcux, rows = P.mcuy;
+            if (S.ns == 1) {
+                cols = ((P.W * C0.h + P.hmax - 1) / P.hmax + 7) / 8;
+                rows = ((P.H * C0.v + P.vmax - 1) / P.vmax + 7) / 8;
+            }
+            const long long units = cols * rows;
+            if (units > 0x7fffffff) return -2;
+            const long long n_int = P.restart > 0 ? (units + P.restart - 1) / P.restart : 1;
+            int32_t rec[WITW_JPEG_PLAN_PROG_SCAN_INTS];
+            memset(rec, 0, sizeof(rec));
+            rec[WITW_JPEG_PLAN_PROG_SCAN_NS] = S.ns;
+            for (int k = 0; k < S.ns; ++k) rec[WITW_JPEG_PLAN_PROG_SCAN_COMPS + k] = S.comp[k];
+            rec[WITW_JPEG_PLAN_PROG_SCAN_SS] = S.Ss; rec[WITW_JPEG_PLAN_PROG_SCAN_SE] = S.Se;
+            rec[WITW_JPEG_PLAN_PROG_SCAN_AH] = S.Ah; rec[WITW_JPEG_PLAN_PROG_SCAN_AL] = S.Al;
+            rec[WITW_JPEG_PLAN_PROG_SCAN_COLS] = (int32_t)cols; rec[WITW_JPEG_PLAN_PROG_SCAN_ROWS] = (int32_t)rows;
+            rec[WITW_JPEG_PLAN_PROG_SCAN_RESTART] = P.restart > 0 ? P.restart : 0;
+            rec[WITW_JPEG_PLAN_PROG_SCAN_STAGE] = stage;
+            rec[WITW_JPEG_PLAN_PROG_SCAN_SEGS] = (int32_t)n_int;
+            // the tables in force now, only those the scan decodes with
+            if (S.Ss == 0 ? S.Ah == 0 : true) rec[WITW_JPEG_PLAN_PROG_SCAN_TABLES] = (int32_t)out.at;
+            if (S.Ss == 0 && S.Ah == 0) {
+                for (int k = 0; k < S.ns; ++k) {
+                    const Huff& hf = P.dc[P.c[S.comp[k]].td];
+                    if (hf.nsym > 16) return -2;
+                    uint8_t t[WITW_JPEG_PLAN_DC_STRIDE];
+                    memset(t, 0, sizeof(t));
+                    memcpy(t, hf.counts, 16);
+                    memcpy(t + WITW_JPEG_PLAN_TABLE_SYMS, hf.sym, (size_t)hf.nsym);
+                    if (!out.put(t, sizeof(t))) return -1;
+                }
+            } else if (S.Ss) {
+                const Huff& hf = P.ac[C0.ta];
+                uint8_t t[WITW_JPEG_PLAN_AC_STRIDE];
+                memset(t, 0, sizeof(t));
+                memcpy(t, hf.counts, 16);
+                memcpy(t + WITW_JPEG_PLAN_TABLE_SYMS, hf.sym, (size_t)hf.nsym);
+                if (!out.put(t, sizeof(t))) return -1;
+            }
+            rec[WITW_JPEG_PLAN_PROG_SCAN_SEGS_AT] = (int32_t)out.at;
+            // the segments: the markers of the scan's data as Unstuffed::load reads them, RSTn in sequence and n_int - 1 of them
+            const uint8_t* q = d + i;
+            const uint8_t* const e = d + n;
+            const uint8_t* end = e;
+            long long found = 0;
+            int next_rst = 0;
+            auto segment = [&](size_t byte_at, long long k) {
+                const long long first = P.restart > 0 ? k * P.restart : 0;
+                const long long left = units - first;
+                const uint32_t r[WITW_JPEG_PLAN_PROG_SEG_INTS] = {(uint32_t)byte_at, (uint32_t)first,
+                                                                   (uint32_t)(P.restart > 0 && P.restart < left ? P.restart : left)};
+                return out.put(r, sizeof(r));
+            };
+            if (!segment(i, 0)) return -1;
+            while (q < e) {
+                const uint8_t* f = (const uint8_t*)memchr(q, 0xFF, (size_t)(e - q));
+                if (!f || f + 1 >= e) break;
+                const int mk = f[1];
+                if (mk == 0) { q = f + 2; continue; }
+                if (mk == 0xFF) { q = f + 1; continue; }
+                if (mk >= 0xD0 && mk <= 0xD7) {
+                    if (mk - 0xD0 != next_rst || found + 1 >= n_int) return -3;
+                    next_rst = (next_rst + 1) & 7;
+                    ++found;
+                    if (!segment((size_t)(f + 2 - d), found)) return -1;
+                    q = f + 2;
+                    continue;
+                }
+                end = f;
+                break;
+            }
+            if (found != n_int - 1) return -3;
+            rec[WITW_JPEG_PLAN_PROG_SCAN_DATA_END] = (int32_t)(end - d);
+            if (plan) memcpy(plan + WITW_JPEG_PLAN_PROG_SCAN_AT + sizeof(rec) * (size_t)n_scans, rec, sizeof(rec));
+            ++n_scans;
+            n_segments += n_int;
+            if (n_int > max_segments) max_segments = n_int;
+            if (stage + 1 > stages) stages = stage + 1;
+            i = (size_t)(end - d);
+        } else if (m >= 0xC0 && m <= 0xCF) {
+            return -3;
+        }
+        if (i + 2 > n || d[i] != 0xFF) return -3;
+        while (i < n && d[i] == 0xFF) ++i;
+        if (i >= n) return -3;
+        m = d[i++];
+        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m <= 0x01) return -3;
+    }
+    for (int c = 0; c < P.ncomp; ++c)
+        for (int k = 0; k < 64; ++k)
+            if (bits[c][k] != 0) return -2;
+    if (n_segments > 0x7fffffff || out.at > 0x7fffffff) return -2;
+    if (plan) {
+        h[WITW_JPEG_PLAN_MAGIC_AT] = WITW_JPEG_PLAN_PROG_MAGIC;
+        h[WITW_JPEG_PLAN_PROG_SCANS] = n_scans; h[WITW_JPEG_PLAN_PROG_SEGMENTS] = (int32_t)n_segments;
+        h[WITW_JPEG_PLAN_MCUX] = P.mcux; h[WITW_JPEG_PLAN_MCUY] = P.mcuy; h[WITW_JPEG_PLAN_NCOMP] = P.ncomp;
+        for (int c = 0; c < P.ncomp; ++c) {
+            int32_t* q = h + WITW_JPEG_PLAN_COMP + WITW_JPEG_PLAN_COMP_STRIDE * c;
+            q[WITW_JPEG_PLAN_COMP_H] = P.c[c].h; q[WITW_JPEG_PLAN_COMP_V] = P.c[c].v;
+            q[WITW_JPEG_PLAN_COMP_BW] = P.c[c].bw; q[WITW_JPEG_PLAN_COMP_BH] = P.c[c].bh; q[WITW_JPEG_PLAN_COMP_FIRST] = (int32_t)P.c[c].off;
+        }
+        h[WITW_JPEG_PLAN_PROG_STAGES] = stages; h[WITW_JPEG_PLAN_PROG_MAX_SEGMENTS] = (int32_t)max_segments;
+        h[WITW_JPEG_PLAN_PROG_BLOCKS] = (int32_t)total; h[WITW_JPEG_PLAN_PROG_BYTES] = (int32_t)out.at;
+    }
+    return (long long)out.at;
+}
+
 }  // namespace
 
 extern "C" {
@@ -659,7 +853,8 @@ int witw_jpeg_decode_coef(const uint8_t* data, size_t n, int16_t* coef, uint16_t
 // segment (memchr over ~80 KB per 512 x 512 image instead of decoding ~60 k Huffman symbols). The plan written here is what the
 // kernel reads beside the FILE BYTES themselves; its layout is described, and named, in csrc/jpeg_layout.h.
 
-// (flags: bit 1 as above; a progressive file has no plan whatever bit 0 says: its scans refine one another)
+// (flags: bit 1 as above; a progressive file has no ENTROPY plan whatever bit 0 says: its scans refine one another -- what the device
+// needs for such a file is the scan plan, witw_jpeg_scan_plan_ex below)
 long long witw_jpeg_entropy_plan_bytes_ex(const uint8_t* data, size_t n, int flags) {      // 0: not a file for this decoder
     Parsed& P = parsed();
     if (parse(data, n, P, false, (flags & WITW_JPEG_ACCEPT_H1V2) != 0)) return 0;
@@ -748,6 +943,33 @@ long long witw_jpeg_entropy_plan_ex(const uint8_t* data, size_t n, uint8_t* plan
 
 long long witw_jpeg_entropy_plan(const uint8_t* data, size_t n, uint8_t* plan, size_t plan_cap, uint16_t* qt) {
     return witw_jpeg_entropy_plan_ex(data, n, plan, plan_cap, qt, 0);
+}
+
+// ---- the scans of a PROGRESSIVE file on the device (csrc/jpeg_progressive.hip: one launch per stage, a workgroup per scan, a thread
+// per restart interval of it). The scan plan ('JPW2', csrc/jpeg_layout.h) is to such a file what the entropy plan is to a sequential
+// one; the entropy-plan entries above keep refusing progressive files. flags: bit 1 as above; bit 0 is implied.
+
+// the size of the file's scan plan in bytes; 0: no plan (not a progressive file this decoder takes, or one witw_jpeg_scan_plan_ex refuses)
+long long witw_jpeg_scan_plan_bytes_ex(const uint8_t* data, size_t n, int flags) {
+    Parsed& P = parsed();
+    if (parse(data, n, P, true, (flags & WITW_JPEG_ACCEPT_H1V2) != 0) || !P.progressive) return 0;
+    const long long need = scan_plan(P, data, n, nullptr, 0, nullptr);
+    return need > 0 ? need : 0;
+}
+
+// plan: plan_cap bytes (witw_jpeg_scan_plan_bytes_ex), 4-byte aligned; qt: ncomp x 64 uint16 (as witw_jpeg_decode_coef_ex writes them).
+// Returns the plan's size in bytes, or -1 / -2 as witw_jpeg_info_ex (-1 also: plan_cap too small; -2 also: a sequential file, a file
+// of more than 64 scans, a DC table of more than 16 symbols, scans that stop short of bit 0 -- witw_jpeg_decode_coef_ex's -2), -3 when a
+// segment length, a scan's Ss / Se / Ah / Al, the order of the scans, a missing table, the restart markers of a scan (RSTn out of
+// sequence, or not one per interval) or a missing EOI is what witw_jpeg_decode_coef_ex refuses with -3. A file without a plan takes
+// the host route. Every check that needs no Huffman decoding is made here; what shows only in the entropy-coded bits is the device's
+// to flag.
+long long witw_jpeg_scan_plan_ex(const uint8_t* data, size_t n, uint8_t* plan, size_t plan_cap, uint16_t* qt, int flags) {
+    Parsed& P = parsed();
+    const int rc = parse(data, n, P, true, (flags & WITW_JPEG_ACCEPT_H1V2) != 0);
+    if (rc) return rc;
+    if (!P.progressive || !plan || !qt) return -2;
+    return scan_plan(P, data, n, plan, plan_cap, qt);
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@ dequantisation, integer inverse DCT, fancy chroma upsampling, YCbCr -> RGB) into
 produces, byte for byte. Files this decoder leaves alone (progressive, arithmetic-coded, CMYK, 12-bit, unusual sampling) are
 decoded by Pillow in the worker as before and travel as bytes in the same batch. Opt-in (PROGRESSIVE below): progressive
 files are entropy-decoded by the worker too -- all their scans, into the blocks a sequential file would hold -- and take the same
-route through the GPU. Opt-in too (SAMPLING_440 below): 4:4:0 files (h1v2, e.g. a losslessly rotated 4:2:2 file) take every
+route through the GPU; or (PROGRESSIVE_DEVICE below) the worker only writes a scan plan and the GPU decodes the scans itself, stage by
+stage. Opt-in too (SAMPLING_440 below): 4:4:0 files (h1v2, e.g. a losslessly rotated 4:2:2 file) take every
 route a 4:2:2 file takes.
 
 Nothing here touches the GPU at import or in a worker: libwitw_jpeg.so is host-only C++."""
@@ -26,10 +27,11 @@ KIND_JPEG = 2          # packed-batch kind: coefficient blocks (+ raw uint8 imag
 #   COL_INFO       2..23   the INFO_INTS ints of witw_jpeg_info_ex (INFO_* below); a raw entry fills COL_H and COL_W only
 #   COL_RAW        24      1: uint8 HWC pixels of a file left to Pillow
 #   COL_CHANNELS   25      ... and their channels
-#   COL_ON_DEVICE  26      1: entropy decoding on the device, the file bytes travelled
-#   COL_PLAN       27      ... byte offset of the entropy plan
+#   COL_ON_DEVICE  26      1: entropy decoding on the device, the file bytes travelled; 2: the same for a PROGRESSIVE file (scan plan)
+#   COL_PLAN       27      ... byte offset of the entropy plan (2: of the scan plan)
 #   COL_FILE_LEN   28      ... file length
-#   COL_INTERVALS  29      ... restart intervals (grid sizing of the device decoder)
+#   COL_INTERVALS  29      ... restart intervals (grid sizing of the device decoder); 2: what sizes the stage launches, in one int64:
+#                          the largest segment count of a scan | scans << 32 | stages << 40 (prog_launch_sizes)
 COL_OFFSET, COL_QT, COL_INFO = 0, 1, 2
 COL_RAW, COL_CHANNELS, COL_ON_DEVICE, COL_PLAN, COL_FILE_LEN, COL_INTERVALS = 24, 25, 26, 27, 28, 29
 DESC_COLS = 30
@@ -39,6 +41,10 @@ INFO_COMP, INFO_COMP_STRIDE = 6, 4            # component c: INFO_COMP + INFO_CO
 INFO_COMP_H, INFO_COMP_V, INFO_COMP_BW, INFO_COMP_BH = 0, 1, 2, 3
 INFO_INTS = 22
 PLAN_INTERVALS = 1
+# ... and of the scan plan of a progressive file ('JPW2'): header ints
+PLAN_PROG_MAGIC = 0x3257504A
+PLAN_PROG_SCANS, PLAN_PROG_SEGMENTS, PLAN_PROG_STAGES, PLAN_PROG_MAX_SEGMENTS, PLAN_PROG_BLOCKS, PLAN_PROG_BYTES = 1, 2, 27, 28, 29, 30
+PLAN_PROG_MAX_SCANS, PLAN_PROG_MAX_STAGES = 64, 14
 COL_H, COL_W = COL_INFO + INFO_H, COL_INFO + INFO_W
 # Baseline / extended-sequential Huffman files are entropy-decoded ON THE DEVICE (round 6; csrc/jpeg.hip): with restart markers one GPU
 # thread per restart interval (jpeg_huffman_kernel), without them a self-synchronising decode, one workgroup per file
@@ -52,10 +58,17 @@ COL_H, COL_W = COL_INFO + INFO_H, COL_INFO + INFO_W
 _mode = os.environ.get('WITW_JPEG_DEVICE_ENTROPY', 'all').lower()
 DEVICE_ENTROPY = False if _mode in ('0', 'off', 'false') else 'restart' if _mode in ('restart', '1') else 'all'
 # Progressive files (SOF2): off = left to Pillow in the worker (pixels cross PCIe); on = the worker decodes their scans into coefficient
-# blocks (witw_jpeg_decode_coef_ex) and the GPU finishes them like any other file -- always by the host-coefficient route, whatever
-# DEVICE_ENTROPY says: scans refine one another, the device entropy decoders do not apply. A file whose scans stop short of full
-# precision stays Pillow's (libjpeg smooths it). WITW_JPEG_PROGRESSIVE = 1 | on | true; open_file / read_coef(progressive=...) override it.
+# blocks (witw_jpeg_decode_coef_ex) and the GPU finishes them like any other file -- by the host-coefficient route, whatever
+# DEVICE_ENTROPY says: the sequential device decoders do not apply to scans that refine one another. A file whose scans stop short of
+# full precision stays Pillow's (libjpeg smooths it). WITW_JPEG_PROGRESSIVE = 1 | on | true; open_file / read_coef(progressive=...) override it.
 PROGRESSIVE = os.environ.get('WITW_JPEG_PROGRESSIVE', '').lower() in ('1', 'on', 'true')
+# Opt-in on top of that (implies taking progressive files): their scans are Huffman-decoded ON THE DEVICE too. A scan depends only on the
+# earlier scans that coded the same (component, coefficient) cells, so the worker writes a scan plan (JpegFile.scan_plan: a byte scan,
+# stages of mutually independent scans), the FILE BYTES travel, and one launch per stage decodes every progressive file of a batch side
+# (csrc/jpeg_progressive.hip: a workgroup per scan, a thread per restart interval). Needs DEVICE_ENTROPY on; a file without a plan
+# (more than 64 scans, illegal or incomplete scans) takes the host-coefficient route above, and through it Pillow.
+# WITW_JPEG_PROGRESSIVE_DEVICE = 1 | on | true; open_file / read_coef(progressive='device') override it. What was measured: DESIGN.md §4.7.
+PROGRESSIVE_DEVICE = os.environ.get('WITW_JPEG_PROGRESSIVE_DEVICE', '').lower() in ('1', 'on', 'true')
 ACCEPT_PROGRESSIVE = 1     # flag bit 0 of witw_jpeg_info_ex / witw_jpeg_decode_coef_ex
 # 4:4:0 files (h1v2: luma 1x2, chroma 1x1 -- a portrait photo turned losslessly from a 4:2:2 file): off = left to Pillow in the worker; on =
 # taken like a 4:2:2 file, through whichever entropy route DEVICE_ENTROPY picks (the MCU is Y, Y below it, Cb, Cr; the plan tells the
@@ -84,6 +97,9 @@ def host_lib():
                                 ('witw_jpeg_entropy_plan', ctypes.c_longlong, [ptr, size, ptr, size, ptr])):
             for fn, a in ((getattr(lib, name), args), (getattr(lib, name + '_ex'), args + [ctypes.c_int])):
                 fn.restype, fn.argtypes = res, a
+        # (the scan plan of a progressive file has the _ex form only)
+        lib.witw_jpeg_scan_plan_bytes_ex.restype, lib.witw_jpeg_scan_plan_bytes_ex.argtypes = ctypes.c_longlong, [ptr, size, ctypes.c_int]
+        lib.witw_jpeg_scan_plan_ex.restype, lib.witw_jpeg_scan_plan_ex.argtypes = ctypes.c_longlong, [ptr, size, ptr, size, ptr, ctypes.c_int]
         _HOST = lib
     return _HOST
 
@@ -104,12 +120,14 @@ class JpegCoef(object):
 class JpegFile(JpegCoef):
     """A JPEG file whose header has been parsed (info) but whose entropy-coded data is still to be decoded: pack() decodes it
     straight into its place in the batch block (no array of its own, no copy). `coef` / `qt` decode on demand. progressive: a
-    progressive file (open_file(progressive=True)): all its scans are decoded on the host, never on the device. flags: what the file
+    progressive file (open_file(progressive=True)): all its scans are decoded on the host -- unless device_scans (a progressive file
+    opened with progressive='device'): pack() then sends it to the device with a scan plan when it has one. flags: what the file
     was opened under (ACCEPT_PROGRESSIVE | ACCEPT_H1V2): the _ex entries take it again when the file is decoded or planned."""
-    __slots__ = ('data', 'progressive', 'flags')
+    __slots__ = ('data', 'progressive', 'flags', 'device_scans')
 
-    def __init__(self, info, data, progressive=False, flags=0):
+    def __init__(self, info, data, progressive=False, flags=0, device_scans=False):
         self.info, self.data, self.progressive, self.flags = info, data, progressive, flags
+        self.device_scans = bool(device_scans and progressive)
 
     def decode_into(self, coef, qt):
         """coef int16 [blocks, 64], qt uint16 [components, 64]: views of the destination. -> False if the entropy data is bad (or,
@@ -130,6 +148,24 @@ class JpegFile(JpegCoef):
         plan = np.empty((n,), dtype=np.uint8)
         qt = np.empty((int(self.info[INFO_NCOMP]), 64), dtype=np.uint16)
         if lib.witw_jpeg_entropy_plan_ex(self.data.ctypes.data, self.data.size, plan.ctypes.data, n, qt.ctypes.data, self.flags) != n:
+            return None
+        return plan, qt
+
+    def scan_plan(self):
+        """What the DEVICE needs to decode the scans of this PROGRESSIVE file itself (csrc_host/jpeg_coef.cpp witw_jpeg_scan_plan_ex:
+        frame geometry, a record per scan with its stage, the Huffman tables in force at each scan, a record per restart interval of
+        each scan) -> (plan uint8 array, qt uint16 [components, 64]), or None: not a progressive file, or one the plan writer leaves
+        to the host route (more than PLAN_PROG_MAX_SCANS scans, illegal scan parameters or scan order, restart markers out of
+        sequence, no EOI, scans that stop short of bit 0). A byte scan of the file, no Huffman decoding."""
+        if not self.progressive:
+            return None
+        lib = host_lib()
+        n = int(lib.witw_jpeg_scan_plan_bytes_ex(self.data.ctypes.data, self.data.size, self.flags))
+        if n <= 0:
+            return None
+        plan = np.empty((n,), dtype=np.uint8)
+        qt = np.empty((int(self.info[INFO_NCOMP]), 64), dtype=np.uint16)
+        if lib.witw_jpeg_scan_plan_ex(self.data.ctypes.data, self.data.size, plan.ctypes.data, n, qt.ctypes.data, self.flags) != n:
             return None
         return plan, qt
 
@@ -154,14 +190,16 @@ class JpegFile(JpegCoef):
 
 def open_file(src, progressive=None, h1v2=None):
     """src: a path or the bytes of a JPEG file -> JpegFile (header parsed, entropy decoding deferred to pack()), or None when the
-    file is left to the host decoder. progressive: take progressive files too (None: the module flag PROGRESSIVE); h1v2: take 4:4:0
-    files too (None: the module flag SAMPLING_440)."""
+    file is left to the host decoder. progressive: take progressive files too -- True: their scans are decoded in pack(), on the host;
+    'device': on the device where the file has a scan plan (None: 'device' under the module flag PROGRESSIVE_DEVICE, else the module
+    flag PROGRESSIVE); h1v2: take 4:4:0 files too (None: the module flag SAMPLING_440)."""
     data = np.fromfile(src, dtype=np.uint8) if isinstance(src, (str, os.PathLike)) else np.frombuffer(src, dtype=np.uint8)
     info = np.zeros(INFO_INTS, dtype=np.int32)
-    flags = (ACCEPT_PROGRESSIVE if (PROGRESSIVE if progressive is None else progressive) else 0) | \
-        (ACCEPT_H1V2 if (SAMPLING_440 if h1v2 is None else h1v2) else 0)
+    if progressive is None:
+        progressive = 'device' if PROGRESSIVE_DEVICE else PROGRESSIVE
+    flags = (ACCEPT_PROGRESSIVE if progressive else 0) | (ACCEPT_H1V2 if (SAMPLING_440 if h1v2 is None else h1v2) else 0)
     rc = host_lib().witw_jpeg_info_ex(data.ctypes.data, data.size, info.ctypes.data, flags)      # (1: a progressive file, only under its flag)
-    return JpegFile(info, data, progressive=rc == 1, flags=flags) if rc in (0, 1) else None
+    return JpegFile(info, data, progressive=rc == 1, flags=flags, device_scans=progressive == 'device') if rc in (0, 1) else None
 
 
 def read_coef(src, progressive=None, h1v2=None):
@@ -183,6 +221,13 @@ def plan_intervals(plan):
     return int(plan[4 * PLAN_INTERVALS:4 * PLAN_INTERVALS + 4].view(np.int32)[0])
 
 
+def prog_launch_sizes(plan):
+    """What sizes the stage launches of a progressive file, from its scan plan (uint8 array, JpegFile.scan_plan), as ONE int64 (the
+    descriptor's COL_INTERVALS of such a file): the largest segment count of a scan | scans << 32 | stages << 40."""
+    h = plan[:128].view(np.int32)
+    return int(h[PLAN_PROG_MAX_SEGMENTS]) | (int(h[PLAN_PROG_SCANS]) << 32) | (int(h[PLAN_PROG_STAGES]) << 40)
+
+
 def _shared_bytes(n):
     """n bytes of shared memory as a uint8 tensor: a DataLoader worker's batch block is built in place where the parent process
     will read it (torch would otherwise copy every tensor of a batch into shared memory when it pickles it)."""
@@ -196,20 +241,27 @@ def pack(images, shared=False, alloc=None):
     alloc(nbytes) -> (offset, uint8 numpy view) or None: build the block in caller-provided memory (ring.PinnedRing), in which
     case the first result is (offset, nbytes) instead of a tensor."""
     desc, off, spans = np.zeros((len(images), DESC_COLS), dtype=np.int64), 0, []
-    plans = {}
+    plans, prog = {}, set()
     for i, a in enumerate(images):
         if DEVICE_ENTROPY and isinstance(a, JpegFile):
-            pl = a.entropy_plan()
-            # (a plan of ONE interval = a file without restart markers: the self-synchronising kernel, mode 'all' only)
-            if pl is not None and (DEVICE_ENTROPY in ('all', True) or plan_intervals(pl[0]) > 1):
-                plans[i] = pl
+            if a.progressive:
+                # opened for the device (open_file(progressive='device')) and planned: the stage launches; else the host decodes its scans below
+                pl = a.scan_plan() if a.device_scans else None
+                if pl is not None:
+                    plans[i] = pl
+                    prog.add(i)
+            else:
+                pl = a.entropy_plan()
+                # (a plan of ONE interval = a file without restart markers: the self-synchronising kernel, mode 'all' only)
+                if pl is not None and (DEVICE_ENTROPY in ('all', True) or plan_intervals(pl[0]) > 1):
+                    plans[i] = pl
         if i in plans:
             # entropy decoding on the device: the FILE BYTES travel (24 readable bytes behind the end: the kernel reads aligned 8-byte
             # words one ahead of the one it decodes)
             nbytes = int(a.data.size) + 24
             desc[i, COL_INFO:COL_RAW] = a.info
-            desc[i, COL_ON_DEVICE], desc[i, COL_FILE_LEN] = 1, int(a.data.size)
-            desc[i, COL_INTERVALS] = plan_intervals(plans[i][0])
+            desc[i, COL_ON_DEVICE], desc[i, COL_FILE_LEN] = 2 if i in prog else 1, int(a.data.size)
+            desc[i, COL_INTERVALS] = prog_launch_sizes(plans[i][0]) if i in prog else plan_intervals(plans[i][0])
         elif isinstance(a, JpegCoef):
             nbytes = int(a.info[INFO_BLOCKS]) * 128
             desc[i, COL_INFO:COL_RAW] = a.info
@@ -376,16 +428,27 @@ def _entropy_decode(dev, d, ref, keep):
     """Entropy decoding on the device of the entries d that travelled as file bytes (offsets from ref) -> (coef int16: the files'
     coefficient blocks one after another, first block of each file, errors int32 per file). Files with restart markers: one thread
     per interval; files without (ONE interval of more than SELFSYNC_MIN_BLOCKS blocks): the self-synchronising kernel, one workgroup
-    per file."""
+    per file; progressive files (COL_ON_DEVICE 2): one launch per stage of their scan plans. All write into the one zero-filled
+    coefficient buffer and the one flag per file."""
     from . import _lib, ops
     lib, st = _lib.load(), ops._stream()
     blocks = d[:, COL_INFO + INFO_BLOCKS]
     first = np.cumsum(blocks) - blocks
     coef = torch.zeros((int(blocks.sum()) * 64,), dtype=torch.int16, device=dev)
     errors = torch.zeros((d.shape[0],), dtype=torch.int32, device=dev)
-    sync = (d[:, COL_INTERVALS] == 1) & (blocks > SELFSYNC_MIN_BLOCKS)
+    prog = d[:, COL_ON_DEVICE] == 2
+    sync = ~prog & (d[:, COL_INTERVALS] == 1) & (blocks > SELFSYNC_MIN_BLOCKS)
     rows = np.stack([ref + d[:, COL_OFFSET], ref + d[:, COL_PLAN], coef.data_ptr() + first * 128, d[:, COL_FILE_LEN]], axis=1).astype(np.int64)
-    ir, isy = np.nonzero(~sync)[0], np.nonzero(sync)[0]
+    ir, isy, ipg = np.nonzero(~sync & ~prog)[0], np.nonzero(sync)[0], np.nonzero(prog)[0]
+    if ipg.size:
+        # progressive files: one launch per stage over all of them, in order on the stream -- the only synchronisation between stages
+        sizes = d[ipg, COL_INTERVALS]
+        segs, scans, stages = int((sizes & 0xffffffff).max()), int(((sizes >> 32) & 0xff).max()), int(((sizes >> 40) & 0xff).max())
+
+        def launch(files, n, err):
+            for stage in range(stages):
+                _lib.check(lib.witw_jpeg_progressive_stage(files, n, stage, scans, segs, err, st), 'witw_jpeg_progressive_stage')
+        _entropy_launch(dev, rows[ipg], launch, errors, ipg, keep)
     if ir.size:
         most = int(d[ir, COL_INTERVALS].max())
         _entropy_launch(dev, rows[ir], lambda files, n, err: _lib.check(lib.witw_jpeg_huffman(files, n, most, err, st), 'witw_jpeg_huffman'),
