@@ -292,6 +292,32 @@ int witw_match_pairs_count_masked(const float* ov, const float* su, const float*
  * impl < 0 only queries; returns the previous setting. */
 int witw_match_pairs_impl(int impl);
 
+/* ---- Orientation profiles: the match at EVERY shift, and ranked orientation hypotheses drawn from it.
+ * witw_match_profile: score_all / distance_all [Bo,Bs,64] (either may be NULL, not both). score_all[o][s][k] is the correlation
+ * of pair (o,s) at shift k; distance_all[o][s][k] = 2*(1 - score/(wn[o][k]*sn[s])), witw_match_fwd's epilogue expression. Per
+ * pair the 64 scores carry THE BITS of the accumulation chain every forward form runs (row outer, k inner, k padded to even
+ * with a zero multiplier): the first arg-max of score_all[o][s][:] is witw_match_fwd's orientation, and score_all / distance_all
+ * at that shift are its score / distance bit for bit, whatever kernel form witw_match_fwd picks for the shape. workspace:
+ * witw_match_workspace_floats(Bo,Bs) floats, filled as witw_match_fwd fills it (window norms, then surface norms);
+ * witw_match_pairs* and witw_match_pairs_profile take it unchanged.
+ * witw_match_pairs_profile: the same for a LIST of pairs (as witw_match_pairs: pair_o / pair_s int32 on the device, wn / sn
+ * the norm blocks of a match workspace over the same ov / su); outputs [n_pairs,64], rows bit-identical to the rows
+ * witw_match_profile writes for those pairs. The route at retrieval scale: the profiles of a query's k candidates.
+ * witw_profile_hypotheses: score_all [n_pairs,64] -> shifts [n_pairs,n_hyp] (int64). Hypothesis 1 is the first maximum over the
+ * allowed shifts -- witw_match_fwd_masked's rule, ties and NaNs included, so it is that entry's orientation. Hypothesis j+1
+ * is the first maximum over the allowed shifts whose circular distance (on the ring of 64) to every earlier hypothesis is
+ * > min_sep; once no shift is left the remaining entries are -1. Pair p reads the word shift_mask[p % n_words]: a dense
+ * [Bo,Bs] profile passes the [Bs] words of witw_match_fwd_masked and n_words = Bs, a pair list passes gathered words and
+ * n_words = n_pairs, one shared word n_words = 1; NULL, or a word of 0, allows all 64 shifts. 1 <= n_hyp <= 64,
+ * 0 <= min_sep <= 31. Ranking is by the raw score, the quantity the reference's correlation maximises. */
+int witw_match_profile(const float* ov, const float* su, int Bo, int Bs, int We, float* score_all, float* distance_all,
+                       float* workspace, void* stream);
+int witw_match_pairs_profile(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o,
+                             const int* pair_s, int n_pairs, int Bo, int Bs, int We, float* score_all, float* distance_all,
+                             void* stream);
+int witw_profile_hypotheses(const float* score_all, int n_pairs, const unsigned long long* shift_mask, int n_words, int n_hyp,
+                            int min_sep, long long* shifts, void* stream);
+
 /* ---- Dropout2d masks (AddDropout, model/cvig_fov.py:234-245): out [n_layers][B][C] = 0 or 1/(1-p) per (sample, channel) from
  * Philox4x32-10 keyed on `seed`, counter (sample*C + channel, layers[i] | encoder << 16, step, rank) -- reproducible from those
  * numbers alone (the reference uses torch's global RNG stream). layers: HOST array of n_layers (<= 3) layer indices. */

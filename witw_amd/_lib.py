@@ -147,6 +147,9 @@ SIGNATURES = {
     'witw_rank_count_thresh': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'witw_match_pairs': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 4),
     'witw_match_pairs_impl': (c_int, [c_int]),
+    'witw_match_profile': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
+    'witw_match_pairs_profile': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 3),
+    'witw_profile_hypotheses': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'witw_match_fwd_dft_masked': (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 7),
     'witw_match_pairs_masked': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 5),
     'witw_match_pairs_count_masked': (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 4),

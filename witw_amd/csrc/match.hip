@@ -29,8 +29,8 @@ struct MatchArgs {
     const float* wn;     // [Bo,64] window norms per shift
     const float* sn;     // [Bs]    surface norms
     long long* orientation;  // [Bo,Bs] or null
-    float* distance;         // [Bo,Bs] or null
-    float* score;            // [Bo,Bs] or null (max correlation)
+    float* distance;         // [Bo,Bs] or null; the PROFILE instantiations: [Bo,Bs,64] or null, the distance at every shift
+    float* score;            // [Bo,Bs] or null (max correlation); PROFILE: [Bo,Bs,64] or null, the score at every shift
     int Bo, Bs, We;
     const unsigned long long* mask;   // [Bs] or null: bit k of mask[s] set = shift k may be chosen for surface s (0 = no prior)
 };
@@ -49,7 +49,8 @@ __device__ __forceinline__ void mask_shift(unsigned long long m, float& v, int& 
 
 // OPW = overhead images per wave (1 or 2), MT = 32-surface M-tiles per wave (2, or 1 for batches too small to fill the
 // chip with 128-surface blocks); a block covers 2*OPW overheads x 64*MT surfaces.
-template <int OPW, int MT, bool MASKED>
+// PROFILE (witw_match_profile): the same K loop, but the epilogue keeps all 64 scores of every pair instead of their arg-max.
+template <int OPW, int MT, bool MASKED, bool PROFILE = false>
 __global__ __launch_bounds__(NT) void match_kernel(MatchArgs p) {
     constexpr int MO = 2 * OPW;
     constexpr int MSB = 64 * MT;         // surfaces per block
@@ -138,6 +139,43 @@ __global__ __launch_bounds__(NT) void match_kernel(MatchArgs p) {
         }
         if (r + 1 < 64) store_stage(cur ^ 1);
         __syncthreads();
+    }
+
+    // ---- PROFILE epilogue: every accumulator leaves as it is. Register r of lane (l31, hk) in tile [mt][o][n] is surface row
+    // (r & 3) + 8 * (r >> 2) + 4 * hk, shift 32 * n + l31: one store per register writes the 32 consecutive floats of a half
+    // profile of each of two pairs (128-byte segments; no LDS transpose). The window norm is read once per (overhead, shift) and
+    // the surface norm once per surface row; the distance is the arg-max epilogue's expression, operation for operation.
+    if constexpr (PROFILE) {
+        static_assert(!MASKED, "a profile holds every shift: a mask applies where hypotheses are drawn from it");
+        float wnv[OPW][2];
+#pragma unroll
+        for (int o = 0; o < OPW; ++o) {
+            const int og = o0 + OPW * wo + o;
+#pragma unroll
+            for (int n = 0; n < 2; ++n) wnv[o][n] = (p.distance && og < p.Bo) ? p.wn[(size_t)og * 64 + 32 * n + l31] : 1.f;
+        }
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int srow = s0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hk;
+                if (srow >= p.Bs) continue;
+                const float snv = p.distance ? p.sn[srow] : 1.f;
+#pragma unroll
+                for (int o = 0; o < OPW; ++o) {
+                    const int og = o0 + OPW * wo + o;
+                    if (og >= p.Bo) continue;
+                    const size_t off = ((size_t)og * p.Bs + srow) * 64 + l31;
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        const float v = acc[mt][o][n][r];
+                        if (p.score) p.score[off + 32 * n] = v;
+                        if (p.distance) p.distance[off + 32 * n] = 2.f * (1.f - v / (wnv[o][n] * snv));
+                    }
+                }
+            }
+        }
+        return;
     }
 
     // ---- epilogue: arg-max over the 64 shifts (2 N-tiles x 32 lanes), first index wins ties
@@ -1016,7 +1054,9 @@ __global__ __launch_bounds__(256) void match_pairs_kernel(const float* __restric
 // buffered by row parity; a wave's LDS operations execute in order, so no barrier) and lane j reads strip[k + j] -- consecutive
 // lanes, consecutive banks; the multiplier is wave-uniform (scalar loads). Arg-max and distance: the MFMA kernel's own code.
 // MASKED: as in match_pairs_kernel.
-template <int WE, bool MASKED>      // WE > 0: the embedding width as a constant (64: retrieval at fov 360); 0: any width
+// PROFILE (witw_match_pairs_profile): lane j holds the score of shift j when the chain ends, so lane j stores it -- score and
+// distance are then [n_pairs,64], the distance at every shift by the expression below -- and no arg-max follows.
+template <int WE, bool MASKED, bool PROFILE = false>      // WE > 0: the embedding width as a constant (64: retrieval at fov 360); 0: any width
 __global__ __launch_bounds__(256) void match_pairs_valu_kernel(const float* __restrict__ ov, const float* __restrict__ su,
                                                                const float* __restrict__ wn, const float* __restrict__ sn,
                                                                const int* __restrict__ pair_o, const int* __restrict__ pair_s,
@@ -1054,6 +1094,13 @@ __global__ __launch_bounds__(256) void match_pairs_valu_kernel(const float* __re
         } else {
             for (int k = 0; k < Wp; ++k) acc = __builtin_fmaf(k < We ? srow[k] : 0.f, b[k], acc);
         }
+    }
+    if constexpr (PROFILE) {
+        static_assert(!MASKED, "a profile holds every shift: a mask applies where hypotheses are drawn from it");
+        const size_t off = (size_t)pr * 64 + lane;
+        if (score) score[off] = acc;
+        if (distance) distance[off] = 2.f * (1.f - acc / (wn[(size_t)o * 64 + lane] * sn[s]));
+        return;
     }
     // lanes 0-31: shift l31 against shift l31 + 32 first, then the butterfly over the 32 columns -- the comparison tree of the
     // MFMA kernel (acc0 / acc1), so that ties and NaNs resolve alike
@@ -1323,6 +1370,49 @@ __global__ __launch_bounds__(NT, 2) void match_fixed_kernel(FixedArgs p) {
         case 3: fixed_tile<WP, 3>(p, smem, first, rows, shift, o0); break;
         default: fixed_tile<WP, 4>(p, smem, first, rows, shift, o0); break;
     }
+}
+
+// ---- ranked orientation hypotheses from a profile (witw_profile_hypotheses): one wave per pair, lane = shift. Hypothesis 1 is
+// the first maximum over the shifts the pair's word allows -- the masked arg-max of the kernels above, the same comparison tree
+// (shift l31 against l31 + 32, then the butterfly over 32 columns), so that ties and NaNs resolve as witw_match_fwd_masked resolves
+// them. Every hypothesis then clears its own bit and the min_sep bits either side of it (circular) in the 64-bit allowed word,
+// and the next one is the first maximum over what is left; once the word is empty the remaining places are -1. The loop runs
+// n_hyp times whatever the data; lane j keeps hypothesis j, so the list leaves in one store.
+__global__ __launch_bounds__(256) void profile_hypotheses_kernel(const float* __restrict__ score_all,
+                                                                 const unsigned long long* __restrict__ mask, int n_words,
+                                                                 int n_pairs, int n_hyp, int min_sep, long long* __restrict__ shifts) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int pr = blockIdx.x * 4 + wave;
+    if (pr >= n_pairs) return;                       // wave-uniform; the kernel has no barrier
+    const int l31 = lane & 31;
+    const float mine = score_all[(size_t)pr * 64 + lane];
+    const float lo = __shfl(mine, l31, 64), hi = __shfl(mine, l31 + 32, 64);
+    unsigned long long allowed = mask ? load_shift_mask(mask, pr % n_words, n_words) : ~0ull;
+    allowed = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)allowed) |
+              ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(allowed >> 32)) << 32);
+    const unsigned long long band0 = (2ull << (2 * min_sep)) - 1ull;      // 2 * min_sep + 1 <= 63 low bits
+    long long out = -1;
+    for (int j = 0; j < n_hyp; ++j) {
+        if (allowed == 0ull) break;                  // wave-uniform: every lane holds the pair's word
+        float v = lo;
+        int idx = l31;
+        float v1 = hi;
+        int i1 = 32 + l31;
+        mask_shift(allowed, v, idx);
+        mask_shift(allowed, v1, i1);
+        if (v1 > v || (v1 == v && i1 < idx)) { v = v1; idx = i1; }
+#pragma unroll
+        for (int d = 1; d < 32; d <<= 1) {
+            const float vo = __shfl_xor(v, d, 64);
+            const int io = __shfl_xor(idx, d, 64);
+            if (vo > v || (vo == v && io < idx)) { v = vo; idx = io; }
+        }
+        const int k = __builtin_amdgcn_readfirstlane(idx) & 63;
+        if (lane == j) out = k;
+        const int rot = (k - min_sep) & 63;          // the band [k - min_sep, k + min_sep] on the ring of 64
+        allowed &= ~((band0 << rot) | (rot ? band0 >> (64 - rot) : 0ull));
+    }
+    if (lane < n_hyp) shifts[(size_t)pr * n_hyp + lane] = out;
 }
 
 }  // namespace
@@ -1618,6 +1708,77 @@ int witw_match_pairs_impl(int impl) {
     const int prev = g_match_pairs_impl;
     if (impl >= 0) g_match_pairs_impl = impl ? 1 : 0;
     return prev;
+}
+
+// ---- orientation profiles: the match at EVERY shift. score_all / distance_all [Bo,Bs,64] (either may be null): the 64 scores of
+// every pair -- the accumulators of match_kernel, i.e. the chain every forward form runs (row outer, k inner, k padded to even with
+// a zero multiplier), so the first arg-max of a row is witw_match_fwd's orientation and the two values there are its score and
+// distance, bit for bit, whatever form the forward picks for the shape -- and 2 * (1 - score / (wn[o][k] * sn[s])) at every shift.
+// The workspace is filled as witw_match_fwd fills it. Only the generic kernel forms have the profile epilogue: at 256 bytes
+// out per 524k FLOP the launch stays bound by the matrix pipe; the choice among them is match_fwd_launch's grid arithmetic.
+int witw_match_profile(const float* ov, const float* su, int Bo, int Bs, int We, float* score_all, float* distance_all,
+                       float* workspace, void* stream) {
+    WITW_CHECK_ARG(ov && su && workspace, "match_profile: null pointer");
+    WITW_CHECK_ARG(score_all || distance_all, "match_profile: no output requested (score_all and distance_all are both null)");
+    WITW_CHECK_ARG(Bo > 0 && Bs > 0, "match_profile: empty batch Bo=%d Bs=%d", Bo, Bs);
+    WITW_CHECK_ARG(We >= 1 && We <= 64, "match_profile: surface embedding width %d outside [1,64]", We);
+    const int gx = cdiv(Bs, MS);
+    const int opw = (long long)gx * cdiv(Bo, 4) >= 512 ? 2 : 1;                       // overheads per wave
+    const int mt = (opw == 2 || (long long)gx * cdiv(Bo, 2) >= 256) ? 2 : 1;          // 32-surface tiles per wave
+    const dim3 grid(cdiv(Bs, 64 * mt), cdiv(Bo, 2 * opw));
+    WITW_CHECK_ARG(grid.y <= 65535u, "match_profile: too many overhead rows Bo=%d; profile them in chunks", Bo);
+    hipStream_t st = (hipStream_t)stream;
+    float* wn = workspace;
+    float* sn = workspace + (size_t)Bo * 64;
+    hipLaunchKernelGGL(window_norm_kernel, dim3(Bo), dim3(256), 0, st, ov, wn, We);
+    hipLaunchKernelGGL(row_norm_kernel, dim3(Bs), dim3(256), 0, st, su, sn, 64 * We);
+    MatchArgs a;
+    a.ov = ov; a.su = su; a.wn = wn; a.sn = sn;
+    a.orientation = nullptr; a.distance = distance_all; a.score = score_all;
+    a.Bo = Bo; a.Bs = Bs; a.We = We;
+    a.mask = nullptr;
+    if (opw == 2) hipLaunchKernelGGL((match_kernel<2, 2, false, true>), grid, dim3(NT), 0, st, a);
+    else if (mt == 2) hipLaunchKernelGGL((match_kernel<1, 2, false, true>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((match_kernel<1, 1, false, true>), grid, dim3(NT), 0, st, a);
+    witw_note_variant("match_kernel<%d,%d,false,true>", opw, mt);
+    WITW_CHECK_LAUNCH("match_profile");
+    return WITW_OK;
+}
+
+// The profiles of a LIST of pairs, [n_pairs,64], through the vector-pipe chain of witw_match_pairs: rows bit-identical to the
+// rows witw_match_profile writes for those pairs. wn / sn: the norm blocks of a match workspace over the same ov / su.
+int witw_match_pairs_profile(const float* ov, const float* su, const float* wn, const float* sn, const int* pair_o, const int* pair_s,
+                             int n_pairs, int Bo, int Bs, int We, float* score_all, float* distance_all, void* stream) {
+    WITW_CHECK_ARG(ov && su && wn && sn && pair_o && pair_s, "match_pairs_profile: null pointer");
+    WITW_CHECK_ARG(score_all || distance_all, "match_pairs_profile: no output requested (score_all and distance_all are both null)");
+    WITW_CHECK_ARG(n_pairs > 0 && Bo > 0 && Bs > 0, "match_pairs_profile: empty list n=%d Bo=%d Bs=%d", n_pairs, Bo, Bs);
+    WITW_CHECK_ARG(We >= 1 && We <= 64, "match_pairs_profile: surface embedding width %d outside [1,64]", We);
+    if (We == 64)
+        hipLaunchKernelGGL((match_pairs_valu_kernel<64, false, true>), dim3(cdiv(n_pairs, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn,
+                           pair_o, pair_s, n_pairs, We, (long long*)nullptr, distance_all, score_all, (const int*)nullptr, (const float*)nullptr,
+                           (int*)nullptr, (const unsigned long long*)nullptr);
+    else
+        hipLaunchKernelGGL((match_pairs_valu_kernel<0, false, true>), dim3(cdiv(n_pairs, 4)), dim3(256), 0, (hipStream_t)stream, ov, su, wn, sn,
+                           pair_o, pair_s, n_pairs, We, (long long*)nullptr, distance_all, score_all, (const int*)nullptr, (const float*)nullptr,
+                           (int*)nullptr, (const unsigned long long*)nullptr);
+    WITW_CHECK_LAUNCH("match_pairs_profile");
+    return WITW_OK;
+}
+
+// score_all [n_pairs,64] -> shifts [n_pairs,n_hyp] (int64): hypothesis 1 = the first maximum over the shifts that word
+// shift_mask[p % n_words] allows (null, or a word of 0: all 64) -- witw_match_fwd_masked's rule --, hypothesis j + 1 = the first
+// maximum over the allowed shifts farther than min_sep (circular, on the ring of 64) from every earlier one; -1 once none is left.
+int witw_profile_hypotheses(const float* score_all, int n_pairs, const unsigned long long* shift_mask, int n_words, int n_hyp,
+                            int min_sep, long long* shifts, void* stream) {
+    WITW_CHECK_ARG(score_all && shifts, "profile_hypotheses: null pointer");
+    WITW_CHECK_ARG(n_pairs > 0, "profile_hypotheses: empty list n_pairs=%d", n_pairs);
+    WITW_CHECK_ARG(!shift_mask || n_words >= 1, "profile_hypotheses: n_words=%d mask words", n_words);
+    WITW_CHECK_ARG(n_hyp >= 1 && n_hyp <= 64, "profile_hypotheses: n_hyp=%d outside [1,64]", n_hyp);
+    WITW_CHECK_ARG(min_sep >= 0 && min_sep <= 31, "profile_hypotheses: min_sep=%d outside [0,31]", min_sep);
+    hipLaunchKernelGGL(profile_hypotheses_kernel, dim3(cdiv(n_pairs, 4)), dim3(256), 0, (hipStream_t)stream, score_all, shift_mask,
+                       shift_mask ? n_words : 1, n_pairs, n_hyp, min_sep, shifts);
+    WITW_CHECK_LAUNCH("profile_hypotheses");
+    return WITW_OK;
 }
 
 // counts[q] = #{o : D[o,q] < threshold[q] - eps}; the (o, q) with |D[o,q] - threshold[q]| <= eps go to pair_o / pair_s

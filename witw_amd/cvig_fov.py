@@ -11,7 +11,7 @@ from types import SimpleNamespace
 
 import torch
 
-from . import _lib, build as _build, ops, parallel, retrieval, slab_loss, synth
+from . import _lib, build as _build, match_profile, ops, parallel, retrieval, slab_loss, synth
 from .retrieval import _direct_pass, _empty_topk, _merge_topk, _sort_by_value_then_index, last_retrieve_stats      # noqa: F401
 
 
@@ -718,6 +718,147 @@ def match(overhead_embed, surface_embed, shift_mask=None, known_shift=None):
     if torch.is_grad_enabled() and (overhead_embed.requires_grad or surface_embed.requires_grad):
         return _MatchFn.apply(overhead_embed, surface_embed, prior)
     return prior.match_fwd(ops, overhead_embed.contiguous(), surface_embed.contiguous())
+
+
+# ----------------------------------------------------------------------------- orientation profiles and ranked hypotheses
+def _pair_indices(who, pairs, Bo, Bs, device):
+    """pairs = (pair_o, pair_s): overhead / surface row numbers, integer tensors (or sequences) of one length -> the two as
+    contiguous int32 tensors on `device`, every index checked against its batch (the kernels read what they are given)"""
+    try:
+        po, ps = pairs
+        po, ps = torch.as_tensor(po), torch.as_tensor(ps)
+    except (TypeError, ValueError):
+        raise _lib.WitwError('%s: pairs must be (pair_o, pair_s), two integer tensors of one length' % who)
+    for t in (po, ps):
+        if t.dim() != 1 or t.dtype not in (torch.int32, torch.int64) or t.numel() != po.numel():
+            raise _lib.WitwError('%s: pairs must be (pair_o, pair_s), two 1-D int32 / int64 tensors of one length, got %s %s and %s %s'
+                                 % (who, tuple(po.shape), po.dtype, tuple(ps.shape), ps.dtype))
+    for name, t, n in (('pair_o', po, Bo), ('pair_s', ps, Bs)):
+        if t.numel() and not (0 <= int(t.min()) and int(t.max()) < n):
+            raise _lib.WitwError('%s: %s holds row numbers outside [0, %d)' % (who, name, n))
+    return po.to(device=device, dtype=torch.int32).contiguous(), ps.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _match_norms(ov, su):
+    """(wn [Bo*64], sn [Bs]): the norm blocks of a match workspace over (ov, su) without the Bo x Bs match -- the window norms
+    depend on the overhead side and the width alone, the surface norms on the surface side, so two one-row fixed matches leave
+    them, from the norm kernels every match launch runs"""
+    Bo, Bs = ov.shape[0], su.shape[0]
+    zero = lambda n: torch.zeros((n,), dtype=torch.int64, device=ov.device)
+    wn = ops.match_fwd_fixed(ov, su[:1], zero(1), want_workspace=True, want_orientation=False)[3][:Bo * 64]
+    sn = ops.match_fwd_fixed(ov[:1], su, zero(Bs), want_workspace=True, want_orientation=False)[3][64:64 + Bs]
+    return wn.contiguous(), sn.contiguous()
+
+
+def orientation_profile(overhead_embed, surface_embed, pairs=None, workspace=None):
+    """The match at EVERY orientation: (scores, distances), each f32 [Bo,Bs,64] -- or [n,64] for pairs = (pair_o, pair_s), the
+    overhead / surface row numbers of a list of n pairs (e.g. retrieve_topk's indices with their query numbers: a dense profile of
+    a gallery is never wanted). scores[...,k] is the correlation at shift k (the reference's `correlation` before its arg-max),
+    distances[...,k] the distance match() would return were k the orientation. The first arg-max of scores[o,s] IS match()'s
+    orientation and the two values there are its score and distance, bit for bit; a pair list's rows carry the bits of the dense
+    rows. workspace (pairs only): the norm workspace of an earlier match over the same tensors (ops.match_fwd(...,
+    want_workspace=True)); computed here when None. Runs under no_grad: a profile is a report, not a node of the graph."""
+    with torch.no_grad():
+        ov, su = overhead_embed.contiguous(), surface_embed.contiguous()
+        if pairs is None:
+            return match_profile.match_profile(ov, su)
+        Bo, Bs = ov.shape[0], su.shape[0]
+        po, ps = _pair_indices('orientation_profile', pairs, Bo, Bs, ov.device)
+        ops._match_operands('orientation_profile', ov, su)
+        if workspace is None:
+            wn, sn = _match_norms(ov, su)
+        else:
+            if not (isinstance(workspace, torch.Tensor) and workspace.dim() == 1 and workspace.numel() >= Bo * 64 + Bs):
+                raise _lib.WitwError('orientation_profile: workspace must be the 1-D norm workspace of a match over the same tensors')
+            wn, sn = workspace[:Bo * 64].contiguous(), workspace[Bo * 64:Bo * 64 + Bs].contiguous()
+        return match_profile.match_pairs_profile(ov, su, wn, sn, po, ps)
+
+
+def min_separation_shifts(min_separation_deg):
+    """Degrees -> the `min_sep` of match_profile.profile_hypotheses, in shifts on the ring of 64: floor(deg * 64 / 360). Two
+    hypotheses are then MORE than that many shifts apart: 22.5 -> 4 (at least 5 shifts = 28.125 degrees apart), 5.625 -> 1,
+    anything below one shift (5.625 degrees) -> 0 (any two different shifts). Must land in [0, 31]: 0 <= deg < 180."""
+    import math
+    deg = float(min_separation_deg)
+    if not (math.isfinite(deg) and deg >= 0):
+        raise _lib.WitwError('min_separation_deg must be a finite number of degrees >= 0, got %r' % (min_separation_deg,))
+    sep = int(math.floor(deg * 64. / 360.))
+    if sep > 31:
+        raise _lib.WitwError('min_separation_deg = %r is half the circle or more: no second hypothesis can exist (must be < 180)'
+                             % (min_separation_deg,))
+    return sep
+
+
+def refine_orientation(scores, shift):
+    """Sub-bin offset of an orientation: scores [...,64] (the raw scores of orientation_profile), shift int64 [...] or [...,n]
+    (shifts of those profiles; -1 = none) -> delta float64, shaped as shift, in [-1/2, 1/2]: the vertex of the parabola through
+    the scores at shift - 1, shift, shift + 1 (circular: 63 and 0 are neighbours),
+        delta = (y- - y+) / (2 * (y- - 2 y0 + y+)),
+    computed in float64. delta = 0 where the three points do not curve downwards (denominator >= 0: a flat top or no local
+    maximum), where any of them is not finite, and where shift is -1. Plain torch: works on CPU tensors. The refined heading
+    is (shift + delta) * 360 / 64 - 180 degrees."""
+    if scores.shape[-1] != 64:
+        raise _lib.WitwError('refine_orientation: scores must be [...,64], got %s' % (tuple(scores.shape),))
+    listed = shift.dim() == scores.dim()
+    if shift.dtype != torch.int64 or tuple(shift.shape[:scores.dim() - 1]) != tuple(scores.shape[:-1]) or not (
+            listed or shift.dim() == scores.dim() - 1):
+        raise _lib.WitwError('refine_orientation: shift must be int64 %s or %s + (n,), got %s %s'
+                             % (tuple(scores.shape[:-1]), tuple(scores.shape[:-1]), tuple(shift.shape), shift.dtype))
+    sc = scores.to(torch.float64)
+    sh = shift.to(sc.device) if listed else shift.to(sc.device).unsqueeze(-1)
+    k = sh.clamp(min=0) & 63
+    ym, y0, yp = (torch.gather(sc, -1, (k + d) & 63) for d in (63, 0, 1))
+    den = ym - 2. * y0 + yp
+    ok = torch.isfinite(ym) & torch.isfinite(y0) & torch.isfinite(yp) & (den < 0) & (sh >= 0)
+    delta = torch.where(ok, 0.5 * (ym - yp) / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den)).clamp(-0.5, 0.5)
+    return delta if listed else delta.squeeze(-1)
+
+
+def _check_hypothesis_count(who, n):
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 64:
+        raise _lib.WitwError('%s: the number of hypotheses must be an integer in [1, 64], got %r' % (who, n))
+    return n
+
+
+def orientation_hypotheses(overhead_embed, surface_embed, n=3, min_separation_deg=22.5, shift_mask=None, pairs=None, refine=True,
+                           output_width_max=64):
+    """The n best orientations of every pair, ranked: (shift, degrees, distance, score), each [Bo,Bs,n] -- or [m,n] for
+    pairs = (pair_o, pair_s), see orientation_profile.
+      shift     int64: hypothesis 1 is match()'s orientation (under the same shift_mask); hypothesis j + 1 is the first maximum
+                of the raw correlation over the allowed shifts more than floor(min_separation_deg * 64 / 360) shifts away (circular)
+                from every earlier hypothesis -- 22.5 degrees -> 4, so hypotheses lie at least 5 shifts (28.125 degrees) apart;
+                a separation below one shift (5.625 degrees) -> 0, any other shift. -1 where no shift is left.
+      degrees   float64, those of orientation_mask: shift * 360 / output_width_max - 180; with refine=True the sub-bin offset
+                of refine_orientation is added to the shift first (the shift column itself is never altered).
+      distance  f32: what match() would return at that shift (column 0: what it does return, bit for bit).
+      score     f32: exp(10 * (1 - distance)), the heat map's score (sweep_scores).
+    Where shift is -1 the other three are NaN. shift_mask: int64 [Bs] as for match() (orientation_mask); hypotheses are drawn
+    from the allowed shifts only. Ranking is by raw correlation, the quantity the reference's `correlation` maximises. Runs
+    under no_grad: orientations are constants of the graph, here as everywhere."""
+    n = _check_hypothesis_count('orientation_hypotheses', n)
+    W = int(output_width_max)
+    if not 1 <= W <= 64:
+        raise _lib.WitwError('orientation_hypotheses: output_width_max must lie in [1, 64], got %r' % (output_width_max,))
+    min_sep = min_separation_shifts(min_separation_deg)
+    with torch.no_grad():
+        words = None
+        if shift_mask is not None:
+            words = _Prior.of(shift_mask, None, surface_embed).mask
+        scores, dists = orientation_profile(overhead_embed, surface_embed, pairs)
+        if scores.numel() == 0:
+            words = None                     # an empty pair list: nothing reads a word
+        if words is not None and pairs is not None:
+            words = words[torch.as_tensor(pairs[1]).to(device=words.device, dtype=torch.int64)].contiguous()
+        shift = match_profile.profile_hypotheses(scores, n, min_sep, words)
+        valid = shift >= 0
+        k = shift.clamp(min=0)
+        nan = torch.full((), float('nan'), dtype=torch.float32, device=shift.device)
+        distance = torch.where(valid, torch.gather(dists, -1, k), nan)
+        pos = k.to(torch.float64)
+        if refine:
+            pos = pos + refine_orientation(scores, shift)
+        degrees = torch.where(valid, pos * 360. / W - 180., nan.to(torch.float64))
+        return shift, degrees, distance, torch.exp(10. * (1. - distance))
 
 
 class Adam(object):
@@ -2047,14 +2188,30 @@ def test(dataset='cvusa', fov=360, batch_size=64, num_workers=8, csv_path=None, 
     return t
 
 
-def sweep_scores(overhead_embed, surface_embed, output_width_max=64, shift_mask=None, known_shift=None):
+def sweep_scores(overhead_embed, surface_embed, output_width_max=64, shift_mask=None, known_shift=None, hypotheses=1,
+                 min_separation_deg=22.5, refine=True):
     """The scoring block of tools/heatmap/heatmap.py:172-178 (one photo against N satellite tiles):
     -> (orientation in degrees, dissimilarity, score = exp(10*(1-d))), each [N] (or [N,Bs]). shift_mask / known_shift: see match(); the
-    degrees returned here are the ones orientation_mask / orientation_shift take."""
+    degrees returned here are the ones orientation_mask / orientation_shift take.
+    hypotheses = M > 1 (not in the reference): a 4th item, the tuple of orientation_hypotheses(n=M, min_separation_deg, shift_mask,
+    refine, output_width_max), unsqueezed ([N,Bs,M]). Its first column is the first three items again -- same shift, same
+    distance and score bits -- which is checked here. A known_shift has one shift per query and no second hypothesis: refused."""
+    if hypotheses != 1:
+        _check_hypothesis_count('sweep_scores', hypotheses)
+        if known_shift is not None:
+            raise _lib.WitwError('sweep_scores: hypotheses=%d with known_shift: one given shift has no second hypothesis; pass '
+                                 'the heading as a shift_mask window instead' % hypotheses)
     ori, dist = match(overhead_embed, surface_embed, shift_mask, known_shift)
     orientations = torch.squeeze(ori) * 360 / output_width_max - 180
     distances = torch.squeeze(dist)
-    return orientations, distances, torch.exp(10. * (1. - distances))
+    if hypotheses == 1:
+        return orientations, distances, torch.exp(10. * (1. - distances))
+    hyp = orientation_hypotheses(overhead_embed, surface_embed, n=hypotheses, min_separation_deg=min_separation_deg,
+                                 shift_mask=shift_mask, refine=refine, output_width_max=output_width_max)
+    if not (torch.equal(hyp[0][..., 0], ori) and torch.equal(hyp[2][..., 0].contiguous().view(torch.int32),
+                                                              dist.detach().contiguous().view(torch.int32))):
+        raise _lib.WitwError('sweep_scores: the first hypothesis is not the match (orientation or distance bits differ)')
+    return orientations, distances, torch.exp(10. * (1. - distances)), hyp
 
 
 def parse_orientation_window(text):

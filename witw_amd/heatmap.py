@@ -214,15 +214,37 @@ def heading_window(heading, fov, heading_tolerance=None):
     return (float(heading) - fov / 2. + 180.) % 360. - 180., tol
 
 
+def check_hypotheses(hypotheses, min_separation, window):
+    """The `hypotheses` / `min_separation` of sweep(), checked against each other and against the heading window
+    ((center_deg, half_width_deg) or None) -> (hypotheses, min_separation). ValueError names what is wrong."""
+    if isinstance(hypotheses, bool) or not isinstance(hypotheses, int) or not 1 <= hypotheses <= 64:
+        raise ValueError('hypotheses must be an integer in [1, 64], got %r' % (hypotheses,))
+    min_separation = float(min_separation)
+    if not 0 <= min_separation < 180:
+        raise ValueError('min_separation must lie in [0, 180) degrees, got %r' % (min_separation,))
+    if hypotheses > 1 and window is not None and window[1] == 0:
+        raise ValueError('hypotheses=%d with a trusted heading (heading_tolerance 0): the one given orientation has no second '
+                         'hypothesis; give the heading a tolerance' % hypotheses)
+    return hypotheses, min_separation
+
+
 def sweep(aoi, bounds, edge, offset, fov, sat_dir, photo_path, csv_path, tile_source=None, surface_encoder=None,
-          overhead_encoder=None, weights_dir='../../model', photo=None, batch_size=64, heading=None, heading_tolerance=None):
+          overhead_encoder=None, weights_dir='../../model', photo=None, batch_size=64, heading=None, heading_tolerance=None,
+          hypotheses=1, min_separation=22.5):
     """tools/heatmap/heatmap.py:113-187. Extra keyword arguments inject the raster source, already-loaded encoders
     or an in-memory photo (tests, services); by default everything is read from the reference's paths.
     heading (not in the reference): compass bearing of the photo's optical axis in degrees (EXIF GPSImgDirection); every tile's
     orientation search is then restricted to the shifts within heading_tolerance degrees (default DEFAULT_HEADING_TOLERANCE)
-    of it -- see heading_window for the geometry. heading_tolerance without heading is an error."""
+    of it -- see heading_window for the geometry. heading_tolerance without heading is an error.
+    hypotheses = M > 1 (not in the reference): per tile the M best orientations at least min_separation degrees apart (the rule of
+    cvig_fov.orientation_hypotheses), drawn from the heading window when there is one. The CSV then gains, behind its five
+    columns (which are unchanged): `orientation_refined`, the first orientation with the sub-bin offset of
+    cvig_fov.refine_orientation, and for j = 2..M `orientation_j` (the bin's degrees, as `orientation`), `dissimilarity_j`,
+    `score_j`; cells of hypotheses that do not exist are empty. A trusted heading (heading_tolerance = 0) is one orientation and
+    has no second hypothesis: refused together with M > 1."""
     import pandas as pd
     window = heading_window(heading, fov, heading_tolerance)
+    hypotheses, min_separation = check_hypotheses(hypotheses, min_separation, window)
     center_eastings, center_northings, windows = tile_windows(bounds, edge, offset)
     if tile_source is None:
         tile_source = GdalTileSource(os.path.join(sat_dir, names[aoi - 1] + '.tif'))
@@ -244,9 +266,20 @@ def sweep(aoi, bounds, edge, offset, fov, sat_dir, photo_path, csv_path, tile_so
         prior = {'known_shift': cvig.orientation_shift(window[0])}
     else:
         prior = {'shift_mask': None if window is None else cvig.orientation_mask(window[0], window[1])}     # one photo: one word
-    orientations, distances, scores = cvig.sweep_scores(overhead_embed, surface_embed, **prior)
+    if hypotheses == 1:
+        orientations, distances, scores = cvig.sweep_scores(overhead_embed, surface_embed, **prior)
+    else:
+        orientations, distances, scores, hyp = cvig.sweep_scores(overhead_embed, surface_embed, hypotheses=hypotheses,
+                                                                 min_separation_deg=min_separation, **prior)
     df = pd.DataFrame({'x': center_eastings, 'y': center_northings, 'orientation': orientations.cpu().numpy().reshape(-1),
                        'dissimilarity': distances.cpu().numpy().reshape(-1), 'score': scores.cpu().numpy().reshape(-1)})
+    if hypotheses > 1:
+        shift, degrees, dist_j, score_j = (t.reshape(-1, hypotheses).cpu().numpy() for t in hyp)
+        df['orientation_refined'] = degrees[:, 0]
+        for j in range(1, hypotheses):
+            df['orientation_%d' % (j + 1)] = np.where(shift[:, j] >= 0, shift[:, j] * 360. / 64 - 180., np.nan)
+            df['dissimilarity_%d' % (j + 1)] = dist_j[:, j]
+            df['score_%d' % (j + 1)] = score_j[:, j]
     df.to_csv(csv_path, index=False)
     return df
 
@@ -269,11 +302,21 @@ def main(argv=None):
                              'orientation search [Default = search all orientations]')
     parser.add_argument('--heading-tolerance', type=float, default=None,
                         help='Half width of the orientation window around --heading (deg) [Default = %g]' % DEFAULT_HEADING_TOLERANCE)
+    parser.add_argument('--hypotheses', type=int, default=1, metavar='M',
+                        help='Orientation hypotheses per tile: M > 1 adds orientation_refined and orientation_j / dissimilarity_j / '
+                             'score_j (j = 2..M) columns to the CSV [Default = 1: the reference\'s five columns]')
+    parser.add_argument('--min-separation', type=float, default=22.5, metavar='DEG',
+                        help='Least angle between two hypotheses of a tile (deg) [Default = 22.5]')
     args = parser.parse_args(argv)
     if args.heading_tolerance is not None and args.heading is None:
         parser.error('--heading-tolerance needs --heading')
+    try:
+        check_hypotheses(args.hypotheses, args.min_separation, heading_window(args.heading, args.fov, args.heading_tolerance))
+    except ValueError as e:
+        parser.error(str(e))
     sweep(args.aoi, args.bounds, args.edge, args.offset, args.fov, args.satdir, args.photopath, args.csvpath,
-          heading=args.heading, heading_tolerance=args.heading_tolerance)
+          heading=args.heading, heading_tolerance=args.heading_tolerance, hypotheses=args.hypotheses,
+          min_separation=args.min_separation)
 
 
 if __name__ == '__main__':
